@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- HMC leapfrog chain-steps/s on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,7 +15,17 @@ A "step" is one leapfrog step of every chain of the batch, exactly as the sample
 (3 x [DDIM mix VJP + score input-gradient]) and the fused momentum+position update -- nothing is skipped or
 cached.  value = N * 64 * K / (max-over-ranks time).
 
-Extra objects on the same line:
+A plain run sets up, runs one untimed step (MIOpen's first-call work; the collective out-of-memory check), W warm-up
+steps and the K timed steps, and prints the line; every object below is null in it.
+
+--dump-outputs DIR  after the timed steps, rank 0 writes what its last step handed back -- the updated positions `x`
+                    and momenta `p` and the clipped decode `xt` -- as DIR/<name>.npy (float32).  An array larger than
+                    its share of DUMP_BYTES is written as a fixed seeded sample of its elements (same indices every run);
+                    the inputs are seeded, so two builds given the same arguments can be compared output for output
+                    (at the flagship size, with MIOpen's cache warm, two processes have written identical bits; small
+                    --tiny-score runs are not bit-reproducible between processes).
+
+Extra objects on the same line, measured only with `--full`:
   roofline      the dominant HIP kernel (fused leapfrog update, 20 B/element = 5T per chain):
                 algorithmic bytes per launch / average launch duration, HIP events on the launch stream
                 over a region of back-to-back launches that rotates over buffer sets larger than the
@@ -30,9 +40,13 @@ Extra objects on the same line:
                 configs[4] (hmc_latent, 16 chains): a few end-to-end steps (`--latent` prints its full line).
   cpu_baseline  the oracle (CPU restatement, validated bit-exact against the reference) on the host cores:
                 with the U-Net in the loop (B = 1) and score-stubbed at B = 1 and B = 64.
+  full_run      sampler.hmc_chains for a few whole trajectories; single_chain: the one-chain operating point;
+                hot_path_kernels: each HIP kernel of a step timed alone; final_gather: the per-chain loss at the end
+                point (one more decode + gradient) gathered over the ranks.
 
 `--latent` prints the line of BASELINE configs[4] instead (hmc_latent: 16 chains per GPU of [3,64,64] latents, LDM
-U-Net + VQ-f4 first stage at the configs/config_ffhq_latent.yml widths, random init, inpaint_random at 256x256).
+U-Net + VQ-f4 first stage at the configs/config_ffhq_latent.yml widths, random init, inpaint_random at 256x256); its
+roofline, vq_kernel and final_gather objects are measured only with `--full`.
 """
 import argparse
 import json
@@ -52,6 +66,7 @@ B_PER_GPU, DIM, CH = 64, 256, 3
 B_LATENT, ZDIM = 16, 64          # configs[4]: batch 128 over 8 GPUs
 SIGMA0_CLI, TAU, EPS, TIMESTEPS = 0.05, 1.0, 0.05, 3
 SPECTRAL_FLOP_PER_CHAIN = 805.3e6          # 8 GEMMs x 3 channels x 33.55 MFLOP
+DUMP_BYTES = 48 << 20            # --dump-outputs: all arrays together (at 64 chains each output is 50.3 MB: sampled)
 
 
 def parse():
@@ -63,6 +78,12 @@ def parse():
                     help='chains per score-network call (activation memory); default: the whole batch -- with the fused GroupNorm '
                          'kernels the three autograd graphs of 64 chains fit the 288 GB (round 1 needed 32)')
     ap.add_argument('--batch', type=int, default=None, help='chains per GPU (BASELINE: 64; 16 with --latent)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed (x, p, xt) as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything besides the headline steps (rooflines, hot path, by_deg, full_run, '
+                         'single chain, final gather, CPU baseline); the --no-* / --kernel-only / --roofline-launches / '
+                         '--full-run-* options below shape those legs')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-by-deg', action='store_true', help='skip the sr4 / deblur_aniso legs')
     ap.add_argument('--no-full-run', action='store_true', help='skip the whole-trajectory leg (sampler.hmc_chains itself)')
@@ -70,7 +91,7 @@ def parse():
                     help='tau of the whole-trajectory leg (L = floor(tau / 0.05) leapfrog steps per trajectory; the reference '
                          'default 1.0 gives L = 20 = 33 s per trajectory at 64 chains)')
     ap.add_argument('--full-run-trajectories', type=int, default=4)
-    ap.add_argument('--kernel-only', action='store_true', help='skip the end-to-end steps (profiling the HIP kernels)')
+    ap.add_argument('--kernel-only', action='store_true', help='with --full: skip the end-to-end steps (profiling the HIP kernels)')
     ap.add_argument('--roofline-launches', type=int, default=200)
     ap.add_argument('--deg', default='inpaint_random',
                     help='degradation: inpaint_random (the BASELINE metric), sr4 (configs[2]), deblur_aniso (configs[3]), ...')
@@ -79,7 +100,10 @@ def parse():
                     help='rehearsal only: a 32-channel U-Net of the same architecture (control-flow tests; never the metric)')
     ap.add_argument('--rehearse-shared-gpu', action='store_true',
                     help='rehearsal only: all ranks use cuda:0 over gloo (checks the N>1 control flow on a 1-GPU box)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.kernel_only and not args.full:
+        ap.error('--kernel-only runs only legs of --full: add --full')
+    return args
 
 
 def build_problem(device, B, chain_id0, seed=5678, deg='inpaint_random', model=None, tiny=False, sigma0=SIGMA0_CLI):
@@ -419,8 +443,28 @@ def settle_score_chunk(eng, make_engine, args, step, world, rank, sharding, devi
         eng = make_engine(args.chunk)
 
 
-def timed_steps(eng, x, p, y, eps, sig, ws, warmup, steps, world, rank, sharding, device):
-    """The contract's timed region: W untimed steps, barrier + synchronize, K steps, synchronize + barrier, max over ranks."""
+def dump_outputs(out_dir, arrays, seed=0, budget=DUMP_BYTES):
+    """--dump-outputs: each tensor as out_dir/<name>.npy in float32 (float64 stays float64).  A tensor larger than its
+    share of the budget is written as the elements at a fixed seeded sample of flat indices (sorted), the same on every
+    run for the same shape, so two builds can be compared element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype != torch.float64:
+            t = t.float()
+        flat = t.reshape(-1)
+        k = share // flat.element_size()
+        if flat.numel() > k:
+            idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), size=k, replace=False))
+            t = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy())
+
+
+def timed_steps(eng, x, p, y, eps, sig, ws, warmup, steps, world, rank, sharding, device, end_loss=True):
+    """The contract's timed region: W untimed steps, barrier + synchronize, K steps, synchronize + barrier, max over ranks.
+    -> (seconds, per-chain loss at the end point or None without end_loss, update events, the last step's decode xt)."""
     import nhmc.kernels as K
 
     def step():
@@ -436,7 +480,7 @@ def timed_steps(eng, x, p, y, eps, sig, ws, warmup, steps, world, rank, sharding
     eng.update_events = []
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        xt, _ = step()
     torch.cuda.synchronize()
     sharding.barrier()
     dt = sharding.max_over_ranks(time.perf_counter() - t0, device)
@@ -444,10 +488,13 @@ def timed_steps(eng, x, p, y, eps, sig, ws, warmup, steps, world, rank, sharding
         K.copy_probe(mark[0], mark[1])
         torch.cuda.synchronize()
     events, eng.update_events = eng.update_events, None
+    xt = xt.clone()                                  # the engine's buffer: a later step would overwrite it
+    if not end_loss:
+        return dt, None, events, xt
     # per-chain loss at the end point for the final gather: a MID step does not sum it (the sampler reads the loss at a
     # trajectory's two ends only), so it is evaluated once here, outside the timed region
     _, loss, _, _ = eng.decode_and_grad(x, y)
-    return dt, loss.clone(), events
+    return dt, loss.clone(), events, xt
 
 
 def full_run_leg(device, prob, B, chunk, tau, trajectories):
@@ -514,7 +561,7 @@ def degradation_leg(device, deg, model, B, chunk, steps=2):
     eps = torch.full((B,), EPS, dtype=torch.float64, device=device)
     sig = torch.full((B,), 2 * sigma0 + 1.6, dtype=torch.float64, device=device)
     ws = K.leapfrog_ws(B, CH * DIM * DIM, device)
-    dt, _, _ = timed_steps(eng, prob['x'], prob['p'], prob['y'], eps, sig, ws, 1, steps, 1, 0, sharding, device)
+    dt, _, _, _ = timed_steps(eng, prob['x'], prob['p'], prob['y'], eps, sig, ws, 1, steps, 1, 0, sharding, device)
     hot = hot_path_only(device, prob, B, 20, chunk=chunk)
     out = dict(value=round(B * steps / dt, 3), unit='chain-steps/s', steps=steps, ms_per_step=round(1e3 * dt / steps, 2),
                hot_path_only=dict(value=round(hot['value'], 1), ms_per_step=round(hot['ms_per_step'], 4)),
@@ -561,7 +608,7 @@ def latent_leg(device, steps=6):
     """configs[4] inside the default run: a few hmc_latent steps at 16 chains (`bench.py --latent` is the full line)."""
     from nhmc import sharding
     lp = latent_problem(device, B_LATENT, 0, None)
-    dt, _, _ = timed_steps(lp['eng'], lp['x'], lp['p'], lp['y'], lp['eps'], lp['sig'], lp['ws'], 2, steps, 1, 0, sharding, device)   # W = 2: the first steps allocate
+    dt, _, _, _ = timed_steps(lp['eng'], lp['x'], lp['p'], lp['y'], lp['eps'], lp['sig'], lp['ws'], 2, steps, 1, 0, sharding, device)   # W = 2: the first steps allocate
     return dict(value=round(B_LATENT * steps / dt, 3), unit='chain-steps/s', steps=steps, ms_per_step=round(1e3 * dt / steps, 2),
                 chains=B_LATENT, workload='BASELINE configs[4]: hmc_latent, [%d,64,64] latents, LDM U-Net + VQ-f4 decode in the loop, '
                                           'inpaint_random at 256x256, eps=0.1 sigma_y=0.5, random-init fp32' % lp['model'].channels)
@@ -587,10 +634,16 @@ def latent_main(args):
     eng = settle_score_chunk(eng, lambda c: sampler.LeapfrogEngine(algo.score, op, None, seq, seq_next, device, chunk=c, alpha_table=table,
                                                                   image_map=model.differentiable_decode_first_stage),
                              args, lambda e: e.step(K.LF_MID, x, x, p, y, eps, sig, 1.0, ws), world, rank, sharding, device)
-    dt, loss, _ = timed_steps(eng, x, p, y, eps, sig, ws, args.warmup, args.steps, world, rank, sharding, device)
-    stats = torch.stack([loss.float(), x.reshape(B, -1).pow(2).sum(1)], dim=1).contiguous()
-    allstats = sharding.gather_chains(stats, world * B, rank, world)
-    if rank == 0:
+    dt, loss, _, xt = timed_steps(eng, x, p, y, eps, sig, ws, args.warmup, args.steps, world, rank, sharding, device,
+                                  end_loss=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(x=x, p=p, xt=xt))
+    roofline = vq = gather = None
+    if args.full:
+        stats = torch.stack([loss.float(), x.reshape(B, -1).pow(2).sum(1)], dim=1).contiguous()
+        allstats = sharding.gather_chains(stats, world * B, rank, world)
+        gather = dict(chains=int(allstats.shape[0]), loss_mean=float(allstats[:, 0].double().mean()))
+    if rank == 0 and args.full:
         roof = leapfrog_roofline(device, B_PER_GPU, args.roofline_launches)
         # the HIP kernel this path adds: codebook lookup of all 16 x 4096 latent pixels against 8192 codes
         z = K.randn_philox(zshape, 3, 0, 0, device=device).clamp_(-1, 1)
@@ -605,6 +658,15 @@ def latent_main(args):
         torch.cuda.synchronize()
         vq_us = e0.elapsed_time(e1) * 1e3 / 50
         n_pairs = B * ZDIM * ZDIM * cb.shape[0]
+        roofline = dict(bound='hbm', achieved=round(roof['achieved'], 1), peak=HBM_PEAK_GBS, unit='GB/s',
+                        frac=round(roof['achieved'] / HBM_PEAK_GBS, 4), traffic=None, kernel=roof['kernel'],
+                        avg_us=round(roof['avg_us'], 2),
+                        note='the fused update at the pixel path\'s 64 x 196 608 elements (the latent state is 16 x 12 288: launch-bound)')
+        vq = dict(kernel='k_vq_nearest<3> (nhmc_vq_nearest)', avg_us=round(vq_us, 1), pairs=n_pairs,
+                  gpairs_per_s=round(n_pairs / vq_us / 1e3, 1),
+                  note='one thread per latent pixel, codebook staged through LDS; torch would materialise a '
+                       f'{n_pairs * 4 / 2 ** 30:.1f} GiB distance matrix')
+    if rank == 0:
         line = {
             'metric': 'HMC leapfrog chain-steps/sec (FFHQ-latent 64x64x3 hmc_latent, inpaint_random at 256x256, LDM U-Net + VQ-f4 decode in the loop)',
             'value': round(world * B * args.steps / dt, 3), 'unit': 'chain-steps/s', 'n_gpus': world, 'steps': args.steps,
@@ -615,15 +677,7 @@ def latent_main(args):
                                    f'timesteps=3, {B} chains per GPU, LDM U-Net (224 ch) + VQ-f4 decoder (128 ch, 8192 codes) random-init fp32',
                        'chains_per_gpu': B, 'global_chains': world * B, 'score_chunk': args.chunk or B,
                        'parallelism': f'chains sharded over {world} rank(s), no data-path collective'},
-            'roofline': dict(bound='hbm', achieved=round(roof['achieved'], 1), peak=HBM_PEAK_GBS, unit='GB/s',
-                             frac=round(roof['achieved'] / HBM_PEAK_GBS, 4), traffic=None, kernel=roof['kernel'],
-                             avg_us=round(roof['avg_us'], 2),
-                             note='the fused update at the pixel path\'s 64 x 196 608 elements (the latent state is 16 x 12 288: launch-bound)'),
-            'vq_kernel': dict(kernel='k_vq_nearest<3> (nhmc_vq_nearest)', avg_us=round(vq_us, 1), pairs=n_pairs,
-                              gpairs_per_s=round(n_pairs / vq_us / 1e3, 1),
-                              note='one thread per latent pixel, codebook staged through LDS; torch would materialise a '
-                                   f'{n_pairs * 4 / 2 ** 30:.1f} GiB distance matrix'),
-            'final_gather': dict(chains=int(allstats.shape[0]), loss_mean=float(allstats[:, 0].double().mean())),
+            'roofline': roofline, 'vq_kernel': vq, 'final_gather': gather,
             'cpu_baseline': None,
         }
         print(json.dumps(line), flush=True)
@@ -688,9 +742,13 @@ def main():
         eng = settle_score_chunk(eng, lambda c: sampler.LeapfrogEngine(prob['algo'].score, prob['op'], prob['b'], prob['seq'],
                                                                       prob['seq_next'], device, chunk=c),
                                  args, lambda e: e.step(K.LF_MID, x, x, p, y, eps, sig, 1.0, ws), world, rank, sharding, device)
-        dt, loss, in_situ = timed_steps(eng, x, p, y, eps, sig, ws, args.warmup, args.steps, world, rank, sharding, device)
+        dt, loss, in_situ, xt = timed_steps(eng, x, p, y, eps, sig, ws, args.warmup, args.steps, world, rank, sharding, device,
+                                            end_loss=args.full)
         ms_per_step = 1e3 * dt / args.steps
         value = world * B * args.steps / dt
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, dict(x=x, p=p, xt=xt))
+    if args.full and not args.kernel_only:
         # the one collective of the design: per-chain results gathered once, after the timed region (RCCL over xGMI at N > 1)
         stats = torch.stack([loss.float(), x.reshape(B, -1).pow(2).sum(1)], dim=1).contiguous()
         torch.cuda.synchronize()
@@ -700,8 +758,8 @@ def main():
         torch.cuda.synchronize()
         gather = dict(chains=int(allstats.shape[0]), ms=round(1e3 * (time.perf_counter() - t0), 3),
                       loss_mean=float(allstats[:, 0].double().mean()))
-    roof = hot = cpu = single = by_deg = full = None
-    if rank == 0:
+    roofline = hot = ktable = cpu = single = by_deg = full = None
+    if rank == 0 and args.full:
         roof = leapfrog_roofline(device, B, args.roofline_launches)
         hot = hot_path_only(device, prob, B, 20, chunk=args.chunk)
         ktable = kernel_table(device, prob, B) if args.deg == 'inpaint_random' else None
@@ -739,6 +797,7 @@ def main():
             by_deg['hmc_latent'] = latent_leg(device)
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline()
+    if rank == 0:
         line = {
             'metric': f'HMC leapfrog chain-steps/sec (256x256x3 FFHQ {args.deg}, U-Net score in the loop)',
             'value': None if value is None else round(value, 3), 'unit': 'chain-steps/s', 'n_gpus': world,

@@ -47,3 +47,41 @@ def test_only_the_cpu_baseline_leg_touches_the_oracle():
     lo, hi = src.index('def cpu_baseline'), src.index('def single_chain_rate')
     code_uses = [u for u in uses if 'import' in src[src.rfind('\n', 0, u):src.find('\n', u)]]
     assert code_uses and all(lo < u < hi for u in code_uses)
+
+
+def test_full_and_dump_outputs_flags(monkeypatch, tmp_path):
+    import pytest
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '4', '--warmup', '2'])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 4, 2)        # a plain run: headline steps only
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', str(tmp_path)])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == str(tmp_path)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--kernel-only'])                 # its legs are --full legs
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_writes_whole_small_arrays_and_a_fixed_sample_of_large_ones(tmp_path):
+    import numpy as np
+    import torch
+    import bench
+    small = torch.arange(24, dtype=torch.float32).reshape(2, 3, 4)
+    big = torch.randn(3 * 2 ** 20, generator=torch.Generator().manual_seed(1))
+    f64 = torch.linspace(0, 1, 10, dtype=torch.float64)
+    half = torch.ones(5, dtype=torch.float16)
+    budget = 4 * 2 ** 20
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), dict(small=small, big=big, f64=f64, half=half), budget=budget)
+    got = {n: np.load(tmp_path / 'a' / f'{n}.npy') for n in ('small', 'big', 'f64', 'half')}
+    assert got['small'].dtype == np.float32 and got['small'].shape == (2, 3, 4) and (got['small'] == small.numpy()).all()
+    assert got['f64'].dtype == np.float64 and (got['f64'] == f64.numpy()).all()
+    assert got['half'].dtype == np.float32 and (got['half'] == 1).all()
+    share = budget // 4
+    assert got['big'].dtype == np.float32 and got['big'].nbytes == share               # sampled down to its share
+    assert np.isin(got['big'], big.numpy()).all()
+    assert (np.load(tmp_path / 'b' / 'big.npy') == got['big']).all()                    # the same indices every run
+    total = sum(os.path.getsize(tmp_path / 'a' / f'{n}.npy') for n in got)
+    assert total <= budget + 4 * 256                                                    # + the .npy headers
+    assert bench.DUMP_BYTES + 3 * 256 <= 64 * 10 ** 6                                   # the contract: at most 64 MB

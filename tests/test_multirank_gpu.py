@@ -57,7 +57,7 @@ def test_cli_results_do_not_depend_on_the_number_of_ranks(tmp_path):
 
 def test_bench_two_rank_control_flow_on_the_shared_gpu(tmp_path):
     out = _torchrun(2, os.path.join(ROOT, 'bench.py'),
-                    ['--gpus', '2', '--steps', '1', '--warmup', '1', '--batch', '4', '--chunk', '2', '--tiny-score',
+                    ['--gpus', '2', '--full', '--steps', '1', '--warmup', '1', '--batch', '4', '--chunk', '2', '--tiny-score',
                      '--rehearse-shared-gpu', '--no-cpu-baseline', '--roofline-launches', '8'], ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
@@ -69,7 +69,7 @@ def test_bench_ranks_halve_the_score_chunk_together(tmp_path):
     """An out-of-memory error on ONE rank (injected on rank 1) makes EVERY rank retry with half the score chunk, so the
     barriers of the timed region still line up (bench.settle_score_chunk)."""
     out = _torchrun(2, os.path.join(ROOT, 'bench.py'),
-                    ['--gpus', '2', '--steps', '1', '--warmup', '1', '--batch', '4', '--chunk', '4', '--tiny-score',
+                    ['--gpus', '2', '--full', '--steps', '1', '--warmup', '1', '--batch', '4', '--chunk', '4', '--tiny-score',
                      '--rehearse-shared-gpu', '--no-cpu-baseline', '--roofline-launches', '8'], ROOT,
                     extra_env={'NHMC_BENCH_FAKE_OOM': '1'})
     assert out.returncode == 0, out.stderr[-2000:]
@@ -89,7 +89,7 @@ def _bare_bench(args, extra_env=None):
 
 @pytest.mark.parametrize('n', [2, 4])        # 4 ranks + this process = 5 processes on the card (the box allows 6)
 def test_bare_bench_command_starts_its_own_ranks(n):
-    out = _bare_bench(['--gpus', str(n), '--steps', '1', '--warmup', '1', '--batch', '2', '--chunk', '2', '--tiny-score',
+    out = _bare_bench(['--gpus', str(n), '--full', '--steps', '1', '--warmup', '1', '--batch', '2', '--chunk', '2', '--tiny-score',
                        '--rehearse-shared-gpu', '--no-cpu-baseline', '--roofline-launches', '8'])
     assert out.returncode == 0, out.stderr[-2000:]
     assert f'--gpus {n} without WORLD_SIZE: launching' in out.stderr
