@@ -328,6 +328,55 @@ int nhmc_data_srconv_vjp(const float* xt_next, const float* y, const float* V1, 
                          int n_chains, int channels, int dim, int small_dim, nhmc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Nonlinear operators of --algo hmc           main_sampling.py:315-322, :693-695 / :709-711
+ *
+ * HDR (obs_functions/Hfuncs.py:406-445): H(x) = clip(x / 0.5, -1, 1) elementwise, M = N, y dense [n_chains][N].
+ * x / 0.5 is exactly 2 x in fp32, so all elementwise outputs are the reference's bits.  Gradient masks follow torch's
+ * clamp backward (the gradient passes where the argument lies inside OR ON the bounds):
+ *   nhmc_hdr_H       : y = clip(2 x) over n_total elements (n_total % 4 == 0).
+ *   nhmc_data_hdr    : loss partials of sum (y - clip(2 v))^2 (nhmc_data_tiles(n_elem) per chain), v = clip(xt) when
+ *                      apply_clip, and g_xt = ((-2 r) 1[|2 v| <= 1]) 2 [1[|xt| <= 1]]   -- autograd of :694-695.
+ *   nhmc_mix_bwd_hdr : nhmc_data_hdr on the clipped decode of the LAST DDIM step fused with that step's VJP
+ *                      (as nhmc_ddim_mix_bwd_inpaint: R xt, e, y; W g_xt, g_e; nhmc_leapfrog_tiles(n_elem) partials).
+ * ---------------------------------------------------------------------------------- */
+int nhmc_hdr_H(const float* x, float* y, int64_t n_total, nhmc_stream_t stream);
+int nhmc_data_hdr(const float* xt, const float* y, int apply_clip, float* g_xt, double* loss_ws, int n_chains,
+                  int64_t n_elem, nhmc_stream_t stream);
+int nhmc_mix_bwd_hdr(const float* xt, const float* e, int e_channels, const float* at, const float* at_next,
+                     const float* y, float* g_xt, float* g_e, int fill_sigma, double* loss_ws, int n_chains,
+                     int channels, int64_t hw, nhmc_stream_t stream);
+
+/* Phase retrieval (obs_functions/Hfuncs.py:318-366, fft2_m / ifft2_m :8-19): H(x) = |fft2c(pad(x, pad))| per channel
+ * plane, centred, norm = 'ortho', n = dim + 2 pad; y natural [n_chains][C][n][n], M = C n n.  The zero padding makes the
+ * padded centred DFT two rectangular real sandwiches: with F the centred ortho DFT matrix of size n and
+ * Fc = F[:, pad:pad+dim] = Cm + i Sm ([n][dim]),
+ *     Re Y = Cm X Cm^T - Sm X Sm^T,   Im Y = Cm X Sm^T + Sm X Cm^T,   H(x) = sqrt(Re^2 + Im^2),
+ * run on the fp32 MFMA (dim % 32 == 0, (2 pad) % 32 == 0; any such n, no power of two needed).
+ * fac: float[6 n dim], packed  [Cm^T | Sm^T] ([dim][2n]),  [Cm | Sm] ([n][2 dim]),  [Sm ; Cm] ([2n][dim]).
+ * tmp: float[nhmc_phase_tmp_floats(...)] for every entry below.
+ *   nhmc_phase_H       : mode 0: out = H(x) [n_chains][C][n][n];  mode 1: out = [Re Y ; Im Y] [n_chains][C][2][n][n].
+ *   nhmc_phase_pinv    : H^+(y) = crop(|ifft2c(y)|) -> [n_chains][C][dim][dim] (the factors conjugated).
+ *   nhmc_phase_adjoint : the exact adjoint of x -> [Re Y ; Im Y]: w [n_chains][C][2][n][n] -> [n_chains][C][dim][dim].
+ *   nhmc_data_phase    : loss partials of sum (y - |Y(v)|)^2 (nhmc_phase_tiles per chain) and its gradient, the adjoint
+ *                        applied to -2 (y - |Y|) Y / |Y| (0 where |Y| = 0, torch's sgn(0)), times the clip mask of xt when
+ *                        apply_clip -- autograd of :694-695 through the FFT, as four MFMA launches.
+ *   nhmc_data_phase_vjp: the same on xt_next (the clipped decode of the LAST DDIM step) with that step's VJP in the
+ *                        last product's epilogue (as nhmc_data_spectral_vjp): writes g_xt and channels [0, C) of g_e. */
+int nhmc_phase_tiles(int channels, int dim, int pad);
+size_t nhmc_phase_tmp_floats(int n_chains, int channels, int dim, int pad);
+int nhmc_phase_H(const float* x, const float* fac, int mode, float* out, float* tmp, int n_chains, int channels, int dim,
+                 int pad, nhmc_stream_t stream);
+int nhmc_phase_pinv(const float* y, const float* fac, float* out, float* tmp, int n_chains, int channels, int dim, int pad,
+                    nhmc_stream_t stream);
+int nhmc_phase_adjoint(const float* w, const float* fac, float* out, float* tmp, int n_chains, int channels, int dim,
+                       int pad, nhmc_stream_t stream);
+int nhmc_data_phase(const float* xt, const float* y, const float* fac, int apply_clip, float* g_xt, double* loss_ws,
+                    float* tmp, int n_chains, int channels, int dim, int pad, nhmc_stream_t stream);
+int nhmc_data_phase_vjp(const float* xt_next, const float* y, const float* fac, const float* xt, const float* e,
+                        int e_channels, const float* at, const float* at_next, float* g_xt, float* g_e, double* loss_ws,
+                        float* tmp, int n_chains, int channels, int dim, int pad, nhmc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * a5  Hamiltonian                          main_sampling.py:697,717-718
  *   H = (0.5*Sx + (1/(2 sigma_y^2))*loss) + (0.5*Sp)*m^-1, per chain, in the reference's fp32
  *   op order on fp32-rounded sums; Sx,Sp summed (fixed order, fp64) from the leapfrog partials.

@@ -64,6 +64,16 @@ SIGNATURES = {
     'nhmc_srconv_tiles': (I, [I, I]),
     'nhmc_data_srconv': (I, [P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, P]),
     'nhmc_data_srconv_vjp': (I, [P, P, P, P, P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, P]),
+    'nhmc_hdr_H': (I, [P, P, I64, P]),
+    'nhmc_data_hdr': (I, [P, P, I, P, P, I, I64, P]),
+    'nhmc_mix_bwd_hdr': (I, [P, P, I, P, P, P, P, P, I, P, I, I, I64, P]),
+    'nhmc_phase_tiles': (I, [I, I, I]),
+    'nhmc_phase_tmp_floats': (SZ, [I, I, I, I]),
+    'nhmc_phase_H': (I, [P, P, I, P, P, I, I, I, I, P]),
+    'nhmc_phase_pinv': (I, [P, P, P, P, I, I, I, I, P]),
+    'nhmc_phase_adjoint': (I, [P, P, P, P, I, I, I, I, P]),
+    'nhmc_data_phase': (I, [P, P, P, I, P, P, P, I, I, I, I, P]),
+    'nhmc_data_phase_vjp': (I, [P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, P]),
     'nhmc_hamiltonian': (I, [P, I, P, P, D, P, P, I, P]),
     'nhmc_metropolis': (I, [P, P, P, P, P, P, I, P]),
     'nhmc_schedule_begin': (I, [P, P, P, P, P, P, D, I, I, I, P]),

@@ -5,8 +5,10 @@
 
 Same flag names and defaults; unknown flags are ignored as in the reference (`parse_known_args`, :1031).  Only
 `--algo hmc` (and `--algo hmc_latent` through `main_latent`, the counterpart of main_sampling_latent.py:791-918 with
-its own defaults: `--epsilon 0.1`, no `--annealed_temp`) and the degradations on the hot path are served; anything
-else raises `NotImplementedError` (the reference's own error for an unknown algo, :256-257).  Additions, all optional: `--chains` images are
+its own defaults: `--epsilon 0.1`, no `--annealed_temp`) and the degradations on the hot path are served -- the nine
+linear ones and the two nonlinear ones that need nothing from outside, `hdr` and `phase_retrieval` (matched as the
+reference matches them, `'hdr' in deg` / `'phase' in deg`, :315-322; `sigma_0` is doubled for them too, :348); anything
+else (`deblur_nonlinear` needs the external bkse network) raises `NotImplementedError` (the reference's own error for an unknown algo, :256-257).  Additions, all optional: `--chains` images are
 sampled in parallel as independent chains (the reference is batch-1), `--score_chunk` bounds the U-Net batch,
 `--synthetic K` uses K synthetic images when no dataset folder is present, `--philox` switches the noise to the
 shard-invariant counter-based generator.  Under torchrun the images are sharded over ranks and the per-image

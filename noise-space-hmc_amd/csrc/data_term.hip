@@ -314,3 +314,88 @@ extern "C" int nhmc_sum_partials(const double* ws, int tiles, int stride, int of
                      tiles, stride, offset, n_chains, out);
   return nhmc_launch_status();
 }
+
+// ---- HDR (obs_functions/Hfuncs.py:406-445) ---------------------------------------------------------------------
+// H(x) = clip(x / 0.5, -1, 1) elementwise: a NONLINEAR operator, M = N.  x / 0.5 is exactly 2 x in fp32 (and autograd's
+// grad / 0.5 exactly 2 grad), so every elementwise value is the reference's bits.  The gradient follows torch's clamp
+// backward: it passes where the clamp's argument lies inside OR ON the bounds (nhmc_in1), so x = +-0.5 keeps its
+// gradient and x = 0.75 or +-1 does not:
+//   loss_b = sum (y_b - clip(2 v))^2,  v = clip(xt) (apply_clip) or xt,
+//   g_xt   = ((-2 r) * 1[-1 <= 2 v <= 1]) * 2  [* 1[-1 <= xt <= 1]].
+namespace {
+
+__device__ __forceinline__ float hdr_fwd(float v) { return nhmc_clip1(2.0f * v); }
+// d (y - clip(2 v))^2 / d v and the squared residual, in autograd's op order
+__device__ __forceinline__ float hdr_grad(float v, float yv, double& acc) {
+  const float r = yv - hdr_fwd(v);
+  acc += (double)(r * r);
+  return ((-(2.0f * r)) * nhmc_in1(2.0f * v)) * 2.0f;
+}
+
+__global__ __launch_bounds__(NHMC_BLOCK) void k_hdr_H(const float4* __restrict__ x, float4* __restrict__ y, int64_t n4) {
+  const int64_t t0 = (int64_t)blockIdx.x * (NHMC_BLOCK * NHMC_VEC_PER_THREAD) + threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < NHMC_VEC_PER_THREAD; ++i) {
+    const int64_t q = t0 + (int64_t)i * NHMC_BLOCK;
+    if (q >= n4) continue;
+    const float4 v = nhmc_ldnt(&x[q]);
+    nhmc_stnt(&y[q], make_float4(hdr_fwd(v.x), hdr_fwd(v.y), hdr_fwd(v.z), hdr_fwd(v.w)));
+  }
+}
+
+__global__ __launch_bounds__(NHMC_BLOCK) void k_data_hdr(
+    const float4* __restrict__ xt, const float4* __restrict__ y, int apply_clip, float4* __restrict__ g_xt,
+    double* __restrict__ loss_ws, int64_t n4) {
+  const int chain = blockIdx.y;
+  const int64_t base = (int64_t)chain * n4;
+  const int64_t t0 = (int64_t)blockIdx.x * (NHMC_BLOCK * NHMC_VEC_PER_THREAD) + threadIdx.x;
+  double acc = 0.0;                       // fp32 squares summed in fp64, as the other data terms
+  float4 xv[NHMC_VEC_PER_THREAD], yv[NHMC_VEC_PER_THREAD];
+#pragma unroll
+  for (int i = 0; i < NHMC_VEC_PER_THREAD; ++i) {
+    const int64_t q = t0 + (int64_t)i * NHMC_BLOCK;
+    if (q < n4) { xv[i] = nhmc_ldnt(&xt[base + q]); yv[i] = nhmc_ldnt(&y[base + q]); }
+  }
+#pragma unroll
+  for (int i = 0; i < NHMC_VEC_PER_THREAD; ++i) {
+    const int64_t q = t0 + (int64_t)i * NHMC_BLOCK;
+    if (q >= n4) continue;
+    const float* xe = reinterpret_cast<const float*>(&xv[i]);
+    const float* ye = reinterpret_cast<const float*>(&yv[i]);
+    float4 o;
+    float* oe = reinterpret_cast<float*>(&o);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float gr = hdr_grad(apply_clip ? nhmc_clip1(xe[c]) : xe[c], ye[c], acc);
+      if (apply_clip) gr = gr * nhmc_in1(xe[c]);
+      oe[c] = gr;
+    }
+    nhmc_stnt(&g_xt[base + q], o);
+  }
+  __shared__ double red[4];
+  double v[1] = {acc};
+  nhmc_block_sum<1>(v, red);
+  if (threadIdx.x == 0) loss_ws[(int64_t)chain * gridDim.x + blockIdx.x] = v[0];
+}
+
+}  // namespace
+
+extern "C" int nhmc_hdr_H(const float* x, float* y, int64_t n_total, nhmc_stream_t stream) {
+  if (!x || !y || n_total <= 0) return NHMC_ERR_ARG;
+  if ((n_total & 3) || !nhmc_aligned16(x) || !nhmc_aligned16(y)) return NHMC_ERR_ALIGN;
+  const int64_t tiles = (n_total + NHMC_TILE - 1) / NHMC_TILE;
+  if (tiles > 0x7fffffff) return NHMC_ERR_SHAPE;
+  NHMC_LAUNCH(k_hdr_H, dim3((unsigned)tiles), dim3(NHMC_BLOCK), 0, nhmc_s(stream), (const float4*)x, (float4*)y, n_total / 4);
+  return nhmc_launch_status();
+}
+
+extern "C" int nhmc_data_hdr(const float* xt, const float* y, int apply_clip, float* g_xt, double* loss_ws, int n_chains,
+                             int64_t n_elem, nhmc_stream_t stream) {
+  if (!xt || !y || !g_xt || !loss_ws || n_chains <= 0 || n_elem <= 0) return NHMC_ERR_ARG;
+  if (n_chains > 65535) return NHMC_ERR_SHAPE;
+  if ((n_elem & 3) || !nhmc_aligned16(xt) || !nhmc_aligned16(y) || !nhmc_aligned16(g_xt)) return NHMC_ERR_ALIGN;
+  dim3 grid((unsigned)nhmc_data_tiles(n_elem), (unsigned)n_chains), block(NHMC_BLOCK);
+  NHMC_LAUNCH(k_data_hdr, grid, block, 0, nhmc_s(stream), (const float4*)xt, (const float4*)y, apply_clip, (float4*)g_xt,
+              loss_ws, n_elem / 4);
+  return nhmc_launch_status();
+}

@@ -484,6 +484,66 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_sr4(
   if (threadIdx.x == 0) loss_ws[((int64_t)chain * gridDim.y + plane) * gridDim.x + blockIdx.x] = v[0];
 }
 
+// Last DDIM step VJP fused with the HDR data term (obs_functions/Hfuncs.py:406-445, H = clip(x / 0.5, -1, 1)): the shape
+// of k_mix_bwd_inpaint with a dense observation -- R xt, e[:C], y; W g_xt, g_e = 5T, one launch.  The clipped decode is
+// recomputed in registers (k_mix_fwd's bits), r = y - clip(2 * decode), and the upstream gradient passes three clamp
+// masks in autograd's order: the operator's (argument inside or on +-1), the final clip's, the x0 clip's.
+__global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_hdr(
+    const float4* __restrict__ xt, const float4* __restrict__ e, int64_t e_stride4, const float* __restrict__ at,
+    const float* __restrict__ at_next, const float4* __restrict__ y, float4* __restrict__ g_xt,
+    float4* __restrict__ g_e, double* __restrict__ loss_ws, int64_t n4, int fill_sigma) {
+  const int chain = blockIdx.y;
+  const Coef k = coef(at, at_next, chain);
+  const int64_t base = (int64_t)chain * n4, ebase = (int64_t)chain * e_stride4;
+  const int64_t t0 = (int64_t)blockIdx.x * (NHMC_BLOCK * NHMC_VEC_PER_THREAD) + threadIdx.x;
+  double acc = 0.0;                                          // fp32 squares summed in fp64: independent of the tiling
+  float4 xv[NHMC_VEC_PER_THREAD], ev[NHMC_VEC_PER_THREAD], yv[NHMC_VEC_PER_THREAD];
+#pragma unroll
+  for (int i = 0; i < NHMC_VEC_PER_THREAD; ++i) {
+    const int64_t q = t0 + (int64_t)i * NHMC_BLOCK;
+    if (q < n4) { xv[i] = nhmc_ldnt(&xt[base + q]); ev[i] = nhmc_ldnt(&e[ebase + q]); yv[i] = nhmc_ldnt(&y[base + q]); }
+  }
+#pragma unroll
+  for (int i = 0; i < NHMC_VEC_PER_THREAD; ++i) {
+    const int64_t q = t0 + (int64_t)i * NHMC_BLOCK;
+    if (q >= n4) continue;
+    const float* xe = reinterpret_cast<const float*>(&xv[i]);
+    const float* ee = reinterpret_cast<const float*>(&ev[i]);
+    const float* ye = reinterpret_cast<const float*>(&yv[i]);
+    float4 ox, oe;
+    float* gx = reinterpret_cast<float*>(&ox);
+    float* gee = reinterpret_cast<float*>(&oe);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float u = (xe[c] - ee[c] * k.c1) / k.c2;
+      const float pre = k.c3 * nhmc_clip1(u) + k.c4 * ee[c];    // decode before the final clip
+      const float arg = 2.0f * nhmc_clip1(pre);                 // x / 0.5: exact in fp32
+      const float r = ye[c] - nhmc_clip1(arg);
+      acc += (double)(r * r);
+      float gin = ((-(2.0f * r)) * nhmc_in1(arg)) * 2.0f;       // clamp backward, then grad / 0.5
+      gin = gin * nhmc_in1(pre);                                 // final clip mask
+      const float gu = ((gin * k.c3) * nhmc_in1(u)) / k.c2;
+      gx[c] = gu;
+      gee[c] = k.c4 * gin + (-gu) * k.c1;
+    }
+    nhmc_stnt(&g_xt[base + q], ox);
+    nhmc_stnt(&g_e[ebase + q], oe);
+  }
+  const int64_t extra = fill_sigma ? e_stride4 - n4 : 0;
+  if (extra > 0) {
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int i = 0; i < NHMC_VEC_PER_THREAD; ++i) {
+      const int64_t q = t0 + (int64_t)i * NHMC_BLOCK;
+      if (q < extra) nhmc_stnt(&g_e[ebase + n4 + q], z);
+    }
+  }
+  __shared__ double red[4];
+  double v[1] = {acc};
+  nhmc_block_sum<1>(v, red);
+  if (threadIdx.x == 0) loss_ws[(int64_t)chain * gridDim.x + blockIdx.x] = v[0];
+}
+
 bool bad_shape(int n_chains, int channels, int64_t hw, int e_channels) {
   return n_chains <= 0 || n_chains > 65535 || channels <= 0 || hw <= 0 ||
          (e_channels != channels && e_channels != 2 * channels);
@@ -629,5 +689,22 @@ extern "C" int nhmc_ddim_mix_bwd_sr(const float* xt, const float* e, int e_chann
     default: NHMC_BSR(16); break;
   }
 #undef NHMC_BSR
+  return nhmc_launch_status();
+}
+
+// Last-step VJP fused with the HDR data term; y dense [n_chains][C*hw]; loss partials: nhmc_leapfrog_tiles(n_elem) per chain.
+extern "C" int nhmc_mix_bwd_hdr(const float* xt, const float* e, int e_channels, const float* at, const float* at_next,
+                                const float* y, float* g_xt, float* g_e, int fill_sigma, double* loss_ws, int n_chains,
+                                int channels, int64_t hw, nhmc_stream_t stream) {
+  if (!xt || !e || !at || !at_next || !y || !g_xt || !g_e || !loss_ws) return NHMC_ERR_ARG;
+  if (bad_shape(n_chains, channels, hw, e_channels)) return NHMC_ERR_SHAPE;
+  const int64_t n_elem = (int64_t)channels * hw;
+  if ((n_elem & 3) || !nhmc_aligned16(xt) || !nhmc_aligned16(e) || !nhmc_aligned16(y) || !nhmc_aligned16(g_xt) ||
+      !nhmc_aligned16(g_e))
+    return NHMC_ERR_ALIGN;
+  dim3 grid((unsigned)nhmc_leapfrog_tiles(n_elem), (unsigned)n_chains), block(NHMC_BLOCK);
+  NHMC_LAUNCH(k_mix_bwd_hdr, grid, block, 0, nhmc_s(stream), (const float4*)xt, (const float4*)e,
+              (int64_t)e_channels * hw / 4, at, at_next, (const float4*)y, (float4*)g_xt, (float4*)g_e, loss_ws, n_elem / 4,
+              fill_sigma);
   return nhmc_launch_status();
 }

@@ -867,3 +867,279 @@ extern "C" int nhmc_data_srconv_vjp(const float* xt_next, const float* y, const 
   return srconv_chain<false>(xt_next, y, f, xt, &vj, g_xt, loss_ws, tmp, n_chains * channels, channels, dim, small_dim,
                              nhmc_s(stream));
 }
+
+// ---- phase retrieval (obs_functions/Hfuncs.py:318-366) ----------------------------------------------------------
+// H(x) = | fft2c(pad(x, p)) | per channel plane, centred and orthonormal, n = d + 2 p.  The padding is zero, so with F
+// the centred ortho DFT matrix of size n, Fc = F[:, p:p+d] = Cm + i Sm (real [n][d] factors built on the host in float64),
+//     Re Y = Cm X Cm^T - Sm X Sm^T,      Im Y = Cm X Sm^T + Sm X Cm^T,      H(x) = sqrt(Re^2 + Im^2):
+// rectangular real sandwiches on the fp32 MFMA, for any n % 32 == 0 (384 at 256 x 256 is no power of two) and with an
+// exact adjoint.  Four launches per data term, all of the form OUT = IN^T S (no transposed operand anywhere):
+//   1  P  = X^T [Cm^T | Sm^T]              [d][2n]     k_sgemm, K = d          (P = [(Cm X)^T | (Sm X)^T])
+//   2  Re, Im from P (k_cgemm below, both accumulated in the MFMA accumulators); epilogue: a = |Y|, r = y - a, loss
+//      partial, W = r Y / a (0 where a = 0: torch's sgn(0)) -> [2][n][n]; Re and Im themselves never reach memory
+//   3  U2 = Wim^T Cm - Wre^T Sm,  U1 = Wim^T Sm + Wre^T Cm    [2][n][d]   k_cgemm again (plain pair epilogue)
+//   4  G  = U2^T Sm + U1^T Cm = Cm^T Wre Cm - Sm^T Wre Sm + Cm^T Wim Sm + Sm^T Wim Cm   [d][d]   k_sgemm, K = 2n,
+//      with the -2 / clip mask (EPI_GRAD) or the last DDIM step's VJP (EPI_VJP) in its epilogue.
+// FLOP per plane: 2 d d 2n + 4 (2 n n d) + 4 (2 n n d) + 2 d d 2n = 0.8 GFLOP at d = 256.
+//
+// k_cgemm: one complex-shaped product  P = A^T SA - B^T SB,  Q = A^T SB + B^T SA   (A, B: [K][R] rows of ld_in floats
+// per image; SA, SB: [K][C] rows of ld_s floats, shared).  Block tile T x T = (32 NW)^2, one 32 x 32 MFMA tile of P and
+// of Q per wave, K step 32, the four operand tiles staged through LDS as in k_sgemm (T = 64: 32 KB, four blocks per CU).
+enum { PEPI_PAIR = 0, PEPI_MOD = 1, PEPI_RESID = 2 };
+namespace {
+
+template <int NW, int EPI>
+__global__ __launch_bounds__(64 * NW * NW) void k_cgemm(
+    const float* __restrict__ A, const float* __restrict__ B, int ld_in, int64_t in_stride,
+    const float* __restrict__ SA, const float* __restrict__ SB, int ld_s, float* __restrict__ OUT,
+    const float* __restrict__ Y, double* __restrict__ ws, int K, int R, int C) {
+  constexpr int T = 32 * NW, NT = 64 * NW * NW;
+  constexpr int NV = (BK * T / 4) / NT;          // float4 per thread per operand tile
+  __shared__ float L[4 * BK * T];                // four operand tiles in the main loop, the P and Q slabs in the epilogue
+  float* const As = L;
+  float* const Bs = L + BK * T;
+  float* const SAs = L + 2 * BK * T;
+  float* const SBs = L + 3 * BK * T;
+
+  const int tiles_c = C / T, tiles_img = (R / T) * tiles_c;
+  const int total = gridDim.x;
+  int logical = blockIdx.x;
+  if ((total & 7) == 0) logical = (logical & 7) * (total >> 3) + (logical >> 3);   // the tiles of an image share an XCD
+  const int img = logical / tiles_img, tile = logical % tiles_img;
+  const int tr = (tile / tiles_c) * T, tc = (tile % tiles_c) * T;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wi = wave / NW, wj = wave % NW;
+  const int lr = lane & 31, lh = lane >> 5;
+  const float* __restrict__ Aimg = A + (int64_t)img * in_stride;
+  const float* __restrict__ Bimg = B + (int64_t)img * in_stride;
+
+  f32x16 P, Q;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { P[r] = 0.0f; Q[r] = 0.0f; }
+
+  for (int k0 = 0; k0 < K; k0 += BK) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int idx = tid + v * NT, kk = idx / (T / 4), c4 = idx % (T / 4);
+      const int64_t io = (int64_t)(k0 + kk) * ld_in + tr + c4 * 4, so = (int64_t)(k0 + kk) * ld_s + tc + c4 * 4;
+      const nhmc_v4f pa = *reinterpret_cast<const nhmc_v4f*>(&Aimg[io]);
+      const nhmc_v4f pb = *reinterpret_cast<const nhmc_v4f*>(&Bimg[io]);
+      const nhmc_v4f qa = *reinterpret_cast<const nhmc_v4f*>(&SA[so]);
+      const nhmc_v4f qb = *reinterpret_cast<const nhmc_v4f*>(&SB[so]);
+      *reinterpret_cast<nhmc_v4f*>(&As[kk * T + c4 * 4]) = pa;
+      *reinterpret_cast<nhmc_v4f*>(&Bs[kk * T + c4 * 4]) = pb;
+      *reinterpret_cast<nhmc_v4f*>(&SAs[kk * T + c4 * 4]) = qa;
+      *reinterpret_cast<nhmc_v4f*>(&SBs[kk * T + c4 * 4]) = qb;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int kk = 0; kk < BK; kk += 2) {
+      const float a = As[(kk + lh) * T + wi * 32 + lr], b = Bs[(kk + lh) * T + wi * 32 + lr];
+      const float sa = SAs[(kk + lh) * T + wj * 32 + lr], sb = SBs[(kk + lh) * T + wj * 32 + lr];
+      P = __builtin_amdgcn_mfma_f32_32x32x2f32(a, sa, P, 0, 0, 0);
+      Q = __builtin_amdgcn_mfma_f32_32x32x2f32(a, sb, Q, 0, 0, 0);
+      P = __builtin_amdgcn_mfma_f32_32x32x2f32(-b, sb, P, 0, 0, 0);
+      Q = __builtin_amdgcn_mfma_f32_32x32x2f32(b, sa, Q, 0, 0, 0);
+    }
+    __syncthreads();
+  }
+
+  // ---- epilogue: one slab of 32 rows x T columns of P and of Q through LDS, then 16-byte row accesses ----
+  static_assert(2 * 32 * T <= 4 * BK * T, "the P and Q slabs must fit the operand tiles");
+  float* const LP = L;
+  float* const LQ = L + 32 * T;
+  const int64_t plane = (int64_t)R * C;
+  float* __restrict__ out_img = OUT + (int64_t)img * plane * (EPI == PEPI_MOD ? 1 : 2);
+  const float* __restrict__ y_img = EPI == PEPI_RESID ? Y + (int64_t)img * plane : nullptr;
+  double lsum = 0.0;                                    // fp32 squares summed in fp64
+  constexpr int SLAB_V = (32 * T / 4) / NT;
+  for (int h = 0; h < NW; ++h) {
+    if (wi == h) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * lh, col = wj * 32 + lr;
+        LP[row * T + col] = P[r];
+        LQ[row * T + col] = Q[r];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int v = 0; v < SLAB_V; ++v) {
+      const int idx = tid + v * NT, row = idx / (T / 4), c4i = idx % (T / 4);
+      const int64_t off = (int64_t)(tr + h * 32 + row) * C + tc + c4i * 4;
+      nhmc_v4f p = *reinterpret_cast<const nhmc_v4f*>(&LP[row * T + c4i * 4]);
+      nhmc_v4f q = *reinterpret_cast<const nhmc_v4f*>(&LQ[row * T + c4i * 4]);
+      if (EPI == PEPI_PAIR) {
+        *reinterpret_cast<nhmc_v4f*>(&out_img[off]) = p;
+        *reinterpret_cast<nhmc_v4f*>(&out_img[plane + off]) = q;
+      } else {
+        nhmc_v4f a;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[j] = sqrtf(p[j] * p[j] + q[j] * q[j]);
+        if (EPI == PEPI_MOD) {
+          *reinterpret_cast<nhmc_v4f*>(&out_img[off]) = a;
+        } else {
+          const nhmc_v4f yv = *reinterpret_cast<const nhmc_v4f*>(&y_img[off]);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float r = yv[j] - a[j];
+            lsum += (double)(r * r);
+            p[j] = a[j] > 0.0f ? r * (p[j] / a[j]) : 0.0f;        // d|Y| = Y / |Y|, sgn(0) = 0
+            q[j] = a[j] > 0.0f ? r * (q[j] / a[j]) : 0.0f;
+          }
+          *reinterpret_cast<nhmc_v4f*>(&out_img[off]) = p;
+          *reinterpret_cast<nhmc_v4f*>(&out_img[plane + off]) = q;
+        }
+      }
+    }
+    __syncthreads();                                      // the slabs are rewritten by the next row of waves
+  }
+  if (EPI == PEPI_RESID) {
+    __shared__ double red[NW * NW];
+    double sw = nhmc_wave_sum(lsum);
+    if (lane == 0) red[wave] = sw;
+    __syncthreads();
+    if (tid == 0) {
+      double tot = 0.0;
+      for (int w = 0; w < NW * NW; ++w) tot += red[w];
+      ws[(int64_t)img * tiles_img + tile] = tot;           // tiles of one chain are contiguous
+    }
+  }
+}
+
+int ctile_of(int R, int C) { return (R % 64 == 0 && C % 64 == 0) ? 64 : 32; }
+
+template <int EPI>
+int cgemm(const float* A, const float* B, int ld_in, int64_t in_stride, const float* SA, const float* SB, int ld_s,
+          float* OUT, const float* Y, double* ws, int n_img, int K, int R, int C, hipStream_t st) {
+  const int T = ctile_of(R, C);
+  dim3 grid((unsigned)((C / T) * (R / T) * n_img));
+  if (T == 64)
+    NHMC_LAUNCH((k_cgemm<2, EPI>), grid, dim3(256), 0, st, A, B, ld_in, in_stride, SA, SB, ld_s, OUT, Y, ws, K, R, C);
+  else
+    NHMC_LAUNCH((k_cgemm<1, EPI>), grid, dim3(64), 0, st, A, B, ld_in, in_stride, SA, SB, ld_s, OUT, Y, ws, K, R, C);
+  return nhmc_launch_status();
+}
+
+bool phase_bad(int n_chains, int channels, int dim, int pad) {
+  return n_chains <= 0 || channels <= 0 || dim <= 0 || pad < 0 || (dim % 32) || ((2 * pad) % 32) ||
+         (int64_t)n_chains * channels > 65535 || dim + 2 * pad > 8192;
+}
+
+// `fac`: the packed resident factors, float[6 n d]:  catT = [Cm^T | Sm^T] ([d][2n]),  cat = [Cm | Sm] ([n][2d]),
+// stk = [Sm ; Cm] ([2n][d]).
+struct PhaseFactors { const float *catT, *cat, *stk; };
+PhaseFactors phase_factors(const float* fac, int d, int n) {
+  return PhaseFactors{fac, fac + (int64_t)2 * n * d, fac + (int64_t)4 * n * d};
+}
+
+// stages 1-2: x -> the epilogue EPI of the complex spectrum.  tmp: float[n_img * 2 n d]
+template <int EPI, bool PRECLIP>
+int phase_forward(const float* x, const PhaseFactors& f, float* out, const float* y, double* ws, float* tmp, int n_img,
+                  int channels, int d, int n, hipStream_t st) {
+  int rc;
+  if ((rc = gemm_krc<EPI_NONE, PRECLIP>(x, f.catT, tmp, nullptr, nullptr, nullptr, n_img, channels, d, d, 2 * n, st))) return rc;
+  return cgemm<EPI>(tmp, tmp + n, 2 * n, (int64_t)d * 2 * n, f.catT, f.catT + n, 2 * n, out, y, ws, n_img, d, n, n, st);
+}
+
+// stages 3-4: W [n_img][2][n][n] -> the epilogue EPI of Cm^T Wre Cm - Sm^T Wre Sm + Cm^T Wim Sm + Sm^T Wim Cm
+template <int EPI>
+int phase_adjoint(const float* W, const PhaseFactors& f, float* g, const float* mask_or_xt, const VjpArgs* vjp, float* tmp,
+                  int n_img, int channels, int d, int n, hipStream_t st) {
+  int rc;
+  const int64_t nn = (int64_t)n * n;
+  if ((rc = cgemm<PEPI_PAIR>(W + nn, W, n, 2 * nn, f.cat, f.cat + d, 2 * d, tmp, nullptr, nullptr, n_img, n, n, d, st))) return rc;
+  return gemm_krc<EPI, false>(tmp, f.stk, g, nullptr, mask_or_xt, nullptr, n_img, channels, 2 * n, d, d, st,
+                              vjp ? *vjp : VjpArgs{});
+}
+
+}  // namespace
+
+extern "C" int nhmc_phase_tiles(int channels, int dim, int pad) {
+  const int n = dim + 2 * pad, t = n / ctile_of(n, n);
+  return channels * t * t;
+}
+
+// Floats of scratch per call of the phase entry points: the [d][2n] / [2][n][d] intermediate and the [2][n][n] spectrum.
+extern "C" size_t nhmc_phase_tmp_floats(int n_chains, int channels, int dim, int pad) {
+  const size_t n = (size_t)(dim + 2 * pad);
+  return (size_t)n_chains * channels * (2 * n * dim + 2 * n * n);
+}
+
+// mode 0: out = H(x) = |Y| ([n_chains][C][n][n]);  mode 1: out = [Re Y ; Im Y] ([n_chains][C][2][n][n]).
+extern "C" int nhmc_phase_H(const float* x, const float* fac, int mode, float* out, float* tmp, int n_chains, int channels,
+                            int dim, int pad, nhmc_stream_t stream) {
+  if (!x || !fac || !out || !tmp || (mode != 0 && mode != 1)) return NHMC_ERR_ARG;
+  if (phase_bad(n_chains, channels, dim, pad)) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(x) || !nhmc_aligned16(fac) || !nhmc_aligned16(out) || !nhmc_aligned16(tmp)) return NHMC_ERR_ALIGN;
+  const int n = dim + 2 * pad;
+  const PhaseFactors f = phase_factors(fac, dim, n);
+  if (mode == 0)
+    return phase_forward<PEPI_MOD, false>(x, f, out, nullptr, nullptr, tmp, n_chains * channels, channels, dim, n, nhmc_s(stream));
+  return phase_forward<PEPI_PAIR, false>(x, f, out, nullptr, nullptr, tmp, n_chains * channels, channels, dim, n, nhmc_s(stream));
+}
+
+// H^+(y) = crop(|ifft2c(y)|): the same factors conjugated, |Cm^T y Cm - Sm^T y Sm - i (Cm^T y Sm + Sm^T y Cm)|.
+// y: [n_chains][C][n][n] -> out [n_chains][C][d][d].  tmp: float[n_chains * C * 2 n d].
+extern "C" int nhmc_phase_pinv(const float* y, const float* fac, float* out, float* tmp, int n_chains, int channels, int dim,
+                               int pad, nhmc_stream_t stream) {
+  if (!y || !fac || !out || !tmp) return NHMC_ERR_ARG;
+  if (phase_bad(n_chains, channels, dim, pad)) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(y) || !nhmc_aligned16(fac) || !nhmc_aligned16(out) || !nhmc_aligned16(tmp)) return NHMC_ERR_ALIGN;
+  const int n = dim + 2 * pad, d = dim, n_img = n_chains * channels;
+  const PhaseFactors f = phase_factors(fac, d, n);
+  hipStream_t st = nhmc_s(stream);
+  int rc;
+  if ((rc = gemm_krc<EPI_NONE, false>(y, f.cat, tmp, nullptr, nullptr, nullptr, n_img, channels, n, n, 2 * d, st))) return rc;  // y^T [Cm | Sm]
+  return cgemm<PEPI_MOD>(tmp, tmp + d, 2 * d, (int64_t)n * 2 * d, f.cat, f.cat + d, 2 * d, out, nullptr, nullptr, n_img, n, d, d, st);
+}
+
+// The adjoint of x -> [Re Y ; Im Y] on its own: w [n_chains][C][2][n][n] -> out [n_chains][C][d][d]  (no -2, no mask).
+extern "C" int nhmc_phase_adjoint(const float* w, const float* fac, float* out, float* tmp, int n_chains, int channels,
+                                  int dim, int pad, nhmc_stream_t stream) {
+  if (!w || !fac || !out || !tmp) return NHMC_ERR_ARG;
+  if (phase_bad(n_chains, channels, dim, pad)) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(w) || !nhmc_aligned16(fac) || !nhmc_aligned16(out) || !nhmc_aligned16(tmp)) return NHMC_ERR_ALIGN;
+  const int n = dim + 2 * pad;
+  return phase_adjoint<EPI_NONE>(w, phase_factors(fac, dim, n), out, nullptr, nullptr, tmp, n_chains * channels, channels, dim, n,
+                                 nhmc_s(stream));
+}
+
+// Data term: loss partials of sum (y - |Y(clip xt)|)^2 (nhmc_phase_tiles per chain) and its gradient.  y natural
+// [n_chains][C][n][n].  tmp: nhmc_phase_tmp_floats.
+extern "C" int nhmc_data_phase(const float* xt, const float* y, const float* fac, int apply_clip, float* g_xt, double* loss_ws,
+                               float* tmp, int n_chains, int channels, int dim, int pad, nhmc_stream_t stream) {
+  if (!xt || !y || !fac || !g_xt || !loss_ws || !tmp) return NHMC_ERR_ARG;
+  if (phase_bad(n_chains, channels, dim, pad)) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(xt) || !nhmc_aligned16(y) || !nhmc_aligned16(fac) || !nhmc_aligned16(g_xt) || !nhmc_aligned16(tmp))
+    return NHMC_ERR_ALIGN;
+  const int n = dim + 2 * pad, n_img = n_chains * channels;
+  const PhaseFactors f = phase_factors(fac, dim, n);
+  float* W = tmp + (int64_t)n_img * 2 * n * dim;
+  hipStream_t st = nhmc_s(stream);
+  int rc;
+  if (apply_clip) rc = phase_forward<PEPI_RESID, true>(xt, f, W, y, loss_ws, tmp, n_img, channels, dim, n, st);
+  else            rc = phase_forward<PEPI_RESID, false>(xt, f, W, y, loss_ws, tmp, n_img, channels, dim, n, st);
+  if (rc) return rc;
+  return phase_adjoint<EPI_GRAD>(W, f, g_xt, apply_clip ? xt : nullptr, nullptr, tmp, n_img, channels, dim, n, st);
+}
+
+// The same on the clipped decode xt_next, with the VJP of the last DDIM step (inputs xt, e) in the last product's epilogue.
+extern "C" int nhmc_data_phase_vjp(const float* xt_next, const float* y, const float* fac, const float* xt, const float* e,
+                                   int e_channels, const float* at, const float* at_next, float* g_xt, float* g_e,
+                                   double* loss_ws, float* tmp, int n_chains, int channels, int dim, int pad,
+                                   nhmc_stream_t stream) {
+  if (!xt_next || !y || !fac || !xt || !e || !at || !at_next || !g_xt || !g_e || !loss_ws || !tmp) return NHMC_ERR_ARG;
+  if (phase_bad(n_chains, channels, dim, pad) || (e_channels != channels && e_channels != 2 * channels)) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(xt_next) || !nhmc_aligned16(y) || !nhmc_aligned16(fac) || !nhmc_aligned16(xt) || !nhmc_aligned16(e) ||
+      !nhmc_aligned16(g_xt) || !nhmc_aligned16(g_e) || !nhmc_aligned16(tmp))
+    return NHMC_ERR_ALIGN;
+  const int n = dim + 2 * pad, n_img = n_chains * channels;
+  const PhaseFactors f = phase_factors(fac, dim, n);
+  float* W = tmp + (int64_t)n_img * 2 * n * dim;
+  hipStream_t st = nhmc_s(stream);
+  int rc;
+  if ((rc = phase_forward<PEPI_RESID, false>(xt_next, f, W, y, loss_ws, tmp, n_img, channels, dim, n, st))) return rc;
+  const VjpArgs vjp{e, g_e, at, at_next, e_channels};
+  return phase_adjoint<EPI_VJP>(W, f, g_xt, xt, &vjp, tmp, n_img, channels, dim, n, st);
+}

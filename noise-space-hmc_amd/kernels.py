@@ -617,6 +617,151 @@ def data_spectral_vjp(xt_next, y, factors, Dmap, xt, e, at, at_next, g_e_out=Non
     return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
 
 
+# ---- nonlinear operators: HDR, phase retrieval -------------------------------------------------
+def hdr_H(x):
+    """clip(x / 0.5, -1, 1) elementwise, same shape."""
+    lib = _lib.load()
+    out = torch.empty_like(x)
+    _lib.check(lib.nhmc_hdr_H(_p(x, torch.float32, 'x'), _p(out), x.numel(), _stream()), 'nhmc_hdr_H')
+    return out
+
+
+def _dense_y(y, xt):
+    B, N = _chains_elems(xt)
+    if y.shape[0] != B or y[0].numel() != N:
+        raise _lib.NhmcError(f'the observation must have one entry per image element ({tuple(y.shape)} vs {tuple(xt.shape)})')
+    return B, N
+
+
+def data_hdr(xt, y, apply_clip=True, loss_out=None):
+    """-> (loss [B] float64, g_xt) for H = clip(2 x); y dense, one entry per image element."""
+    lib = _lib.load()
+    B, N = _dense_y(y, xt)
+    tiles = lib.nhmc_data_tiles(N)
+    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
+    g = torch.empty_like(xt)
+    rc = lib.nhmc_data_hdr(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), int(apply_clip), _p(g), _p(ws), B, N, _stream())
+    _lib.check(rc, 'nhmc_data_hdr')
+    return sum_partials(ws, tiles, B, out=loss_out), g
+
+
+def mix_bwd_hdr(xt, e, at, at_next, y, g_e_out=None, loss_out=None):
+    """Last-step VJP fused with the HDR data term -> (loss [B] float64, g_xt, g_e)."""
+    lib = _lib.load()
+    B, Cc, hw, ec = _mix_shapes(xt, e)
+    _dense_y(y, xt)
+    at, at_next = _alpha(at, B, xt.device), _alpha(at_next, B, xt.device)
+    g_xt = torch.empty_like(xt)
+    g_e = g_e_out if g_e_out is not None else torch.empty_like(e)
+    if g_e.shape != e.shape:
+        raise _lib.NhmcError('g_e_out must have the shape of the score output')
+    tiles = leapfrog_tiles(Cc * hw)
+    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
+    rc = lib.nhmc_mix_bwd_hdr(_p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
+                              _p(y, torch.float32, 'y'), _p(g_xt), _p(g_e, torch.float32, 'g_e'), int(g_e_out is None),
+                              _p(ws), B, Cc, hw, _stream())
+    _lib.check(rc, 'nhmc_mix_bwd_hdr')
+    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+
+
+def _phase_shapes(x, fac, pad, side=None):
+    """x: [B, C, s, s] (s = dim, or n = dim + 2 pad when side == 'n') -> B, C, dim, n after checking the packed factors."""
+    if x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise _lib.NhmcError(f'phase retrieval takes [B, C, s, s] planes, got {tuple(x.shape)}')
+    B, Cc, s = x.shape[0], x.shape[1], x.shape[2]
+    dim = s - 2 * pad if side == 'n' else s
+    n = dim + 2 * pad
+    if dim <= 0 or dim % 32 or (2 * pad) % 32:
+        raise _lib.NhmcError('phase retrieval needs img_dim % 32 == 0 and (2 pad) % 32 == 0')
+    if fac.numel() != 6 * n * dim:
+        raise _lib.NhmcError(f'phase factors: expected {6 * n * dim} floats for dim {dim}, pad {pad}, got {fac.numel()}')
+    return B, Cc, dim, n
+
+
+def _phase_tmp(B, Cc, dim, pad, device):
+    return torch.empty(_lib.load().nhmc_phase_tmp_floats(B, Cc, dim, pad), dtype=torch.float32, device=device)
+
+
+def phase_H(x, fac, pad, spectrum=False):
+    """|fft2c(pad(x))| -> [B, C, n, n]; spectrum=True: [Re ; Im] -> [B, C, 2, n, n]."""
+    lib = _lib.load()
+    B, Cc, dim, n = _phase_shapes(x, fac, pad)
+    out = torch.empty((B, Cc, 2, n, n) if spectrum else (B, Cc, n, n), dtype=torch.float32, device=x.device)
+    tmp = _phase_tmp(B, Cc, dim, pad, x.device)
+    rc = lib.nhmc_phase_H(_p(x, torch.float32, 'x'), _p(fac, torch.float32, 'fac'), int(spectrum), _p(out), _p(tmp), B, Cc, dim, pad,
+                          _stream())
+    _lib.check(rc, 'nhmc_phase_H')
+    return out
+
+
+def phase_pinv(y, fac, pad):
+    """crop(|ifft2c(y)|): y [B, C, n, n] -> [B, C, dim, dim]."""
+    lib = _lib.load()
+    B, Cc, dim, n = _phase_shapes(y, fac, pad, side='n')
+    out = torch.empty(B, Cc, dim, dim, dtype=torch.float32, device=y.device)
+    tmp = _phase_tmp(B, Cc, dim, pad, y.device)
+    rc = lib.nhmc_phase_pinv(_p(y, torch.float32, 'y'), _p(fac, torch.float32, 'fac'), _p(out), _p(tmp), B, Cc, dim, pad, _stream())
+    _lib.check(rc, 'nhmc_phase_pinv')
+    return out
+
+
+def phase_adjoint(w, fac, pad):
+    """The adjoint of phase_H(spectrum=True): w [B, C, 2, n, n] -> [B, C, dim, dim]."""
+    lib = _lib.load()
+    if w.dim() != 5 or w.shape[2] != 2:
+        raise _lib.NhmcError('phase_adjoint takes [B, C, 2, n, n]')
+    B, Cc, dim, n = _phase_shapes(w[:, :, 0], fac, pad, side='n')
+    out = torch.empty(B, Cc, dim, dim, dtype=torch.float32, device=w.device)
+    tmp = _phase_tmp(B, Cc, dim, pad, w.device)
+    rc = lib.nhmc_phase_adjoint(_p(w, torch.float32, 'w'), _p(fac, torch.float32, 'fac'), _p(out), _p(tmp), B, Cc, dim, pad, _stream())
+    _lib.check(rc, 'nhmc_phase_adjoint')
+    return out
+
+
+def _phase_y(y, B, Cc, n):
+    if tuple(y.shape) != (B, Cc, n, n):
+        raise _lib.NhmcError(f'phase observation must be [{B}, {Cc}, {n}, {n}], got {tuple(y.shape)}')
+
+
+def data_phase(xt, y, fac, pad, apply_clip=True, loss_out=None):
+    """-> (loss [B] float64, g_xt) for H = |fft2c(pad(x))|; y [B, C, n, n]."""
+    lib = _lib.load()
+    B, Cc, dim, n = _phase_shapes(xt, fac, pad)
+    _phase_y(y, B, Cc, n)
+    tiles = lib.nhmc_phase_tiles(Cc, dim, pad)
+    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
+    tmp = _phase_tmp(B, Cc, dim, pad, xt.device)
+    g = torch.empty_like(xt)
+    rc = lib.nhmc_data_phase(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), _p(fac, torch.float32, 'fac'), int(apply_clip),
+                             _p(g), _p(ws), _p(tmp), B, Cc, dim, pad, _stream())
+    _lib.check(rc, 'nhmc_data_phase')
+    return sum_partials(ws, tiles, B, out=loss_out), g
+
+
+def data_phase_vjp(xt_next, y, fac, pad, xt, e, at, at_next, g_e_out=None, loss_out=None):
+    """Phase-retrieval data term on the clipped decode `xt_next` + VJP of the last DDIM step (inputs xt, e) in the last
+    product's epilogue -> (loss [B] float64, g_xt, g_e)."""
+    lib = _lib.load()
+    B, Cc, hw, ec = _mix_shapes(xt, e)
+    _, _, dim, n = _phase_shapes(xt, fac, pad)
+    _phase_y(y, B, Cc, n)
+    if xt_next.shape != xt.shape:
+        raise _lib.NhmcError('xt_next must have the shape of xt')
+    at, at_next = _alpha(at, B, xt.device), _alpha(at_next, B, xt.device)
+    tiles = lib.nhmc_phase_tiles(Cc, dim, pad)
+    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
+    tmp = _phase_tmp(B, Cc, dim, pad, xt.device)
+    g_xt = torch.empty_like(xt)
+    g_e = g_e_out if g_e_out is not None else torch.zeros_like(e)          # channels [0, C) are written
+    if g_e.shape != e.shape:
+        raise _lib.NhmcError('g_e_out must have the shape of the score output')
+    rc = lib.nhmc_data_phase_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y, torch.float32, 'y'), _p(fac, torch.float32, 'fac'),
+                                 _p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next), _p(g_xt),
+                                 _p(g_e, torch.float32, 'g_e'), _p(ws), _p(tmp), B, Cc, dim, pad, _stream())
+    _lib.check(rc, 'nhmc_data_phase_vjp')
+    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+
+
 # ---- a5-a7 ----------------------------------------------------------------------------------
 def hamiltonian(sums_ws, n_elem, loss, sigma_y, m_inv, want_terms=False, sel=None):
     """sel (int32 [B]): loss is then the gradient cache's loss_pair [2, B] and chain c uses loss[sel[c], c]."""

@@ -1,4 +1,5 @@
-"""Linear forward operators with the reference's `H_functions` surface, on the HIP kernels.
+"""Forward operators with the reference's `H_functions` surface, on the HIP kernels (the linear ones, and the two
+nonlinear ones that need nothing from outside: HDR and phase retrieval).
 
 Mirrors obs_functions/Hfuncs.py for the three operators on the HMC hot path -- same constructor
 arguments, same `H / Ht / H_pinv / is_linear`, inputs `[B, ...]`, outputs `[B, flat]` -- but each
@@ -463,6 +464,101 @@ class SRConv(H_functions):
         return K.data_srconv_vjp(xt_next, self._obs_t(y), self.factors, xt_in, e, at, at_next, g_e_out=g_e_out, loss_out=loss_out)
 
 
+class HDR(H_functions):
+    """obs_functions/Hfuncs.py:406-445: H(x) = clip(x / 0.5, -1, 1) elementwise; M = C H W, H^+ = identity, no H^T.
+    `channels, img_dim` (keywords, optional) only fix M for the callers that size an observation before they have one."""
+
+    def __init__(self, channels=None, img_dim=None):
+        self.channels, self.img_dim = channels, img_dim
+        self.M = channels * img_dim ** 2 if channels and img_dim else None
+
+    def is_linear(self):
+        return False
+
+    def H(self, vec):
+        return K.hdr_H(vec.reshape(vec.shape[0], -1).contiguous())
+
+    forward = H
+
+    def H_pinv(self, vec):
+        return vec
+
+    def data_term(self, xt, y, apply_clip=True, loss_out=None):
+        return K.data_hdr(xt, y.reshape(y.shape[0], -1).contiguous(), apply_clip, loss_out=loss_out)
+
+    def fused_last_vjp(self, xt_in, e, at, at_next, y, g_e_out=None, loss_out=None):
+        """Data term + VJP of the last DDIM step in one kernel -> (loss, g_xt, g_e); used by the sampler's engine."""
+        return K.mix_bwd_hdr(xt_in, e, at, at_next, y.reshape(y.shape[0], -1).contiguous(), g_e_out=g_e_out, loss_out=loss_out)
+
+
+def centred_dft_factors(n, pad, dim):
+    """Cm, Sm [n, dim] in float64: real and imaginary part of F[:, pad:pad+dim], F = fftshift(fft(ifftshift(I), norm='ortho'))
+    along one axis -- the centred orthonormal DFT of size n (obs_functions/fastmri_utils.py:67-89) restricted to the
+    columns the zero padding leaves."""
+    eye = torch.eye(n, dtype=torch.complex128)
+    F = torch.fft.fftshift(torch.fft.fft(torch.fft.ifftshift(eye, dim=0), dim=0, norm='ortho'), dim=0)
+    Fc = F[:, pad:pad + dim]
+    return Fc.real.contiguous(), Fc.imag.contiguous()
+
+
+class PhaseRetrievalOperator(H_functions):
+    """obs_functions/Hfuncs.py:318-366: H(x) = |fft2c(pad(x, p))| per channel plane with p = int(oversample / 8 * 256)
+    WHATEVER the image size (so n = img_dim + 128 for the reference's oversample = 2), M = C n n; H^+(y) = crop(|ifft2c(y)|).
+    The zero padding turns the padded centred DFT into rectangular real sandwiches with Fc = Cm + i Sm (nhmc.h), built
+    once on the host in float64 and resident in fp32 in the three layouts the MFMA chain reads."""
+
+    def __init__(self, oversample, device, channels=3, img_dim=256):
+        self.pad = int((oversample / 8.0) * 256)
+        self.device = device
+        self.channels, self.img_dim = channels, img_dim
+        self.n = n = img_dim + 2 * self.pad
+        if img_dim % 32 or n % 32:
+            raise NhmcError('phase retrieval needs img_dim % 32 == 0 and (img_dim + 2 pad) % 32 == 0')
+        self.M = channels * n * n
+        Cm, Sm = centred_dft_factors(n, self.pad, img_dim)
+        self.Cm, self.Sm = Cm, Sm                                   # float64, host: the definition the tests restate
+        cat_t = torch.cat([Cm.t(), Sm.t()], dim=1)                  # [d][2n]
+        cat = torch.cat([Cm, Sm], dim=1)                            # [n][2d]
+        stk = torch.cat([Sm, Cm], dim=0)                            # [2n][d]
+        self.factors = torch.cat([m.contiguous().reshape(-1) for m in (cat_t, cat, stk)]).float().contiguous().to(device)
+
+    def is_linear(self):
+        return False
+
+    def _obs(self, y):
+        y = y.reshape(y.shape[0], self.channels, self.n, self.n)
+        return y if y.is_contiguous() else y.contiguous()
+
+    def H(self, vec):
+        x = _img(vec, self.channels, self.img_dim)
+        return K.phase_H(x, self.factors, self.pad).reshape(x.shape[0], -1)
+
+    forward = H
+
+    def spectrum(self, vec):
+        """[Re Y ; Im Y] of the padded centred DFT -> [B, C, 2, n, n] (the linear map whose modulus H is)."""
+        return K.phase_H(_img(vec, self.channels, self.img_dim), self.factors, self.pad, spectrum=True)
+
+    def spectrum_adjoint(self, w):
+        """The exact adjoint of `spectrum`: [B, C, 2, n, n] -> [B, C, d, d]."""
+        return K.phase_adjoint(w.contiguous(), self.factors, self.pad)
+
+    def H_pinv(self, vec):
+        return K.phase_pinv(self._obs(vec), self.factors, self.pad).reshape(vec.shape[0], -1)
+
+    def data_term(self, xt, y, apply_clip=True, loss_out=None):
+        return K.data_phase(xt, self._obs(y), self.factors, self.pad, apply_clip, loss_out=loss_out)
+
+    fused_wants_decode = True              # the engine hands over the clipped decode it already holds
+
+    def fused_last_vjp(self, xt_in, e, at, at_next, y, g_e_out=None, xt_next=None, loss_out=None):
+        """Data term + VJP of the last DDIM step (in the last product's epilogue) -> (loss, g_xt, g_e)."""
+        if xt_next is None:
+            xt_next = K.ddim_mix_fwd(xt_in, e, at, at_next, final_clip=True)['xt_next']
+        return K.data_phase_vjp(xt_next, self._obs(y), self.factors, self.pad, xt_in, e, at, at_next, g_e_out=g_e_out,
+                                loss_out=loss_out)
+
+
 def bicubic_taps(factor, a=-0.5):
     """main_sampling.py:266-279."""
     def w(x):
@@ -506,6 +602,10 @@ def build_operator(deg, channels, img_dim, device, generator=None, spectral_proj
         return Deblurring2D(gaussian_taps(1.0), gaussian_taps(20.0), channels, img_dim, device, projected=spectral_projected)
     if deg == 'deblur_gauss':
         return Deblurring(gaussian_taps(10.0, half=2), channels, img_dim, device, projected=spectral_projected)  # main_sampling.py:308-314
+    if 'phase' in deg:                                                  # main_sampling.py:315-318 (substring match, as there)
+        return PhaseRetrievalOperator(2.0, device, channels=channels, img_dim=img_dim)
+    if 'hdr' in deg:                                                    # :319-322
+        return HDR(channels=channels, img_dim=img_dim)
     if deg == 'color':
         return Colorization(img_dim, device)
     if deg.startswith('cs') and deg[2:].isdigit():

@@ -59,3 +59,24 @@ ms = timeit(lambda: opp.data_term(x, y, True), 10)
 msv = timeit(lambda: opp.fused_last_vjp(x, e6, at, an, y, g_e_out=ge, xt_next=cur), 10)
 flp = 4 * B * 3 * 2 * 256 ** 3
 print(f'aniso projected (4 products) B={B}: data term {ms*1e3:.1f} us {flp/ms/1e9:.1f} TFLOP/s, + last VJP {msv*1e3:.1f} us {flp/msv/1e9:.1f} TFLOP/s')
+# the two nonlinear operators.  HDR fused kernel: R xt, R e[:C], R y, W g_xt, W g_e[:C] = 5T, the inpainting fused kernel's
+# traffic with a dense observation -- compare against the inpaint line of THIS run.  Phase retrieval (n = 384): FLOP model
+# per plane 2 d d 2n + 8 (2 n n d) + 2 d d 2n (stage 1, the two four-product stages, stage 4).
+oph = operators.build_operator('hdr', 3, 256, dev)
+yh = torch.randn(B, oph.M, device=dev)
+ms = timeit(lambda: oph.fused_last_vjp(x, e6, at, an, yh, g_e_out=ge))
+msi = timeit(lambda: opi.fused_last_vjp(x, e6, at, an, yi, g_e_out=ge))
+print(f'hdr fused last VJP B={B}: {ms*1e3:.1f} us  {(5*T)/ms/1e6:.0f} GB/s (5T);  inpaint fused, same session: {msi*1e3:.1f} us')
+ms = timeit(lambda: oph.data_term(x, yh, True))
+print(f'hdr data term B={B}: {ms*1e3:.1f} us  {(3*T)/ms/1e6:.0f} GB/s (3T)')
+opf = operators.build_operator('phase_retrieval', 3, 256, dev)
+d_, n_ = 256, opf.n
+yf = torch.rand(B, opf.M, device=dev)
+flf = B * 3 * (2 * (2 * d_ * d_ * 2 * n_) + 8 * (2 * n_ * n_ * d_))
+ms = timeit(lambda: opf.data_term(x, yf, True), 10)
+msv = timeit(lambda: opf.fused_last_vjp(x, e6, at, an, yf, g_e_out=ge, xt_next=cur), 10)
+msa = timeit(lambda: op.fused_last_vjp(x, e6, at, an, y, g_e_out=ge, xt_next=cur), 10)
+print(f'phase_retrieval B={B}: data term {ms*1e3:.1f} us {flf/ms/1e9:.1f} TFLOP/s, + last VJP {msv*1e3:.1f} us {flf/msv/1e9:.1f} TFLOP/s '
+      f'({flf/1e9:.1f} GFLOP);  deblur_aniso + last VJP, same session: {msa*1e3:.1f} us')
+ms = timeit(lambda: opf.H(x), 10)
+print(f'phase_retrieval H B={B}: {ms*1e3:.1f} us')
