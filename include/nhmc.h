@@ -501,6 +501,45 @@ int nhmc_gn_act_bwd(const float* x, const float* dy, const float* gamma, const f
                     int64_t film_stride, const float* pre, int64_t pre_stride, float eps, int act,
                     const double* fwd_ws, const float* dx_add, float* dx, double* ws, int splits, int n, int channels,
                     int groups, int64_t hw, nhmc_stream_t stream);
+/* nhmc_gn_act_bwd with the forward's workspace at a split count of its own (fwd_splits, 1..64): what a forward of the
+ * one-pass entries below leaves.  nhmc_gn_act_bwd(..., splits, ...) == nhmc_gn_act_bwd_fs(..., fwd_splits = splits, ...). */
+int nhmc_gn_act_bwd_fs(const float* x, const float* dy, const float* gamma, const float* beta, const float* film,
+                       int64_t film_stride, const float* pre, int64_t pre_stride, float eps, int act,
+                       const double* fwd_ws, int fwd_splits, const float* dx_add, float* dx, double* ws, int splits, int n,
+                       int channels, int groups, int64_t hw, nhmc_stream_t stream);
+/* One-pass forms of the two entries above (csrc/gn_onepass.hip): one launch each, in which every workgroup keeps its share
+ * of a (sample, group) slab in registers while the slab's statistics are exchanged between the workgroups, so x (and dy) is
+ * read once.  Same formulas, same ws layout: double[n * groups][splits][2] with splits = nhmc_gn_onepass_splits(...), which
+ * (the forward writes n * groups more pairs behind them, the slab totals: ws is double[n * groups * (splits + 1) * 2], and
+ * ws + n * groups * splits * 2 is a workspace of one split, which a backward may be given with fwd_splits = 1)
+ * is 0 for a shape these entries do not cover (the caller then keeps the two-pass entries; the one-pass entries themselves
+ * answer NHMC_ERR_SHAPE).  fwd_splits: the split count of the workspace the forward wrote (either path's).
+ * ws (16-byte aligned, a buffer of its own) is also what the workgroups of a slab exchange their partial sums through:
+ *   when splits > 1 the entry fills it with the byte 0xFF on `stream` ahead of its launch (a node of its own under
+ *   graph capture), and a word that no longer holds that pattern has been published.
+ * nhmc_gn_onepass_prefers(backward, ...): 1 when the one-pass entry is the faster one for this shape and direction (the
+ *   measured rule is next to its definition), 0 when the caller should keep the two-pass entry.
+ * flags: 0, or NHMC_GN_ONEPASS_NOWAIT (tests only): no workgroup waits for the others, each computes the whole slab's
+ *   statistics itself -- the path a workgroup takes when its bounded wait expires; the results are the same bits.
+ * Two sources / destinations (the concatenated input of a U-Net output block):
+ *   forward: x2 != NULL -> the logical input is cat(x1 [n][c1][hw], x2 [n][channels - c1][hw]) along the channels,
+ *     0 < c1 < channels (NHMC_ERR_SHAPE otherwise), and x_cat [n][channels][hw] (required then, NHMC_ERR_ARG without it)
+ *     receives the concatenation; x2 == NULL -> c1 == channels and x_cat == NULL.  y is always [n][channels][hw].
+ *   backward: x, dy, dx_add are [n][channels][hw]; dx2 != NULL -> dx is written as dx1 [n][c1][hw] and
+ *     dx2 [n][channels - c1][hw]; dx2 == NULL -> c1 == channels.  dx_add must alias neither, and neither may alias x or
+ *     dy (NHMC_ERR_ARG): the one-pass backward is not in place.
+ * Null pointers / unknown flags: NHMC_ERR_ARG; a pointer off 16 bytes: NHMC_ERR_ALIGN; all before any device work. */
+#define NHMC_GN_ONEPASS_NOWAIT 1
+int nhmc_gn_onepass_splits(int n, int channels, int groups, int64_t hw);
+int nhmc_gn_onepass_prefers(int backward, int n, int channels, int groups, int64_t hw);
+int nhmc_gn_onepass_fwd(const float* x1, const float* x2, int c1, const float* gamma, const float* beta, const float* film,
+                        int64_t film_stride, const float* pre, int64_t pre_stride, float eps, int act, float* y,
+                        float* x_cat, double* ws, int flags, int n, int channels, int groups, int64_t hw,
+                        nhmc_stream_t stream);
+int nhmc_gn_onepass_bwd(const float* x, const float* dy, const float* gamma, const float* beta, const float* film,
+                        int64_t film_stride, const float* pre, int64_t pre_stride, float eps, int act,
+                        const double* fwd_ws, int fwd_splits, const float* dx_add, float* dx1, float* dx2, int c1,
+                        double* ws, int flags, int n, int channels, int groups, int64_t hw, nhmc_stream_t stream);
 /* out = (h + bias_c) + other, [n][channels][hw]: a convolution's bias folded into the residual add that follows it
  * (unet_ffhq.py:321).  Its backward is the identity towards both h and other. */
 int nhmc_bias_add2(const float* h, const float* bias, const float* other, float* out, int n, int channels,

@@ -89,6 +89,11 @@ SIGNATURES = {
     'nhmc_gn_splits': (I, [I, I, I, I64]),
     'nhmc_gn_act_fwd': (I, [P, P, P, P, I64, P, I64, F, I, P, P, I, I, I, I, I64, P]),
     'nhmc_gn_act_bwd': (I, [P, P, P, P, P, I64, P, I64, F, I, P, P, P, P, I, I, I, I, I64, P]),
+    'nhmc_gn_act_bwd_fs': (I, [P, P, P, P, P, I64, P, I64, F, I, P, I, P, P, P, I, I, I, I, I64, P]),
+    'nhmc_gn_onepass_splits': (I, [I, I, I, I64]),
+    'nhmc_gn_onepass_prefers': (I, [I, I, I, I, I64]),
+    'nhmc_gn_onepass_fwd': (I, [P, P, I, P, P, P, I64, P, I64, F, I, P, P, P, I, I, I, I, I64, P]),
+    'nhmc_gn_onepass_bwd': (I, [P, P, P, P, P, I64, P, I64, F, I, P, I, P, P, P, I, P, I, I, I, I, I64, P]),
     'nhmc_bias_add2': (I, [P, P, P, P, I, I, I64, P]),
     'nhmc_psnr': (I, [P, P, P, P, I, I64, P]),
     'nhmc_randn_philox': (I, [P, U64, U32, U32, F, I, I64, P]),

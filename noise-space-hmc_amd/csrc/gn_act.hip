@@ -29,6 +29,7 @@ struct GnArgs {
                                                   // the convolution that produced x, + a per-sample embedding term): the
                                                   // producer then runs without its broadcast bias-add pass
   int C, G; int64_t hw; float eps; int act; int splits;
+  int fwd_splits;                                 // backward: the split count of the forward's workspace (may differ from `splits`)
 };
 
 __device__ __forceinline__ float gn_sigmoid(float u) { return 1.0f / (1.0f + expf(-u)); }
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_stats(const float4* __restric
   float mean = 0.f, rstd = 0.f;
   if (BWD) {
     double s = 0.0, ss = 0.0;
-    for (int k = 0; k < a.splits; ++k) { s += fwd_ws[((int64_t)bg * a.splits + k) * 2]; ss += fwd_ws[((int64_t)bg * a.splits + k) * 2 + 1]; }
+    for (int k = 0; k < a.fwd_splits; ++k) { s += fwd_ws[((int64_t)bg * a.fwd_splits + k) * 2]; ss += fwd_ws[((int64_t)bg * a.fwd_splits + k) * 2 + 1]; }
     const double n = (double)cpg * (double)a.hw, m = s / n;
     mean = (float)m;
     rstd = (float)(1.0 / sqrt(fmax(ss / n - m * m, 0.0) + (double)a.eps));
@@ -96,9 +97,9 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_apply(const float4* __restric
   __shared__ float st[4];
   if (threadIdx.x == 0) {
     double s = 0.0, ss = 0.0, d0 = 0.0, d1 = 0.0;
-    for (int k = 0; k < a.splits; ++k) {
-      s += fwd_ws[((int64_t)bg * a.splits + k) * 2]; ss += fwd_ws[((int64_t)bg * a.splits + k) * 2 + 1];
-      if (BWD) { d0 += bwd_ws[((int64_t)bg * a.splits + k) * 2]; d1 += bwd_ws[((int64_t)bg * a.splits + k) * 2 + 1]; }
+    for (int k = 0; k < a.fwd_splits; ++k) { s += fwd_ws[((int64_t)bg * a.fwd_splits + k) * 2]; ss += fwd_ws[((int64_t)bg * a.fwd_splits + k) * 2 + 1]; }
+    if (BWD) {
+      for (int k = 0; k < a.splits; ++k) { d0 += bwd_ws[((int64_t)bg * a.splits + k) * 2]; d1 += bwd_ws[((int64_t)bg * a.splits + k) * 2 + 1]; }
     }
     const double n = (double)cpg * (double)a.hw, m = s / n;
     st[0] = (float)m;
@@ -189,7 +190,7 @@ extern "C" int nhmc_gn_act_fwd(const float* x, const float* gamma, const float* 
   int rc = gn_check(x, gamma, beta, n, channels, groups, hw, splits);
   if (rc) return rc;
   if (!y || !ws || !nhmc_aligned16(y)) return NHMC_ERR_ARG;
-  const GnArgs a{gamma, beta, film, film_stride, pre, pre_stride, channels, groups, hw, eps, act, splits};
+  const GnArgs a{gamma, beta, film, film_stride, pre, pre_stride, channels, groups, hw, eps, act, splits, splits};
   const int64_t n4 = (int64_t)(channels / groups) * hw / 4;
   hipStream_t st = nhmc_s(stream);
   NHMC_LAUNCH(k_gn_stats<false>, dim3((unsigned)splits, (unsigned)(n * groups)), dim3(NHMC_BLOCK), 0, st, (const float4*)x,
@@ -201,15 +202,16 @@ extern "C" int nhmc_gn_act_fwd(const float* x, const float* gamma, const float* 
   return nhmc_launch_status();
 }
 
-extern "C" int nhmc_gn_act_bwd(const float* x, const float* dy, const float* gamma, const float* beta, const float* film,
+extern "C" int nhmc_gn_act_bwd_fs(const float* x, const float* dy, const float* gamma, const float* beta, const float* film,
                                int64_t film_stride, const float* pre, int64_t pre_stride, float eps, int act,
-                               const double* fwd_ws, const float* dx_add, float* dx, double* ws, int splits, int n,
+                               const double* fwd_ws, int fwd_splits, const float* dx_add, float* dx, double* ws, int splits, int n,
                                int channels, int groups, int64_t hw, nhmc_stream_t stream) {
   int rc = gn_check(x, gamma, beta, n, channels, groups, hw, splits);
   if (rc) return rc;
+  if (fwd_splits <= 0 || fwd_splits > 64) return NHMC_ERR_ARG;
   if (!dy || !fwd_ws || !dx || !ws || !nhmc_aligned16(dy) || !nhmc_aligned16(dx) || !nhmc_aligned16(dx_add) || dx_add == dx)
     return NHMC_ERR_ARG;
-  const GnArgs a{gamma, beta, film, film_stride, pre, pre_stride, channels, groups, hw, eps, act, splits};
+  const GnArgs a{gamma, beta, film, film_stride, pre, pre_stride, channels, groups, hw, eps, act, splits, fwd_splits};
   const int64_t n4 = (int64_t)(channels / groups) * hw / 4;
   hipStream_t st = nhmc_s(stream);
   NHMC_LAUNCH(k_gn_stats<true>, dim3((unsigned)splits, (unsigned)(n * groups)), dim3(NHMC_BLOCK), 0, st, (const float4*)x,
@@ -218,6 +220,15 @@ extern "C" int nhmc_gn_act_bwd(const float* x, const float* dy, const float* gam
   NHMC_LAUNCH(k_gn_apply<true>, dim3((unsigned)((n4 + NHMC_BLOCK * 2 - 1) / (NHMC_BLOCK * 2)), (unsigned)(n * groups)),
               dim3(NHMC_BLOCK), 0, st, (const float4*)x, (const float4*)dy, fwd_ws, ws, a, (float4*)dx, (const float4*)dx_add);
   return nhmc_launch_status();
+}
+
+extern "C" int nhmc_gn_act_bwd(const float* x, const float* dy, const float* gamma, const float* beta, const float* film,
+                               int64_t film_stride, const float* pre, int64_t pre_stride, float eps, int act,
+                               const double* fwd_ws, const float* dx_add, float* dx, double* ws, int splits, int n,
+                               int channels, int groups, int64_t hw, nhmc_stream_t stream) {
+  if (splits <= 0) return NHMC_ERR_ARG;
+  return nhmc_gn_act_bwd_fs(x, dy, gamma, beta, film, film_stride, pre, pre_stride, eps, act, fwd_ws, splits, dx_add, dx, ws,
+                            splits, n, channels, groups, hw, stream);
 }
 
 extern "C" int nhmc_bias_add2(const float* h, const float* bias, const float* other, float* out, int n, int channels,

@@ -1,0 +1,427 @@
+// One-pass GroupNorm (+ FiLM scale/shift) (+ SiLU), forward and input gradient: every activation crosses HBM once per call.
+//
+// Pass arithmetic.  The two-pass kernels of gn_act.hip read x (and dy) twice, because the statistics of a (sample, group)
+// slab must be complete before any element of it can be normalised and the two halves are separate launches over a
+// tensor far larger than the Infinity Cache:
+//     forward   k_gn_stats (R x)     -> k_gn_apply (R x, W y)                   2 reads + 1 write
+//     backward  k_gn_stats (R x, dy) -> k_gn_apply (R x, dy [, acc], W dx)      4 (5) reads + 1 write
+// Here a slab is spread over `splits` workgroups of one launch, each of which loads its share (256 threads x 8 float4 of x,
+// in the backward also of dy) into registers ONCE, reduces it, exchanges the 16-byte partial with the other workgroups
+// of its slab and then normalises / differentiates its share from registers:
+//     forward   k_gn_onepass<false> (R x, W y)                                  1 read  + 1 write
+//     backward  k_gn_onepass<true>  (R x, dy [, acc], W dx)                     2 (3) reads + 1 write
+// The formulas, the fp64 partial sums, their fixed summation order k = 0 .. splits - 1 and the workspace layout
+// ws[(bg * splits + split) * 2 ..] are those of gn_act.hip, so a forward workspace of either path feeds either backward.
+//
+// The wait protocol (agent scope, placement independent; "the data is the flag").  The entry point fills the workspace
+// with the byte 0xFF by a small launch of its own (k_gn_ws_fill) on the same stream ahead of every launch; no partial sum can have
+// that bit pattern.  Thread 0 of a workgroup stores its two fp64 partials with relaxed agent-scope atomic stores (8-byte, write-
+// through, vector path).  The lanes of its first wave then poll one slot of the slab each -- relaxed agent-scope atomic
+// loads, which bypass this CU's L1, s_sleep between sweeps -- until no word of the slab holds the fill pattern any more;
+// what they have loaded then IS the data, and thread 0 adds it in the fixed order.  (A first version with a ticket
+// counter -- drain, fetch_add, polls of one word, then one lane reading all partials in a loop -- measured 3-4 x the
+// two-pass time at the 256x256 level.)
+// No other load of this kernel touches bytes that another workgroup writes in the same launch.
+//
+// Why the result does not depend on scheduling.  Dispatch order and co-residency are not guaranteed, so the wait is
+// bounded: when the poll limit expires the workgroup stops waiting and computes the partials of the other shares of its
+// slab itself, from memory, split by split, with the thread-to-element mapping and the reduction order of the owning
+// workgroup -- the same numbers bit for bit (the file is built without fp contraction, one code path forms a partial).
+// That is the two-pass cost for that one workgroup and nothing worse; no workgroup can spin without end, and the bits of
+// the output do not tell whether the fallback ran (flag NHMC_GN_ONEPASS_NOWAIT forces it everywhere, for the tests).
+// A slab that fits one workgroup (splits == 1) takes no fill and no wait.
+//
+// Behind the partials the forward leaves the slab totals, ws[n * groups * splits * 2 + bg * 2 ..] (a workspace of one
+// split): a backward that reads those needs one pair of loads per workgroup whatever the forward's split count was.
+//
+// The per-channel terms (pre, gamma, beta, FiLM) of a slab's channels are formed once per workgroup into LDS (groups of up
+// to 64 channels; wider groups read them from memory per float4): per float4 they cost an LDS read instead of up to five
+// dependent global loads, each of which the compiler follows with a full s_waitcnt.
+//
+// Concatenated input (the U-Net's output blocks): the forward may take the logical input as two tensors
+// x1 [n][C1][hw] | x2 [n][C - C1][hw] and then also writes their concatenation x_cat from the same load; the backward
+// may write dx as two contiguous tensors of those shapes.  The source / destination is chosen per channel plane
+// (hw % 4 == 0 keeps a float4 inside one plane); a group may straddle C1.
+#include "nhmc_common.h"
+
+namespace {
+
+constexpr int OP_K = 8;                          // float4 per thread held in registers (32 VGPRs of x, 32 of dy)
+constexpr int OP_SHARE = NHMC_BLOCK * OP_K;      // float4 per workgroup
+constexpr int OP_MAX_SPLITS = 64;
+constexpr unsigned OP_POLLS = 2048;              // bounded wait: a few milliseconds, then the fallback
+// what k_gn_ws_fill leaves ahead of a launch in every word of the partials: no sum of fp32-derived values has this bit pattern (a NaN
+// whose payload is all ones down to the last bit; fp32 -> fp64 conversion leaves the low 29 bits zero)
+constexpr unsigned long long OP_EMPTY = ~0ull;
+
+struct OpArgs {
+  const float* gamma; const float* beta;          // [C]
+  const float* film; int64_t film_stride;         // nullable, as in gn_act.hip
+  const float* pre; int64_t pre_stride;           // nullable, as in gn_act.hip
+  int C, G, C1;                                   // C1: channels of the first source / destination (== C without a second)
+  int hw4, n4;                                    // float4 per channel plane, per (sample, group) slab
+  float eps; int act; int splits, fwd_splits; unsigned polls;
+};
+
+__device__ __forceinline__ float op_sigmoid(float u) { return 1.0f / (1.0f + expf(-u)); }
+
+// float4 index of slab element q (plane pl of the group, offset p4 inside it) in a tensor of `ch_total` channels
+__device__ __forceinline__ int64_t op_index(int b, int ch_total, int ch, int hw4, int p4) {
+  return ((int64_t)b * ch_total + ch) * hw4 + p4;
+}
+
+// nhmc_block_sum<2> in its arithmetic ((wave 0 + wave 1) + (wave 2 + wave 3), result in thread 0), with the two values
+// summed one after the other: thread 0 then holds 4 doubles of LDS data at a time instead of 8, which matters where the
+// backward's 64 data registers are live around it.  lds: double[8].
+__device__ __forceinline__ void op_block_sum(double (&v)[2], double* lds) {
+  const int lane = threadIdx.x & (NHMC_WAVE - 1), wave = threadIdx.x >> 6;
+  v[0] = nhmc_wave_sum(v[0]); v[1] = nhmc_wave_sum(v[1]);
+  if (lane == 0) { lds[wave] = v[0]; lds[4 + wave] = v[1]; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    v[0] = (lds[0] + lds[1]) + (lds[2] + lds[3]);
+    __builtin_amdgcn_sched_barrier(0);
+    v[1] = (lds[4] + lds[5]) + (lds[6] + lds[7]);
+  }
+}
+
+constexpr int OP_CHAN_LDS = 64;                  // channels per group whose terms are staged in LDS
+struct OpChan { float pb, ga, be; };
+// tab (nullable): the terms of the group's channels in LDS, 3 floats each, first channel ch0
+template <bool AFFINE>
+__device__ __forceinline__ OpChan op_chan(const OpArgs& a, int b, int ch, const float* tab = nullptr, int ch0 = 0) {
+  OpChan c;
+  if (tab) { const float* t = tab + 3 * (ch - ch0); c.pb = t[0]; c.ga = t[1]; c.be = t[2]; return c; }
+  c.pb = a.pre ? a.pre[(int64_t)b * a.pre_stride + ch] : 0.0f;
+  c.ga = c.be = 0.0f;
+  if (AFFINE) {
+    c.ga = a.gamma[ch]; c.be = a.beta[ch];
+    if (a.film) { const float sc = 1.0f + a.film[(int64_t)b * a.film_stride + ch]; c.ga *= sc; c.be = c.be * sc + a.film[(int64_t)b * a.film_stride + a.C + ch]; }
+  }
+  return c;
+}
+
+// One element's contribution to the partial sums of its share, and one element of the output: the one place where each
+// is formed (the register path calls them four times per float4, the fallback element by element).
+template <bool BWD>
+__device__ __forceinline__ void op_stat1(const OpArgs& a, const OpChan& c, float x, float d, float mean, float rstd, float& t0,
+                                         float& t1) {
+  if (!BWD) {
+    const float v = x + c.pb;
+    t0 += v; t1 += v * v;
+  } else {
+    const float xh = ((x + c.pb) - mean) * rstd;
+    float du = d;
+    if (a.act) { const float u = xh * c.ga + c.be, sg = op_sigmoid(u); du = du * (sg * (1.0f + u * (1.0f - sg))); }
+    const float dxh = du * c.ga;
+    t0 += dxh; t1 += dxh * xh;
+  }
+}
+template <bool BWD>
+__device__ __forceinline__ float op_apply1(const OpArgs& a, const OpChan& c, float x, float d, float mean, float rstd, float m0,
+                                           float m1) {
+  if (!BWD) {
+    const float u = (((x + c.pb) - mean) * rstd) * c.ga + c.be;
+    return a.act ? u * op_sigmoid(u) : u;
+  }
+  const float xh = ((x + c.pb) - mean) * rstd;
+  float du = d;
+  if (a.act) { const float u = xh * c.ga + c.be, sg = op_sigmoid(u); du = du * (sg * (1.0f + u * (1.0f - sg))); }
+  return rstd * ((du * c.ga - m0) - xh * m1);
+}
+
+template <bool BWD>
+__device__ __forceinline__ void op_stat(const OpArgs& a, int b, int ch, const float4& xv, const float4& dv, float mean, float rstd,
+                                        double& s0, double& s1, const float* tab, int ch0) {
+  const float* xe = reinterpret_cast<const float*>(&xv);
+  const float* de = reinterpret_cast<const float*>(&dv);
+  const OpChan c = op_chan<BWD>(a, b, ch, tab, ch0);
+  float t0 = 0.f, t1 = 0.f;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) op_stat1<BWD>(a, c, xe[e], de[e], mean, rstd, t0, t1);
+  s0 += (double)t0; s1 += (double)t1;
+}
+
+// One float4 of slab (b, g): where it lives.  q: float4 index inside the slab.
+struct OpAt { int ch, p4; };
+__device__ __forceinline__ OpAt op_at(const OpArgs& a, int g, int q) {
+  const int pl = q / a.hw4;
+  return OpAt{g * (a.C / a.G) + pl, q - pl * a.hw4};
+}
+
+// where float4 q of the slab is read from (forward: one of the two sources) / written to (backward: one of the two
+// destinations); p1 serves the channels below C1, p2 (nullable: p1 is then the whole [n][C][hw] tensor) the rest
+template <typename T>
+__device__ __forceinline__ T* op_side(const OpArgs& a, T* p1, T* p2, int b, int64_t base, int q, const OpAt& at) {
+  if (!p2) return p1 + (base + q);
+  return at.ch < a.C1 ? p1 + op_index(b, a.C1, at.ch, a.hw4, at.p4) : p2 + op_index(b, a.C - a.C1, at.ch - a.C1, a.hw4, at.p4);
+}
+
+// normalise (forward) / differentiate (backward) one float4 held in registers and write it
+template <bool BWD>
+__device__ __forceinline__ void op_apply(const OpArgs& a, int b, int64_t base, int q, const OpAt& at, const float4& xv,
+                                         const float4& dv, float mean, float rstd, float m0, float m1, float4* __restrict__ out1,
+                                         float4* __restrict__ out2, float4* __restrict__ xcat, const float4* __restrict__ acc,
+                                         const float* tab, int ch0) {
+  const OpChan c = op_chan<true>(a, b, at.ch, tab, ch0);
+  const float* xe = reinterpret_cast<const float*>(&xv);
+  const float* de = reinterpret_cast<const float*>(&dv);
+  float4 o;
+  float* oe = reinterpret_cast<float*>(&o);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) oe[e] = op_apply1<BWD>(a, c, xe[e], de[e], mean, rstd, m0, m1);
+  if (!BWD) {
+    out1[base + q] = o;
+    if (xcat) xcat[base + q] = xv;
+  } else {
+    if (acc) {
+      const float4 av = acc[base + q];
+      o.x = o.x + av.x; o.y = o.y + av.y; o.z = o.z + av.z; o.w = o.w + av.w;
+    }
+    *op_side(a, out1, out2, b, base, q, at) = o;
+  }
+}
+
+// thread 0: the slab's totals -> st[0..1] = mean, rstd (forward) / st[2..3] = the two means of the backward
+template <bool BWD>
+__device__ __forceinline__ void op_totals(const OpArgs& a, double n, double t0, double t1, float* st) {
+  if (!BWD) {
+    const double m = t0 / n;
+    st[0] = (float)m;
+    st[1] = (float)(1.0 / sqrt(fmax(t1 / n - m * m, 0.0) + (double)a.eps));
+  } else {
+    st[2] = (float)(t0 / n);
+    st[3] = (float)(t1 / n);
+  }
+}
+
+// x: two sources in the forward (x2 nullable), one in the backward.  `ws` is written and read by several workgroups
+// of this launch: agent-scope atomics only, no const / __restrict__ on it.
+template <bool BWD>
+__global__ __launch_bounds__(NHMC_BLOCK) void k_gn_onepass(const float4* __restrict__ x1, const float4* __restrict__ x2,
+                                                           const float4* __restrict__ dy, const double* __restrict__ fwd_ws,
+                                                           OpArgs a, double* ws, float4* __restrict__ out1,
+                                                           float4* __restrict__ out2, float4* __restrict__ xcat,
+                                                           const float4* __restrict__ acc) {
+  const int bg = blockIdx.y, split = blockIdx.x, tid = threadIdx.x;
+  const int b = bg / a.G, g = bg % a.G;
+  const int64_t base = (int64_t)bg * a.n4;
+  const double n = (double)(a.C / a.G) * (double)a.hw4 * 4.0;
+  __shared__ double red[8];
+  __shared__ float st[4];
+  __shared__ int arrived;
+  __shared__ double part[2 * OP_MAX_SPLITS];        // the partials of a slab, one lane loads one
+  __shared__ float chan[3 * OP_CHAN_LDS];
+  const int cpg = a.C / a.G, ch0 = g * cpg;
+  const float* tab = cpg <= OP_CHAN_LDS ? chan : nullptr;
+  if (tab && tid < cpg) {
+    const OpChan c = op_chan<true>(a, b, ch0 + tid);
+    chan[3 * tid] = c.pb; chan[3 * tid + 1] = c.ga; chan[3 * tid + 2] = c.be;
+  }
+  float mean = 0.f, rstd = 0.f;
+  if (BWD) {
+    // the forward's partials: one lane each (a serial chain of dependent loads costs more than the share itself), then
+    // thread 0 adds them in the order k = 0 .. fwd_splits - 1
+    if (tid < a.fwd_splits) { part[2 * tid] = fwd_ws[((int64_t)bg * a.fwd_splits + tid) * 2]; part[2 * tid + 1] = fwd_ws[((int64_t)bg * a.fwd_splits + tid) * 2 + 1]; }
+    __syncthreads();
+    if (tid == 0) {
+      double s = 0.0, ss = 0.0;
+#pragma unroll 2
+      for (int k = 0; k < a.fwd_splits; ++k) { s += part[2 * k]; ss += part[2 * k + 1]; }
+      op_totals<false>(a, n, s, ss, st);
+    }
+    __syncthreads();
+    mean = st[0]; rstd = st[1];
+  }
+
+  // ---- the share of this workgroup, once, into registers
+  float4 xv[OP_K], dv[OP_K];
+#pragma unroll
+  for (int i = 0; i < OP_K; ++i) {
+    const int q = split * OP_SHARE + i * NHMC_BLOCK + tid;
+    xv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    dv[i] = xv[i];
+    if (q < a.n4) {
+      xv[i] = *op_side(a, x1, BWD ? nullptr : x2, b, base, q, op_at(a, g, q));
+      if (BWD) dv[i] = dy[base + q];
+    }
+  }
+  if (!BWD) __syncthreads();                       // `chan` is complete (the backward has passed a barrier already)
+  double v[2] = {0.0, 0.0};
+#pragma unroll
+  for (int i = 0; i < OP_K; ++i) {
+    if (i % 2 == 0) __builtin_amdgcn_sched_barrier(0);      // as in the last loop of this kernel
+    const int q = split * OP_SHARE + i * NHMC_BLOCK + tid;
+    if (q < a.n4) op_stat<BWD>(a, b, op_at(a, g, q).ch, xv[i], dv[i], mean, rstd, v[0], v[1], tab, ch0);
+  }
+  op_block_sum(v, red);                       // thread 0 holds the partial of this share
+
+  // ---- the sums of the whole slab
+  double* slab_ws = ws + (int64_t)bg * a.splits * 2;
+  double t0 = 0.0, t1 = 0.0;                       // thread 0: totals in the order k = 0 .. splits - 1
+  if (a.splits == 1) {
+    if (tid == 0) { slab_ws[0] = v[0]; slab_ws[1] = v[1]; t0 = v[0]; t1 = v[1]; }
+  } else {
+    if (tid < NHMC_WAVE) {                         // wave 0: lane 0 publishes, then one lane per partial of the slab
+      if (tid == 0) {
+        __hip_atomic_store(slab_ws + split * 2, v[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(slab_ws + split * 2 + 1, v[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      // the data is the flag: a word is there when it no longer holds the pattern the launch's memset left
+      unsigned long long* slot = reinterpret_cast<unsigned long long*>(slab_ws) + 2 * (tid < a.splits ? tid : 0);
+      unsigned long long w0 = OP_EMPTY, w1 = OP_EMPTY;
+      int ok = 0;
+      for (unsigned spin = 0; spin < a.polls; ++spin) {
+        w0 = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        w1 = __hip_atomic_load(slot + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ok = __all(w0 != OP_EMPTY && w1 != OP_EMPTY);
+        if (ok) break;
+        __builtin_amdgcn_s_sleep(8);
+      }
+      if (ok && tid < a.splits) { part[2 * tid] = __longlong_as_double((long long)w0); part[2 * tid + 1] = __longlong_as_double((long long)w1); }
+      if (tid == 0) arrived = ok;
+    }
+    __syncthreads();
+    if (tid == 0 && arrived) {
+#pragma unroll 2                                   // (an 8-fold unrolled LDS read here would set the register count)
+      for (int k = 0; k < a.splits; ++k) { t0 += part[2 * k]; t1 += part[2 * k + 1]; }
+    }
+    if (__builtin_expect(!__builtin_amdgcn_readfirstlane(arrived), 0)) {   // a scalar: a uniform branch to the compiler too
+      // Bounded wait expired: the other shares of the slab from memory, as their owners reduce them.  Element by element
+      // in rolled loops: the share in registers stays live across this branch, which is rarely taken and must not set
+      // the kernel's register count; the arithmetic per element and its order are those of the register path.
+      for (int k = 0; k < a.splits; ++k) {
+        double p[2] = {0.0, 0.0};
+        if (k != split) {
+#pragma unroll 1
+          for (int i = 0; i < OP_K; ++i) {
+            const int q = k * OP_SHARE + i * NHMC_BLOCK + tid;
+            if (q >= a.n4) continue;
+            const OpAt at = op_at(a, g, q);
+            const OpChan c = op_chan<BWD>(a, b, at.ch, tab, ch0);
+            const float* xs = reinterpret_cast<const float*>(op_side(a, x1, BWD ? nullptr : x2, b, base, q, at));
+            const float* ds = reinterpret_cast<const float*>(dy + (base + q));
+            float u0 = 0.f, u1 = 0.f;
+#pragma unroll 1
+            for (int e = 0; e < 4; ++e) op_stat1<BWD>(a, c, xs[e], BWD ? ds[e] : 0.0f, mean, rstd, u0, u1);
+            p[0] += (double)u0; p[1] += (double)u1;
+          }
+          op_block_sum(p, red);
+        }
+        if (tid == 0) { t0 += k == split ? v[0] : p[0]; t1 += k == split ? v[1] : p[1]; }
+        __syncthreads();                           // `red` is free again
+      }
+    }
+  }
+  if (tid == 0) op_totals<BWD>(a, n, t0, t1, st);
+  if (!BWD && tid == 0 && split == 0) {            // the slab totals behind the partials: a one-split workspace
+    double* tot = ws + ((int64_t)gridDim.y * a.splits + bg) * 2;
+    tot[0] = t0; tot[1] = t1;
+  }
+  __syncthreads();
+  mean = st[0]; rstd = st[1];
+  const float m0 = st[2], m1 = st[3];
+
+  // ---- normalise / differentiate the share from registers
+#pragma unroll
+  for (int i = 0; i < OP_K; ++i) {
+    // the share fills 32 / 64 VGPRs: keep the scheduler from hoisting all eight `acc` loads on top of them, and from
+    // carrying the plane index and channel terms of all eight float4 over from the statistics (q is opaque here, they
+    // are formed again): 71 instead of 87 VGPRs forward, 126 instead of 146 backward
+    if (i % 2 == 0) __builtin_amdgcn_sched_barrier(0);
+    int q = split * OP_SHARE + i * NHMC_BLOCK + tid;
+    asm volatile("" : "+v"(q));
+    if (q < a.n4) op_apply<BWD>(a, b, base, q, op_at(a, g, q), xv[i], dv[i], mean, rstd, m0, m1, out1, out2, xcat, acc, tab, ch0);
+  }
+}
+
+int op_splits(int n, int C, int G, int64_t hw) {
+  if (n <= 0 || C <= 0 || G <= 0 || hw <= 0 || C % G || hw % 4 || (int64_t)n * G > 65535) return 0;
+  const int64_t n4 = (int64_t)(C / G) * hw / 4, s = (n4 + OP_SHARE - 1) / OP_SHARE;
+  return s > OP_MAX_SPLITS ? 0 : (int)s;
+}
+
+int op_check(const void* x, const void* gamma, const void* beta, const void* ws, int n, int C, int G, int64_t hw, int flags,
+             int* splits) {
+  if (!x || !gamma || !beta || !ws || n <= 0 || C <= 0 || G <= 0 || hw <= 0 || (flags & ~NHMC_GN_ONEPASS_NOWAIT)) return NHMC_ERR_ARG;
+  if (!(*splits = op_splits(n, C, G, hw))) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(x) || !nhmc_aligned16(ws)) return NHMC_ERR_ALIGN;
+  return NHMC_OK;
+}
+
+// every word of the workspace <- the "not yet published" pattern, by a launch of its own ahead of the one-pass kernel on
+// the same stream (a kernel node under capture, ordered like every other launch of the stream).  A kernel and not
+// hipMemsetAsync as a workaround: observed on ROCm 7.2, with the memset captured into a graph the second replay of
+// tests/test_gn_onepass_gpu.py::test_graph_capture_replays_the_eager_bits read leftovers of the first replay as
+// published partials; with this kernel it does not.  The cause inside the runtime was not looked for.
+__global__ __launch_bounds__(NHMC_BLOCK) void k_gn_ws_fill(unsigned long long* ws, int64_t words) {
+  const int64_t i = (int64_t)blockIdx.x * NHMC_BLOCK + threadIdx.x;
+  if (i < words) ws[i] = OP_EMPTY;
+}
+int op_fill_ws(double* ws, int n, int G, int splits, hipStream_t st) {
+  const int64_t words = (int64_t)n * G * splits * 2;
+  NHMC_LAUNCH(k_gn_ws_fill, dim3((unsigned)((words + NHMC_BLOCK - 1) / NHMC_BLOCK)), dim3(NHMC_BLOCK), 0, st,
+              reinterpret_cast<unsigned long long*>(ws), words);
+  return nhmc_launch_status();
+}
+
+}  // namespace
+
+extern "C" int nhmc_gn_onepass_splits(int n, int channels, int groups, int64_t hw) { return op_splits(n, channels, groups, hw); }
+
+// Routing rule, from tools/gn_bench.py at 64 chains on MI355X (one-pass time / two-pass time, same run, nine FFHQ U-Net
+// shapes; profiles/r04_gn_onepass_roofline.txt).  Forward: 0.77 - 0.95 everywhere (0.89 - 0.93 at 1 - 2 splits) ->
+// one-pass wherever it is covered.  Backward: 0.91 - 0.95 at 4 to 32 splits per slab; a tie inside the run-to-run
+// spread at 1 and 2 splits (0.99, 1.01: small tensors, launch bound) and at 64 splits (0.99 median, 1.02 best of three:
+// 256 channels at 256x256, the longest wait for the slowest share) -> one-pass from 4 to 32 splits, two-pass otherwise,
+// unless the caller needs what only the one-pass backward offers (the gradient split into two contiguous tensors).
+extern "C" int nhmc_gn_onepass_prefers(int backward, int n, int channels, int groups, int64_t hw) {
+  const int s = op_splits(n, channels, groups, hw);
+  return backward ? (s >= 4 && s <= 32) : s > 0;
+}
+
+extern "C" int nhmc_gn_onepass_fwd(const float* x1, const float* x2, int c1, const float* gamma, const float* beta,
+                                   const float* film, int64_t film_stride, const float* pre, int64_t pre_stride, float eps,
+                                   int act, float* y, float* x_cat, double* ws, int flags, int n,
+                                   int channels, int groups, int64_t hw, nhmc_stream_t stream) {
+  int splits = 0;
+  int rc = op_check(x1, gamma, beta, ws, n, channels, groups, hw, flags, &splits);
+  if (rc) return rc;
+  if (!y || (x2 && !x_cat) || (!x2 && x_cat)) return NHMC_ERR_ARG;
+  if (x2 ? (c1 <= 0 || c1 >= channels) : c1 != channels) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(y) || !nhmc_aligned16(x2) || !nhmc_aligned16(x_cat)) return NHMC_ERR_ALIGN;
+  if (y == x1 || y == x2 || y == x_cat || x_cat == x1 || (x2 && x_cat == x2)) return NHMC_ERR_ARG;
+  const OpArgs a{gamma, beta, film, film_stride, pre, pre_stride, channels, groups, c1, (int)(hw / 4),
+                 (int)((int64_t)(channels / groups) * hw / 4), eps, act, splits, splits,
+                 (flags & NHMC_GN_ONEPASS_NOWAIT) ? 0u : OP_POLLS};
+  hipStream_t st = nhmc_s(stream);
+  if (splits > 1 && (rc = op_fill_ws(ws, n, groups, splits, st))) return rc;
+  NHMC_LAUNCH(k_gn_onepass<false>, dim3((unsigned)splits, (unsigned)(n * groups)), dim3(NHMC_BLOCK), 0, st, (const float4*)x1,
+              (const float4*)x2, (const float4*)nullptr, (const double*)nullptr, a, ws, (float4*)y,
+              (float4*)nullptr, (float4*)x_cat, (const float4*)nullptr);
+  return nhmc_launch_status();
+}
+
+extern "C" int nhmc_gn_onepass_bwd(const float* x, const float* dy, const float* gamma, const float* beta, const float* film,
+                                   int64_t film_stride, const float* pre, int64_t pre_stride, float eps, int act,
+                                   const double* fwd_ws, int fwd_splits, const float* dx_add, float* dx1, float* dx2, int c1,
+                                   double* ws, int flags, int n, int channels, int groups, int64_t hw, nhmc_stream_t stream) {
+  int splits = 0;
+  int rc = op_check(x, gamma, beta, ws, n, channels, groups, hw, flags, &splits);
+  if (rc) return rc;
+  if (!dy || !fwd_ws || !dx1 || fwd_splits <= 0 || fwd_splits > OP_MAX_SPLITS || fwd_ws == ws) return NHMC_ERR_ARG;
+  if (dx_add == dx1 || (dx2 && (dx_add == dx2 || dx1 == dx2))) return NHMC_ERR_ARG;
+  // not in place: a workgroup whose wait expired reads the other shares of x and dy again
+  if (dx1 == x || dx1 == dy || (dx2 && (dx2 == x || dx2 == dy))) return NHMC_ERR_ARG;
+  if (dx2 ? (c1 <= 0 || c1 >= channels) : c1 != channels) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(dy) || !nhmc_aligned16(dx1) || !nhmc_aligned16(dx2) || !nhmc_aligned16(dx_add)) return NHMC_ERR_ALIGN;
+  const OpArgs a{gamma, beta, film, film_stride, pre, pre_stride, channels, groups, c1, (int)(hw / 4),
+                 (int)((int64_t)(channels / groups) * hw / 4), eps, act, splits, fwd_splits,
+                 (flags & NHMC_GN_ONEPASS_NOWAIT) ? 0u : OP_POLLS};
+  hipStream_t st = nhmc_s(stream);
+  if (splits > 1 && (rc = op_fill_ws(ws, n, groups, splits, st))) return rc;
+  NHMC_LAUNCH(k_gn_onepass<true>, dim3((unsigned)splits, (unsigned)(n * groups)), dim3(NHMC_BLOCK), 0, st, (const float4*)x,
+              (const float4*)nullptr, (const float4*)dy, fwd_ws, a, ws, (float4*)dx1, (float4*)dx2,
+              (float4*)nullptr, (const float4*)dx_add);
+  return nhmc_launch_status();
+}

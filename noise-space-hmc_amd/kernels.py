@@ -6,6 +6,7 @@ the CURRENT torch stream.  No function allocates inside the library; outputs are
 created here.  Nothing falls back to torch arithmetic.
 """
 import ctypes as C
+import os
 
 import torch
 
@@ -904,11 +905,12 @@ def vq_nearest(z, codebook):
     return zq, idx
 
 
-def _gn_shape(x, gamma, groups, film, pre):
-    B, Cc = x.shape[0], x.shape[1]
-    hw = x[0, 0].numel()
+def _gn_shape(shape, gamma, groups, film, pre):
+    B, Cc, hw = shape[0], shape[1], 1
+    for d in shape[2:]:
+        hw *= d
     if gamma.numel() != Cc or Cc % groups or hw % 4:
-        raise _lib.NhmcError(f'fused GroupNorm: shape {tuple(x.shape)} / {groups} groups not covered (hw % 4 == 0, C % G == 0)')
+        raise _lib.NhmcError(f'fused GroupNorm: shape {tuple(shape)} / {groups} groups not covered (hw % 4 == 0, C % G == 0)')
     stride = pstride = 0
     if film is not None:
         if film.dim() != 2 or film.shape != (B, 2 * Cc) or film.stride(1) != 1:
@@ -925,13 +927,45 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-def gn_act_fwd(x, gamma, beta, groups, eps, act, film=None, pre=None):
-    """GroupNorm of (x + pre) (+ FiLM) (+ SiLU) forward -> (y, ws, splits); ws feeds gn_act_bwd."""
+GN_ONEPASS_NOWAIT = 1      # NHMC_GN_ONEPASS_NOWAIT of include/nhmc.h: tests only
+
+
+def gn_onepass_splits(n, channels, groups, hw):
+    """Split count of the one-pass GroupNorm kernels (csrc/gn_onepass.hip) for this shape; 0 when they do not cover it
+    or NHMC_GN_ONEPASS=0 (the A/B switch, read per call) keeps the two-pass kernels."""
+    if os.environ.get('NHMC_GN_ONEPASS', '1') == '0':
+        return 0
+    return _lib.load().nhmc_gn_onepass_splits(n, channels, groups, hw)
+
+
+def gn_act_fwd(x, gamma, beta, groups, eps, act, film=None, pre=None, x2=None, flags=0, onepass=None):
+    """GroupNorm of (x + pre) (+ FiLM) (+ SiLU) forward -> (y, ws, splits); ws feeds gn_act_bwd.
+    x2 (optional, [B, C2, ...] with x's spatial shape): the input is cat([x, x2], dim=1) -- gamma, beta, film, pre are
+    those of the concatenation -- and the result is (y, ws, splits, x_cat) with x_cat the concatenation itself, written
+    by the same kernel; needs the one-pass kernels (gn_onepass_splits(...) > 0).
+    onepass: None = the library's routing rule (nhmc_gn_onepass_prefers); True = one-pass wherever it covers the shape."""
     lib = _lib.load()
-    B, Cc, hw, stride, pstride = _gn_shape(x, gamma, groups, film, pre)
+    if x2 is not None and (x2.shape[0] != x.shape[0] or x2.shape[2:] != x.shape[2:]):
+        raise _lib.NhmcError('fused GroupNorm: the two sources must agree in batch and spatial shape')
+    C1 = x.shape[1]
+    shape = x.shape if x2 is None else (x.shape[0], C1 + x2.shape[1]) + tuple(x.shape[2:])
+    B, Cc, hw, stride, pstride = _gn_shape(shape, gamma, groups, film, pre)
+    one = gn_onepass_splits(B, Cc, groups, hw)
+    if x2 is not None and not one:
+        raise _lib.NhmcError('fused GroupNorm: two sources need the one-pass kernels, which do not cover this shape')
+    if one and x2 is None and not onepass and not lib.nhmc_gn_onepass_prefers(0, B, Cc, groups, hw):
+        one = 0
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    if one:
+        ws = torch.empty(B * groups * (one + 1) * 2, dtype=torch.float64, device=x.device)   # partials, then the slab totals
+        x_cat = torch.empty_like(y) if x2 is not None else None
+        rc = lib.nhmc_gn_onepass_fwd(_p(x, torch.float32, 'x'), _p(x2, torch.float32, 'x2'), C1, _p(gamma, torch.float32, 'gamma'),
+                                     _p(beta, torch.float32, 'beta'), _ptr(film), stride, _ptr(pre), pstride, float(eps), int(act),
+                                     _p(y), _p(x_cat), _p(ws), int(flags), B, Cc, groups, hw, _stream())
+        _lib.check(rc, 'nhmc_gn_onepass_fwd')
+        return (y, ws, one) if x2 is None else (y, ws, one, x_cat)
     splits = lib.nhmc_gn_splits(B, Cc, groups, hw)
     ws = torch.empty(B * groups * splits * 2, dtype=torch.float64, device=x.device)
-    y = torch.empty_like(x)
     rc = lib.nhmc_gn_act_fwd(_p(x, torch.float32, 'x'), _p(gamma, torch.float32, 'gamma'), _p(beta, torch.float32, 'beta'),
                              _ptr(film), stride, _ptr(pre), pstride, float(eps), int(act), _p(y), _p(ws), splits, B, Cc, groups,
                              hw, _stream())
@@ -939,20 +973,47 @@ def gn_act_fwd(x, gamma, beta, groups, eps, act, film=None, pre=None):
     return y, ws, splits
 
 
-def gn_act_bwd(x, dy, gamma, beta, groups, eps, act, film, fwd_ws, splits, pre=None, add=None):
+def gn_act_bwd(x, dy, gamma, beta, groups, eps, act, film, fwd_ws, splits, pre=None, add=None, c1=None, flags=0, onepass=None):
     """Input gradient of gn_act_fwd (parameters, FiLM and pre-bias terms are constants of the path).
-    add (optional, x's shape): a second gradient of x, added in the same pass."""
+    add (optional, x's shape): a second gradient of x, added in the same pass.
+    c1 (optional, 0 < c1 < C): the gradient is returned as two contiguous tensors (dx[:, :c1], dx[:, c1:]); needs the
+    one-pass kernels.  onepass: as in gn_act_fwd."""
     lib = _lib.load()
-    B, Cc, hw, stride, pstride = _gn_shape(x, gamma, groups, film, pre)
-    ws = torch.empty(B * groups * splits * 2, dtype=torch.float64, device=x.device)
-    dx = torch.empty_like(x)
-    if add is not None and (add.shape != x.shape or add.data_ptr() == dx.data_ptr()):
+    B, Cc, hw, stride, pstride = _gn_shape(x.shape, gamma, groups, film, pre)
+    one = gn_onepass_splits(B, Cc, groups, hw)
+    if c1 is not None and not one:
+        raise _lib.NhmcError('fused GroupNorm: a split gradient needs the one-pass kernels, which do not cover this shape')
+    if one and c1 is None and not onepass and not lib.nhmc_gn_onepass_prefers(1, B, Cc, groups, hw):
+        one = 0
+    if add is not None and add.shape != x.shape:
         raise _lib.NhmcError('gn_act_bwd: `add` must have the shape of x')
-    rc = lib.nhmc_gn_act_bwd(_p(x, torch.float32, 'x'), _p(dy, torch.float32, 'dy'), _p(gamma, torch.float32, 'gamma'),
-                             _p(beta, torch.float32, 'beta'), _ptr(film), stride, _ptr(pre), pstride, float(eps), int(act),
-                             _p(fwd_ws, torch.float64), _p(add, torch.float32, 'add') if add is not None else _ptr(None), _p(dx),
-                             _p(ws), splits, B, Cc, groups, hw, _stream())
-    _lib.check(rc, 'nhmc_gn_act_bwd')
+    addp = _p(add, torch.float32, 'add') if add is not None else _ptr(None)
+    fwd_splits, own = splits, splits
+    fwd_p = _p(fwd_ws, torch.float64)
+    if fwd_ws.numel() == B * groups * (splits + 1) * 2:
+        # a one-pass forward's workspace: its trailing one-split block (the slab totals) serves any backward, which
+        # then chooses its own split count
+        fwd_p, fwd_splits = C.c_void_p(fwd_ws.data_ptr() + B * groups * splits * 16), 1
+        own = lib.nhmc_gn_splits(B, Cc, groups, hw)
+    if one:
+        ws = torch.empty(B * groups * one * 2, dtype=torch.float64, device=x.device)
+        if c1 is None:
+            dx1, dx2 = torch.empty_like(x), None
+        else:
+            dx1 = torch.empty((B, c1) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+            dx2 = torch.empty((B, Cc - c1) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+        rc = lib.nhmc_gn_onepass_bwd(_p(x, torch.float32, 'x'), _p(dy, torch.float32, 'dy'), _p(gamma, torch.float32, 'gamma'),
+                                     _p(beta, torch.float32, 'beta'), _ptr(film), stride, _ptr(pre), pstride, float(eps), int(act),
+                                     fwd_p, int(fwd_splits), addp, _p(dx1), _p(dx2), Cc if c1 is None else int(c1),
+                                     _p(ws), int(flags), B, Cc, groups, hw, _stream())
+        _lib.check(rc, 'nhmc_gn_onepass_bwd')
+        return dx1 if c1 is None else (dx1, dx2)
+    ws = torch.empty(B * groups * own * 2, dtype=torch.float64, device=x.device)
+    dx = torch.empty_like(x)
+    rc = lib.nhmc_gn_act_bwd_fs(_p(x, torch.float32, 'x'), _p(dy, torch.float32, 'dy'), _p(gamma, torch.float32, 'gamma'),
+                                _p(beta, torch.float32, 'beta'), _ptr(film), stride, _ptr(pre), pstride, float(eps), int(act),
+                                fwd_p, int(fwd_splits), addp, _p(dx), _p(ws), own, B, Cc, groups, hw, _stream())
+    _lib.check(rc, 'nhmc_gn_act_bwd_fs')
     return dx
 
 

@@ -38,9 +38,13 @@ def sinusoid(t, dim, freqs=None):
 
 
 class _GroupNormAct(torch.autograd.Function):
-    """y = act(GroupNorm(x + pre) (1 + scale) + shift) on the fused HIP kernels (csrc/gn_act.hip): 2 reads + 1 write forward,
-    4 reads + 1 write for the input gradient, nothing but x saved -- against 5R + 4W / 7R + 3W for the ATen op sequence
-    the reference's GroupNorm32 + scale-shift + SiLU lowers to (unet_ffhq.py:310-321)."""
+    """y = act(GroupNorm(x + pre) (1 + scale) + shift) on the fused HIP kernels: 1 read + 1 write forward, 2 reads + 1 write
+    for the input gradient on the one-pass kernels (csrc/gn_onepass.hip: a slab's statistics are exchanged between the
+    workgroups that hold it in registers); 2 reads + 1 write / 4 reads + 1 write on the two-pass kernels (csrc/gn_act.hip),
+    which serve the shapes the one-pass kernels do not cover or are not faster at (nhmc_gn_onepass_prefers) and
+    NHMC_GN_ONEPASS=0.  Nothing but x is saved -- against
+    5R + 4W / 7R + 3W for the ATen op sequence the reference's GroupNorm32 + scale-shift + SiLU lowers to
+    (unet_ffhq.py:310-321)."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, film, pre, groups, eps, act):
@@ -90,6 +94,34 @@ class _GroupNormActFork(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None
 
 
+class _GroupNormActCat(torch.autograd.Function):
+    """_GroupNormActFork for a block input that arrives as two tensors, (h, skip) for cat([h, skip], dim=1) -- every
+    output block of the U-Net (unet_ffhq.py:731 `th.cat([h, hs.pop()], dim=1)`).  The one-pass forward kernel reads the
+    two sources and writes the concatenation (for the skip path's 1x1 convolution) next to y from the same load, so
+    torch.cat's pass does not run; the backward writes the gradient as two contiguous tensors, so neither does the
+    strided slicing of cat's backward nor the .contiguous() copies behind it."""
+
+    @staticmethod
+    def forward(ctx, h, skip, gamma, beta, groups, eps, act):
+        hc, sc = h if h.is_contiguous() else h.contiguous(), skip if skip.is_contiguous() else skip.contiguous()
+        y, ws, splits, x_cat = K.gn_act_fwd(hc, gamma, beta, groups, eps, act, x2=sc)
+        ctx.save_for_backward(x_cat, gamma, beta, ws)
+        ctx.meta = (groups, eps, act, splits, hc.shape[1])
+        return y, x_cat
+
+    @staticmethod
+    def backward(ctx, dy, dx_skip):
+        x_cat, gamma, beta, ws = ctx.saved_tensors
+        groups, eps, act, splits, c1 = ctx.meta
+        if dy is None:
+            return dx_skip[:, :c1], dx_skip[:, c1:], None, None, None, None, None
+        dy = dy if dy.is_contiguous() else dy.contiguous()
+        if dx_skip is not None and not dx_skip.is_contiguous():
+            dx_skip = dx_skip.contiguous()
+        dh, dskip = K.gn_act_bwd(x_cat, dy, gamma, beta, groups, eps, act, None, ws, splits, add=dx_skip, c1=c1)
+        return dh, dskip, None, None, None, None, None
+
+
 class _BiasAdd2(torch.autograd.Function):
     """(h + bias_c) + other in one pass; the gradient reaches h and other unchanged."""
 
@@ -134,6 +166,21 @@ def group_norm_act_fork(gn, x, act=True, act_fn=F.silu):
     if x.requires_grad and torch.is_grad_enabled() and fused_glue(x, gn.weight, gn.bias):
         return _GroupNormActFork.apply(x, gn.weight, gn.bias, None, None, gn.num_groups, gn.eps, act)
     return group_norm_act(gn, x, act=act, act_fn=act_fn), x
+
+
+def pair_glue(gn, h, skip):
+    """True when group_norm_act_pair runs on the two-source one-pass kernels."""
+    return fused_glue(h, gn.weight, gn.bias) and skip.is_cuda and skip.dtype == h.dtype and skip.shape[2:] == h.shape[2:] \
+        and K.gn_onepass_splits(h.shape[0], h.shape[1] + skip.shape[1], gn.num_groups, h[0, 0].numel()) > 0
+
+
+def group_norm_act_pair(gn, h, skip, act=True, act_fn=F.silu):
+    """group_norm_act_fork(gn, cat([h, skip], dim=1)) -> (y, x_cat) without torch.cat where the one-pass kernels cover the
+    shape (_GroupNormActCat); the concatenation + the fork otherwise (CPU, float64, trainable parameters,
+    NHMC_FUSED_GN=0, NHMC_GN_ONEPASS=0)."""
+    if pair_glue(gn, h, skip):
+        return _GroupNormActCat.apply(h, skip, gn.weight, gn.bias, gn.num_groups, gn.eps, act)
+    return group_norm_act_fork(gn, torch.cat([h, skip], dim=1), act=act, act_fn=act_fn)
 
 
 def conv_nobias(conv, x):
@@ -193,7 +240,11 @@ class ResBlock(nn.Module):
         self.skip_connection = nn.Identity() if out_ch == ch else nn.Conv2d(ch, out_ch, 1)
 
     def forward(self, x, emb):
-        h, x = group_norm_act_fork(self.in_layers[0], x)                 # GroupNorm + SiLU; x goes on to the skip path
+        """x: the block input, or a pair (h, skip) standing for cat([h, skip], dim=1) (the output blocks)."""
+        if isinstance(x, tuple):
+            h, x = group_norm_act_pair(self.in_layers[0], *x)
+        else:
+            h, x = group_norm_act_fork(self.in_layers[0], x)             # GroupNorm + SiLU; x goes on to the skip path
         if self.resample:
             h, x = self.h_upd(h), self.x_upd(x)
         conv1, conv2, film = self.in_layers[2], self.out_layers[3], self.emb_layers(emb)
@@ -282,7 +333,8 @@ class UNetModel(nn.Module):
             hs.append(h)
         h = self.middle_block(h, emb)
         for blk in self.output_blocks:
-            h = blk(torch.cat([h, hs.pop()], dim=1), emb)
+            # the pair goes to the block's first GroupNorm kernel, which forms the concatenation as a by-product
+            h = blk((h, hs.pop()) if fused_glue(h) else torch.cat([h, hs.pop()], dim=1), emb)
         return self.out[2](group_norm_act(self.out[0], h))
 
 

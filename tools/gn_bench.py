@@ -1,12 +1,20 @@
 """Fused GroupNorm (+ FiLM + SiLU) kernels of the score network against the HBM roofline, at the FFHQ U-Net's shapes
-(64 chains).  Forward = stats (R x) + apply (R x, W y) = 3 passes; backward = stats (R x, dy) + apply (R x, dy, W dx) = 5.
-Usage: python tools/gn_bench.py [chains]"""
+(64 chains), one-pass (csrc/gn_onepass.hip) and two-pass (csrc/gn_act.hip, NHMC_GN_ONEPASS=0) side by side in one process.
+Passes over the activation that the bandwidth figures divide by:
+    two-pass   forward = stats (R x) + apply (R x, W y) = 3;  backward = stats (R x, dy) + apply (R x, dy, W dx) = 5
+    one-pass   forward = R x, W y = 2;                        backward = R x, dy, W dx = 3
+    default    what kernels.gn_act_fwd / gn_act_bwd run without a switch (nhmc_gn_onepass_prefers): the one-pass forward,
+               and the two-pass backward fed from the slab totals the one-pass forward leaves (fwd_splits = 1)
+A shape the one-pass kernels do not cover prints its two-pass figures twice.
+Usage: python tools/gn_bench.py [chains] [rounds]"""
+import os
 import sys
 import torch
 sys.path.insert(0, '.')
 import nhmc.kernels as K
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 dev = torch.device('cuda')
 
 
@@ -23,15 +31,38 @@ def timeit(f, n=10):
     return e0.elapsed_time(e1) / n
 
 
+def mode(onepass):
+    os.environ['NHMC_GN_ONEPASS'] = '1' if onepass else '0'
+
+
 for Cc, res in ((128, 256), (256, 256), (128, 128), (256, 128), (384, 128), (256, 64), (512, 64), (512, 32), (1024, 16)):
     x = torch.randn(B, Cc, res, res, device=dev)
     dy = torch.randn_like(x)
     gamma, beta = torch.randn(Cc, device=dev), torch.randn(Cc, device=dev)
     film = torch.randn(B, 2 * Cc, device=dev)
     nbytes = x.numel() * 4
-    tf = timeit(lambda: K.gn_act_fwd(x, gamma, beta, 32, 1e-5, True, film=film))
-    y, ws, splits = K.gn_act_fwd(x, gamma, beta, 32, 1e-5, True, film=film)
-    tb = timeit(lambda: K.gn_act_bwd(x, dy, gamma, beta, 32, 1e-5, True, film, ws, splits))
-    print(f'[{B},{Cc},{res},{res}] {nbytes / 2 ** 30:.2f} GiB  splits {splits}: fwd {tf * 1e3:.0f} us = {3 * nbytes / tf / 1e9:.2f} TB/s (3 passes), '
-          f'bwd {tb * 1e3:.0f} us = {5 * nbytes / tb / 1e9:.2f} TB/s (5 passes)', flush=True)
-    del x, dy, y
+    one = K.gn_onepass_splits(B, Cc, 32, res * res)
+    t = {(o, d): [] for o in (False, True) for d in 'fb'}
+    t['default', 'b'] = []
+    for _ in range(ROUNDS):                       # interleaved rounds: the two variants see the same clocks
+        for o in (False, True):
+            mode(o)
+            y, ws, splits = K.gn_act_fwd(x, gamma, beta, 32, 1e-5, True, film=film, onepass=True)
+            t[o, 'f'].append(timeit(lambda: K.gn_act_fwd(x, gamma, beta, 32, 1e-5, True, film=film, onepass=True)))
+            t[o, 'b'].append(timeit(lambda: K.gn_act_bwd(x, dy, gamma, beta, 32, 1e-5, True, film, ws, splits, onepass=True)))
+            if o:
+                t['default', 'b'].append(timeit(lambda: K.gn_act_bwd(x, dy, gamma, beta, 32, 1e-5, True, film, ws, splits)))
+            del y
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    pf, pb = (2, 3) if one else (3, 5)
+    print(f'[{B},{Cc},{res},{res}] {nbytes / 2 ** 30:.2f} GiB  one-pass splits {one}\n'
+          f'    two-pass: fwd {med[False, "f"] * 1e3:.0f} us = {3 * nbytes / med[False, "f"] / 1e9:.2f} TB/s (3 passes), '
+          f'bwd {med[False, "b"] * 1e3:.0f} us = {5 * nbytes / med[False, "b"] / 1e9:.2f} TB/s (5 passes)\n'
+          f'    one-pass: fwd {med[True, "f"] * 1e3:.0f} us = {pf * nbytes / med[True, "f"] / 1e9:.2f} TB/s ({pf} passes), '
+          f'bwd {med[True, "b"] * 1e3:.0f} us = {pb * nbytes / med[True, "b"] / 1e9:.2f} TB/s ({pb} passes)\n'
+          f'    default route: bwd {med["default", "b"] * 1e3:.0f} us = {med["default", "b"] / med[False, "b"]:.3f} of the two-pass backward on a two-pass workspace\n'
+          f'    one-pass / two-pass: fwd {med[True, "f"] / med[False, "f"]:.3f}  bwd {med[True, "b"] / med[False, "b"]:.3f}'
+          f'   (min over rounds: fwd {min(t[True, "f"]) / min(t[False, "f"]):.3f}  bwd {min(t[True, "b"]) / min(t[False, "b"]):.3f})',
+          flush=True)
+    del x, dy
+os.environ.pop('NHMC_GN_ONEPASS', None)
