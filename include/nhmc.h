@@ -545,6 +545,31 @@ int nhmc_gn_onepass_bwd(const float* x, const float* dy, const float* gamma, con
 int nhmc_bias_add2(const float* h, const float* bias, const float* other, float* out, int n, int channels,
                    int64_t hw, nhmc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * a16 conv  3x3 stride-1 padding-1 convolution of the score network as Winograd F(2x2, 3x3) on the fp32 matrix cores
+ *      (csrc/wino_conv.hip), forward and backward-data; fp32 NCHW, one launch, no transformed tensor in HBM.
+ *   y[n][k][h][w] = sum_c sum_rs x[n][c][h + r - 1][w + s - 1] weight[k][c][r][s]   (+ bias[k]) (+ add[n][k][h][w])
+ * nhmc_wino_weights: u[16][c'][k'] = G g G^T of weight [channels_out][channels_in][3][3] (contiguous).
+ *   backward = 0: (c', k') = (channels_in, channels_out), g = weight[k'][c'] -- the forward convolution;
+ *   backward = 1: (c', k') = (channels_out, channels_in), g[r][s] = weight[c'][k'][2 - r][2 - s] -- the filter of the
+ *   backward-data pass, dx = conv(dy, g), which then runs through nhmc_conv3x3_wino like a forward one.
+ *   u holds 16 * channels_in * channels_out floats; it is a function of the weights alone (build once, reuse).
+ * nhmc_conv3x3_wino: x [n][c][h][w], u from nhmc_wino_weights with (c', k') = (c, k), y [n][k][h][w];
+ *   bias (nullable) [k], add (nullable) [n][k][h][w]: y = (acc + bias[k]) + add, the order of nhmc_bias_add2 (add may be y).
+ *   Accumulation runs over c ascending with no atomics: equal inputs give equal bits.
+ *   Covered (nhmc_conv3x3_wino_covers = 1): c % 8 == 0, k % 64 == 0, h % 4 == 0, w % 64 == 0, h * w <= 2^24; stride and
+ *   padding must both be 1.  Anything else: NHMC_ERR_SHAPE; null x / u / y or y == x: NHMC_ERR_ARG; a pointer off 16
+ *   bytes: NHMC_ERR_ALIGN; all before any device work.
+ * nhmc_conv3x3_wino_prefers(backward, n, c, k, h, w): 1 when this entry measured at most 0.90 of the vendor library's time
+ *   for the shape and direction (c, k: the channels of the convolution that runs, i.e. of dy and dx for backward = 1);
+ *   the table is next to its definition.  Only n = 64 was measured; other batch sizes follow the same (c, k, h, w) rows.
+ * ---------------------------------------------------------------------------------- */
+int nhmc_wino_weights(const float* weight, float* u, int backward, int channels_in, int channels_out, nhmc_stream_t stream);
+int nhmc_conv3x3_wino(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c, int k,
+                      int h, int w, int stride, int padding, nhmc_stream_t stream);
+int nhmc_conv3x3_wino_covers(int n, int c, int k, int h, int w);
+int nhmc_conv3x3_wino_prefers(int backward, int n, int c, int k, int h, int w);
+
 /* PSNR of clamp((xt+1)/2,0,1) against clamp((x_orig+1)/2,0,1)   main_sampling.py:738-739
  * ws: double[n_chains][nhmc_data_tiles(n_elem)]. */
 int nhmc_psnr(const float* xt, const float* x_orig, float* psnr, double* ws,

@@ -95,7 +95,11 @@ SIGNATURES = {
     'nhmc_gn_onepass_fwd': (I, [P, P, I, P, P, P, I64, P, I64, F, I, P, P, P, I, I, I, I, I64, P]),
     'nhmc_gn_onepass_bwd': (I, [P, P, P, P, P, I64, P, I64, F, I, P, I, P, P, P, I, P, I, I, I, I, I64, P]),
     'nhmc_bias_add2': (I, [P, P, P, P, I, I, I64, P]),
-    'nhmc_psnr': (I, [P, P, P, P, I, I64, P]),
+    'nhmc_wino_weights': (I, [P, P, I, I, I, P]),
+    'nhmc_conv3x3_wino': (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    'nhmc_conv3x3_wino_covers': (I, [I, I, I, I, I]),
+    'nhmc_conv3x3_wino_prefers': (I, [I, I, I, I, I, I]),
+    'nhmc_psnr':(I, [P, P, P, P, I, I64, P]),
     'nhmc_randn_philox': (I, [P, U64, U32, U32, F, I, I64, P]),
     'nhmc_copy_probe': (I, [P, P, I64, P]),
     'nhmc_uniform_philox': (I, [P, U64, U32, U32, I, P]),

@@ -1,0 +1,292 @@
+// 3x3 stride-1 padding-1 convolution of the score network as Winograd F(2x2, 3x3) in ONE launch, with the sixteen
+// per-frequency products on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact k-ascending fp32 FMA chains).
+//
+//   y[n,k,h,w] = sum_c sum_rs x[n,c,h+r-1,w+s-1] w[k,c,r,s]      NCHW fp32
+//   U = G w G^T   [16][C][K], built once per weight tensor by k_wino_weights (forward, or backward-data: the flipped,
+//                 transposed filter, so that dx = conv(dy, w') runs on the same kernel)
+//   V = B^T d B   from a halo patch of x, zero padding by predicate, staged in LDS per chunk of 8 channels (never in HBM)
+//   M_f[k, tile] += U_f[c, k] V_f[c, tile]   for f = 0..15, c ascending, no atomics: two runs give the same bits
+//   Y = A^T M A   in registers, stored as 256-byte row segments; optional epilogue (acc + bias[k]) + add, k_bias_add2's order
+//
+// Workgroup: 256 threads own 64 output channels x 64 tiles (2 tile rows x 32 tile columns = 4 x 64 outputs) x 16 frequencies.
+// Wave (kh, th) holds channels 32 kh .. + 31 of tile row th for all 16 frequencies: 16 accumulator tiles = 256 registers,
+// one wave per SIMD; every lane has all 16 frequencies of its outputs, so the output transform needs no exchange.
+// LDS: two buffers of U[16][8][64] + V[16][8][64] = 128 KB.  While chunk i is multiplied, chunk i + 1 is loaded into
+// registers (first half of the chunk's MFMAs), transformed and written to the other buffer (second half).
+#include "nhmc_common.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float wc_v2f __attribute__((ext_vector_type(2)));
+
+constexpr int WC_KBLK = 64;                      // output channels per workgroup
+constexpr int WC_ROWS = 4, WC_COLS = 64;         // output block: 2 x 32 tiles
+constexpr int WC_CHUNK = 8;                      // input channels per LDS stage
+constexpr int WC_OPER = 16 * WC_CHUNK * 64;      // floats of one operand (U or V) of one stage
+constexpr int WC_LDS_BYTES = 4 * WC_OPER * 4;    // 2 stages x (U + V)
+
+struct WinoArgs {
+  const float* x; const float* U; const float* bias; const float* add; float* y;
+  int C, K, H, W, row_blocks, col_blocks;
+};
+
+__global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
+  extern __shared__ float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
+  const int kh = wave & 1, th = wave >> 1;
+  const int C = a.C, K = a.K, H = a.H, W = a.W, HW = H * W;
+
+  // the K blocks of one spatial block, then the next spatial block, follow each other on one XCD (they share the input)
+  const int total = gridDim.x;
+  int logical = blockIdx.x;
+  if ((total & 7) == 0) logical = (logical & 7) * (total >> 3) + (logical >> 3);
+  const int kblocks = K / WC_KBLK;
+  const int kb = logical % kblocks, sp = logical / kblocks;
+  const int cb = sp % a.col_blocks, rb = (sp / a.col_blocks) % a.row_blocks, n = sp / (a.col_blocks * a.row_blocks);
+  const int h0 = rb * WC_ROWS, w0 = cb * WC_COLS;
+
+  // ---- loader roles: thread (lc, ltx) transforms channel lc of the chunk for the two tiles of tile column ltx
+  const int lc = tid >> 5, ltx = tid & 31;
+  int voff[6][4];
+  unsigned okmask = 0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    const int row = h0 - 1 + r;
+    const bool rok = (unsigned)row < (unsigned)H;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int col = w0 + 2 * ltx - 1 + s;
+      const bool ok = rok && (unsigned)col < (unsigned)W;
+      voff[r][s] = ok ? lc * HW + row * W + col : 0;
+      okmask |= ok ? 1u << (r * 4 + s) : 0u;
+    }
+  }
+  const float* xn = a.x + (int64_t)n * C * HW;
+  // U stage: 2048 float4 = rows (f, c) of 64 channels; thread takes float4 tid + 256 i: f = (tid >> 7) + 2 i, c = (tid >> 4) & 7
+  const float* ub = a.U + ((int64_t)(tid >> 7) * C + ((tid >> 4) & 7)) * K + kb * WC_KBLK + (tid & 15) * 4;
+  const int64_t ustep = (int64_t)2 * C * K;
+
+  float xr[6][4];
+  nhmc_v4f ur[8];
+  auto issue_loads = [&](int ch) {
+    const float* xs = xn + (int64_t)ch * WC_CHUNK * HW;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) xr[r][s] = xs[voff[r][s]];
+    const float* us = ub + (int64_t)ch * WC_CHUNK * K;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ur[i] = *reinterpret_cast<const nhmc_v4f*>(us + i * ustep);
+  };
+  auto d = [&](int r, int s) { return (okmask >> (r * 4 + s)) & 1u ? xr[r][s] : 0.0f; };
+  // column b of V = B^T d B for both tiles of the thread, and a quarter of the U stage -> LDS stage `st`
+  auto stage_part = [&](int st, int b) {
+    float* Us = lds + st * 2 * WC_OPER;
+    float* Vs = Us + WC_OPER;
+    float e[6];
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+      e[r] = b == 0 ? d(r, 0) - d(r, 2) : b == 1 ? d(r, 1) + d(r, 2) : b == 2 ? d(r, 2) - d(r, 1) : d(r, 1) - d(r, 3);
+#pragma unroll
+    for (int ty = 0; ty < 2; ++ty) {
+      const int r0 = 2 * ty;
+      const float v0 = e[r0] - e[r0 + 2], v1 = e[r0 + 1] + e[r0 + 2], v2 = e[r0 + 2] - e[r0 + 1], v3 = e[r0 + 1] - e[r0 + 3];
+      float* vp = Vs + lc * 64 + ty * 32 + ltx;
+      vp[(0 * 4 + b) * WC_CHUNK * 64] = v0;
+      vp[(1 * 4 + b) * WC_CHUNK * 64] = v1;
+      vp[(2 * 4 + b) * WC_CHUNK * 64] = v2;
+      vp[(3 * 4 + b) * WC_CHUNK * 64] = v3;
+    }
+#pragma unroll
+    for (int i = 2 * b; i < 2 * b + 2; ++i) *reinterpret_cast<nhmc_v4f*>(Us + (tid + 256 * i) * 4) = ur[i];
+  };
+
+  f32x16 acc[16];
+#pragma unroll
+  for (int f = 0; f < 16; ++f)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[f][r] = 0.0f;
+
+  // one chunk: 8 units of 8 MFMAs (k-step u / 2, frequencies 8 (u & 1) .. + 7); the operands of unit u + 1 are read from LDS
+  // before the MFMAs of unit u issue, and the following chunk is staged behind units 4 .. 7
+  const int aoff = lh * 64 + kh * 32 + lr, boff = lh * 64 + th * 32 + lr;
+  auto compute = [&](int st) {
+    const float* Us = lds + st * 2 * WC_OPER + aoff;
+    const float* Vs = lds + st * 2 * WC_OPER + WC_OPER + boff;
+    float av[2][8], bv[2][8];
+    auto fetch = [&](int u, float (&fa)[8], float (&fb)[8]) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int f = 8 * (u & 1) + j, o = (f * WC_CHUNK + 2 * (u >> 1)) * 64;
+        fa[j] = Us[o];
+        fb[j] = Vs[o];
+      }
+    };
+    fetch(0, av[0], bv[0]);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (u + 1 < 8) fetch(u + 1, av[(u + 1) & 1], bv[(u + 1) & 1]);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int f = 8 * (u & 1) + j;
+        acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u & 1][j], bv[u & 1][j], acc[f], 0, 0, 0);
+      }
+      if (u >= 4) stage_part(st ^ 1, u - 4);
+    }
+  };
+
+  const int chunks = C / WC_CHUNK;
+  issue_loads(0);
+#pragma unroll
+  for (int b = 0; b < 4; ++b) stage_part(0, b);
+  __syncthreads();
+  // ONE instance of the chunk body (a second one behind the loop made the register allocator shuffle the 256 accumulators
+  // through scratch): the last chunk stages itself once more into the idle buffer, which nobody reads.  do-while: the
+  // accumulators reach the epilogue from the loop only (C >= 8), not merged with their zero state
+  int ch = 0, st = 0;
+  do {
+    issue_loads(ch + 1 < chunks ? ch + 1 : ch);
+    __builtin_amdgcn_sched_barrier(0);
+    compute(st);
+    __syncthreads();                                // stage st ^ 1 is complete, and every wave is done reading stage st
+    st ^= 1;
+  } while (++ch < chunks);
+
+  // ---- Y = A^T M A per (channel, tile), epilogue, 256-byte row segments (32 lanes x float2)
+  const int oh = h0 + 2 * th, ow = w0 + 2 * lr;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int k = kb * WC_KBLK + kh * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+    float t[2][4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      t[0][b] = (acc[0 + b][r] + acc[4 + b][r]) + acc[8 + b][r];
+      t[1][b] = (acc[4 + b][r] - acc[8 + b][r]) - acc[12 + b][r];
+    }
+    const float bc = a.bias ? a.bias[k] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      wc_v2f o;
+      o.x = (t[i][0] + t[i][1]) + t[i][2];
+      o.y = (t[i][1] - t[i][2]) - t[i][3];
+      const int64_t at = (((int64_t)n * K + k) * H + oh + i) * W + ow;
+      if (a.bias) { o.x = o.x + bc; o.y = o.y + bc; }
+      if (a.add) {
+        const wc_v2f ad = *reinterpret_cast<const wc_v2f*>(a.add + at);
+        o.x = o.x + ad.x; o.y = o.y + ad.y;
+      }
+      __builtin_nontemporal_store(o, reinterpret_cast<wc_v2f*>(a.y + at));
+    }
+  }
+}
+
+// U[f = 4 a + b][ci][ko] = (G g G^T)[a][b], G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1].
+// forward: (ci, ko) = (c, k), g = w[k][c];  backward-data: (ci, ko) = (k, c), g[r][s] = w[k][c][2 - r][2 - s].
+__global__ __launch_bounds__(NHMC_BLOCK) void k_wino_weights(const float* __restrict__ w, float* __restrict__ U, int C, int K,
+                                                             int backward) {
+  const int CI = backward ? K : C, KO = backward ? C : K;
+  const int idx = blockIdx.x * NHMC_BLOCK + threadIdx.x;
+  if (idx >= CI * KO) return;
+  const int ci = idx / KO, ko = idx % KO;
+  const float* g = w + (int64_t)(backward ? ci * C + ko : ko * C + ci) * 9;
+  float t[4][3];
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    const float g0 = g[backward ? 8 - s : s], g1 = g[backward ? 5 - s : 3 + s], g2 = g[backward ? 2 - s : 6 + s];
+    t[0][s] = g0; t[1][s] = 0.5f * ((g0 + g1) + g2); t[2][s] = 0.5f * ((g0 - g1) + g2); t[3][s] = g2;
+  }
+  const int64_t plane = (int64_t)CI * KO;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float* u = U + (int64_t)(4 * r) * plane + idx;
+    u[0] = t[r][0];
+    u[plane] = 0.5f * ((t[r][0] + t[r][1]) + t[r][2]);
+    u[2 * plane] = 0.5f * ((t[r][0] - t[r][1]) + t[r][2]);
+    u[3 * plane] = t[r][2];
+  }
+}
+
+int wc_covers(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) {
+  if (n <= 0 || c < WC_CHUNK || c % WC_CHUNK || k < WC_KBLK || k % WC_KBLK || h < WC_ROWS || h % WC_ROWS || w < WC_COLS || w % WC_COLS)
+    return 0;
+  if (c > 65536 || k > 65536 || h * w > (1 << 24)) return 0;                     // 32-bit offsets inside a chunk / the weights
+  return n * (h / WC_ROWS) * (w / WC_COLS) * (k / WC_KBLK) < (int64_t)1 << 31;
+}
+
+}  // namespace
+
+extern "C" int nhmc_conv3x3_wino_covers(int n, int c, int k, int h, int w) { return wc_covers(n, c, k, h, w); }
+
+// Routing rule: (c, k, h, w) of the convolution that runs (backward-data: c = the gradient's channels, k = the layer's input
+// channels).  A (shape, direction) pair is listed only where tools/conv_bench.py measured this kernel at <= 0.90 of
+// F.conv2d's time at 64 chains on MI355X in the same process (profiles/r05_wino_conv_roofline.txt; the figure behind each
+// row is the larger of the median and the best-of-rounds ratio): a tie is never routed.  Other batch sizes follow the same
+// rows; only n = 64 was measured.
+extern "C" int nhmc_conv3x3_wino_prefers(int backward, int n, int c, int k, int h, int w) {
+  if (!wc_covers(n, c, k, h, w) || h != w) return 0;
+  struct Row { int backward, c, k, res; };
+  static const Row table[] = {
+      {0, 128, 128, 256},   // 128->128 forward: 0.694
+      {1, 128, 128, 256},   // 128->128 backward-data: 0.670
+      {0, 256, 128, 256},   // 256->128 forward: 0.693
+      {1, 128, 256, 256},   // 256->128 backward-data: 0.676
+      {0, 384, 128, 256},   // 384->128 forward: 0.696
+      {1, 128, 384, 256},   // 384->128 backward-data: 0.684
+      {0, 128, 256, 128},   // 128->256 forward: 0.706
+      {1, 256, 128, 128},   // 128->256 backward-data: 0.678
+      {0, 256, 256, 128},   // 256->256 forward: 0.713
+      {1, 256, 256, 128},   // 256->256 backward-data: 0.699
+      {0, 384, 256, 128},   // 384->256 forward: 0.718
+      {1, 256, 384, 128},   // 384->256 backward-data: 0.704
+      {0, 512, 256, 128},   // 512->256 forward: 0.722
+      {1, 256, 512, 128},   // 512->256 backward-data: 0.716
+      {0, 256, 256, 64},   // 256->256 forward: 0.708
+      {1, 256, 256, 64},   // 256->256 backward-data: 0.674
+      {0, 512, 256, 64},   // 512->256 forward: 0.716
+      {1, 256, 512, 64},   // 512->256 backward-data: 0.719
+      {0, 256, 512, 64},   // 256->512 forward: 0.725
+      {1, 512, 256, 64},   // 256->512 backward-data: 0.704
+      {0, 512, 512, 64},   // 512->512 forward: 0.731
+      {1, 512, 512, 64},   // 512->512 backward-data: 0.726
+      {0, 768, 256, 64},   // 768->256 forward: 0.715
+      {1, 256, 768, 64},   // 768->256 backward-data: 0.709
+      {0, 1024, 512, 64},   // 1024->512 forward: 0.734
+      {1, 512, 1024, 64},   // 1024->512 backward-data: 0.742
+  };
+  for (const Row& r : table)
+    if (r.backward == (backward != 0) && r.c == c && r.k == k && r.res == h) return 1;
+  return 0;
+}
+
+extern "C" int nhmc_wino_weights(const float* weight, float* u, int backward, int channels_in, int channels_out,
+                                 nhmc_stream_t stream) {
+  if (!weight || !u || (backward != 0 && backward != 1) || channels_in <= 0 || channels_out <= 0) return NHMC_ERR_ARG;
+  if (channels_in > 65536 || channels_out > 65536) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(u)) return NHMC_ERR_ALIGN;
+  const int pairs = channels_in * channels_out;
+  NHMC_LAUNCH(k_wino_weights, dim3((unsigned)((pairs + NHMC_BLOCK - 1) / NHMC_BLOCK)), dim3(NHMC_BLOCK), 0, nhmc_s(stream), weight,
+              u, channels_in, channels_out, backward);
+  return nhmc_launch_status();
+}
+
+extern "C" int nhmc_conv3x3_wino(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c,
+                                 int k, int h, int w, int stride, int padding, nhmc_stream_t stream) {
+  if (!x || !u || !y || y == x || (add && add == x)) return NHMC_ERR_ARG;
+  if (stride != 1 || padding != 1 || !wc_covers(n, c, k, h, w)) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(x) || !nhmc_aligned16(u) || !nhmc_aligned16(y) || !nhmc_aligned16(add)) return NHMC_ERR_ALIGN;
+  static bool attr_set[64] = {};                             // raise the dynamic-LDS limit once per device
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wino), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            WC_LDS_BYTES) != hipSuccess)
+      return NHMC_ERR_LAUNCH;
+    if (dev >= 0 && dev < 64) attr_set[dev] = true;
+  }
+  const WinoArgs a{x, u, bias, add, y, c, k, h, w, h / WC_ROWS, w / WC_COLS};
+  const int64_t blocks = (int64_t)n * a.row_blocks * a.col_blocks * (k / WC_KBLK);
+  NHMC_LAUNCH(k_conv3x3_wino, dim3((unsigned)blocks), dim3(256), WC_LDS_BYTES, nhmc_s(stream), a);
+  return nhmc_launch_status();
+}

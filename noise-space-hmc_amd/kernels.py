@@ -1029,6 +1029,70 @@ def bias_add2(h, bias, other):
     return out
 
 
+_wino_u = {}          # (id(weight), backward) -> (weakref to it, its version counter, data_ptr, U on its device)
+_wino_builds = 0
+
+
+def wino_weight_builds():
+    """How many times a transformed filter was built (tests: once per weight tensor and direction, again after an edit)."""
+    return _wino_builds
+
+
+def wino_weights(weight, backward=False):
+    """U = G w G^T [16][c'][k'] of a [K, C, 3, 3] filter for conv3x3_wino (backward: the filter of the backward-data pass).
+    Cached per LIVE weight tensor, version counter and storage address, like schedule.alpha_bar_table: the sampler's
+    networks are frozen, so a run builds each U once (during the calls that precede a graph capture); an in-place edit or
+    a move to another device rebuilds it."""
+    global _wino_builds
+    key = (id(weight), bool(backward))
+    hit = _wino_u.get(key)
+    if hit is not None and hit[0]() is weight and hit[1] == weight._version and hit[2] == weight.data_ptr():
+        return hit[3]
+    import weakref
+    lib = _lib.load()
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise _lib.NhmcError(f'wino_weights: a [K, C, 3, 3] filter is needed, got {tuple(weight.shape)}')
+    Kk, Cc = weight.shape[0], weight.shape[1]
+    wd = weight.detach()
+    u = torch.empty((16, Kk, Cc) if backward else (16, Cc, Kk), dtype=torch.float32, device=weight.device)
+    _lib.check(lib.nhmc_wino_weights(_p(wd, torch.float32, 'weight'), _p(u), int(bool(backward)), Cc, Kk, _stream()),
+               'nhmc_wino_weights')
+    _wino_builds += 1
+    for k in [k for k, v in _wino_u.items() if v[0]() is None]:
+        del _wino_u[k]
+    _wino_u[key] = (weakref.ref(weight), weight._version, weight.data_ptr(), u)
+    return u
+
+
+def conv3x3_wino_covers(n, c, k, h, w):
+    return bool(_lib.load().nhmc_conv3x3_wino_covers(n, c, k, h, w))
+
+
+def conv3x3_wino_prefers(backward, n, c, k, h, w):
+    """The library's routing rule (nhmc_conv3x3_wino_prefers); NHMC_WINO=0 (the A/B switch, read per call) answers no."""
+    if os.environ.get('NHMC_WINO', '1') == '0':
+        return False
+    return bool(_lib.load().nhmc_conv3x3_wino_prefers(int(bool(backward)), n, c, k, h, w))
+
+
+def conv3x3_wino(x, weight, bias=None, add=None, backward=False):
+    """conv2d(x, weight, stride 1, padding 1) (+ bias[k]) (+ add) on the Winograd MFMA kernel; backward=True: the
+    backward-data pass of that convolution, x being the output gradient [N, K, H, W] -> [N, C, H, W]."""
+    lib = _lib.load()
+    if x.dim() != 4 or weight.dim() != 4 or x.shape[1] != weight.shape[1 if not backward else 0]:
+        raise _lib.NhmcError(f'conv3x3_wino: x {tuple(x.shape)} does not match the filter {tuple(weight.shape)}')
+    u = wino_weights(weight, backward)
+    N, Cc, H, W = x.shape
+    Kk = u.shape[2]
+    y = torch.empty((N, Kk, H, W), dtype=torch.float32, device=x.device)
+    if (bias is not None and bias.numel() != Kk) or (add is not None and add.shape != y.shape):
+        raise _lib.NhmcError('conv3x3_wino: bias / add do not match the output')
+    rc = lib.nhmc_conv3x3_wino(_p(x, torch.float32, 'x'), _p(u), _p(bias, torch.float32, 'bias'), _p(add, torch.float32, 'add'),
+                               _p(y), N, Cc, Kk, H, W, 1, 1, _stream())
+    _lib.check(rc, 'nhmc_conv3x3_wino')
+    return y
+
+
 def psnr(xt, x_orig):
     lib = _lib.load()
     B, N = _chains_elems(xt)

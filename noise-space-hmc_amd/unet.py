@@ -183,9 +183,68 @@ def group_norm_act_pair(gn, h, skip, act=True, act_fn=F.silu):
     return group_norm_act_fork(gn, torch.cat([h, skip], dim=1), act=act, act_fn=act_fn)
 
 
-def conv_nobias(conv, x):
+class _Conv3x3Wino(torch.autograd.Function):
+    """A frozen 3x3 stride-1 padding-1 convolution (+ bias_k) (+ add) whose forward and / or backward-data pass runs on the
+    Winograd MFMA kernel (csrc/wino_conv.hip); `route` = (forward, backward) says which.  A pass that is not routed runs
+    the vendor library's kernel, as F.conv2d and its autograd node would.  Saves the filter only: there is no weight
+    gradient, and the gradient reaches `add` unchanged."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, add, route):
+        xc = x if x.is_contiguous() else x.contiguous()
+        if add is not None and not add.is_contiguous():
+            add = add.contiguous()
+        ctx.save_for_backward(weight)
+        ctx.route_bwd, ctx.x_shape = route[1], tuple(x.shape)
+        if route[0]:
+            return K.conv3x3_wino(xc, weight, bias, add)
+        h = F.conv2d(xc, weight, None, 1, 1)
+        return h if add is None else K.bias_add2(h, bias, add)
+
+    @staticmethod
+    def backward(ctx, g):
+        (weight,) = ctx.saved_tensors
+        dx = None
+        if ctx.needs_input_grad[0]:
+            gc = g if g.is_contiguous() else g.contiguous()
+            dx = K.conv3x3_wino(gc, weight, backward=True) if ctx.route_bwd \
+                else torch.nn.grad.conv2d_input(ctx.x_shape, weight, gc, 1, 1)
+        return dx, None, None, (g if ctx.needs_input_grad[3] else None), None
+
+
+def wino_route(conv, x, wino=None):
+    """(forward, backward) routing of `conv` applied to x onto the Winograd MFMA kernel, or None when it stays F.conv2d:
+    a frozen 3x3 stride-1 padding-1 convolution of fp32 GPU activations whose shape the kernel covers and, per direction,
+    the library's measured table prefers (wino=True: wherever it is covered -- tests); NHMC_WINO=0 keeps the vendor library."""
+    if wino is False or x.dim() != 4 or not fused_glue(x, conv.weight, conv.bias) or os.environ.get('NHMC_WINO', '1') == '0':
+        return None
+    if tuple(conv.kernel_size) != (3, 3) or tuple(conv.stride) != (1, 1) or conv.padding != (1, 1) \
+            or tuple(conv.dilation) != (1, 1) or conv.groups != 1 or conv.padding_mode != 'zeros':
+        return None
+    n, c, h, w = x.shape
+    k = conv.out_channels
+    fwd, bwd = K.conv3x3_wino_covers(n, c, k, h, w), K.conv3x3_wino_covers(n, k, c, h, w)
+    if not wino:
+        fwd, bwd = fwd and K.conv3x3_wino_prefers(0, n, c, k, h, w), bwd and K.conv3x3_wino_prefers(1, n, k, c, h, w)
+    bwd = bwd and x.requires_grad and torch.is_grad_enabled()
+    return (fwd, bwd) if fwd or bwd else None
+
+
+def conv_nobias(conv, x, wino=None):
     """The convolution without its bias (the fused glue adds it where the output is consumed)."""
+    route = wino_route(conv, x, wino)
+    if route is not None:
+        return _Conv3x3Wino.apply(x, conv.weight, None, None, route)
     return F.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
+
+
+def conv_bias_add2(conv, x, other, wino=None):
+    """(conv(x) + bias) + other: the residual add of a ResBlock, inside the convolution's epilogue where the Winograd kernel
+    takes the forward pass, on k_bias_add2 behind the convolution otherwise."""
+    route = wino_route(conv, x, wino)
+    if route is not None and route[0]:
+        return _Conv3x3Wino.apply(x, conv.weight, conv.bias, other, route)
+    return _BiasAdd2.apply(conv_nobias(conv, x, wino), conv.bias, other)
 
 
 class _Resample2x(torch.autograd.Function):
@@ -227,6 +286,7 @@ class Resample(nn.Module):
 
 class ResBlock(nn.Module):
     takes_emb = True
+    wino = None              # routing of the two 3x3 convolutions (wino_route): None = the measured table, True = forced (tests)
 
     def __init__(self, ch, emb_ch, out_ch=None, up=False, down=False):
         super().__init__()
@@ -251,8 +311,8 @@ class ResBlock(nn.Module):
         if fused_glue(h, conv1.bias, conv2.bias, film):
             # the two convolutions run without their broadcast bias passes: conv1's bias enters the next GroupNorm's
             # load, conv2's the residual add
-            h = group_norm_act(self.out_layers[0], conv_nobias(conv1, h), film=film, pre=conv1.bias)
-            return _BiasAdd2.apply(conv_nobias(conv2, h), conv2.bias, self.skip_connection(x))
+            h = group_norm_act(self.out_layers[0], conv_nobias(conv1, h, self.wino), film=film, pre=conv1.bias)
+            return conv_bias_add2(conv2, h, self.skip_connection(x), self.wino)
         h = group_norm_act(self.out_layers[0], conv1(h), film=film)      # scale-shift norm (FiLM) + SiLU
         return self.skip_connection(x) + conv2(h)
 
