@@ -90,15 +90,14 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_color(const float4* __restrict__
 
 // Last DDIM step VJP fused with the colorization data term: the clipped decode of every channel is recomputed from
 // (xt, e) in registers, weighted into the grey value, and the residual goes straight through the step's VJP
-// (same op order as k_mix_fwd + k_color<0> + k_mix_bwd, hence the same bits; -3T of traffic).
+// (nhmc_mix_decode / nhmc_mix_vjp_masked around k_color<0>'s arithmetic: the two-kernel path's bits; -3T of traffic).
 __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_color(
     const float4* __restrict__ xt, const float4* __restrict__ e, int e_channels, const float* __restrict__ at,
     const float* __restrict__ at_next, const float4* __restrict__ yin, float4* __restrict__ g_xt,
     float4* __restrict__ g_e, W wt, int channels, double* __restrict__ loss_ws, int64_t hw4) {
   const int chain = blockIdx.y;
   const int64_t q = (int64_t)blockIdx.x * NHMC_BLOCK + threadIdx.x;
-  const float a = at[chain], an = at_next[chain];
-  const float c1 = sqrtf(1.0f - a), c2 = sqrtf(a), c3 = sqrtf(an), c4 = sqrtf(1.0f - an);
+  const NhmcMix kc = nhmc_mix_coef(at, at_next, chain);
   float acc = 0.0f;
   if (q < hw4) {
     const int64_t xbase = (int64_t)chain * channels * hw4, ebase = (int64_t)chain * e_channels * hw4;
@@ -112,8 +111,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_color(
         const float* ee = reinterpret_cast<const float*>(&ev);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          uu[c][k] = (xe[k] - ee[k] * c1) / c2;
-          pre[c][k] = c3 * nhmc_clip1(uu[c][k]) + c4 * ee[k];
+          nhmc_mix_decode(kc, xe[k], ee[k], uu[c][k], pre[c][k]);
           const float term = wt.w[c] * nhmc_clip1(pre[c][k]);
           s[k] = c == 0 ? term : s[k] + term;
         }
@@ -133,11 +131,8 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_color(
         float* gee = reinterpret_cast<float*>(&oe);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          float gin = wt.w[c] * (wt.s * (wt.u * (-(2.0f * r[k]))));
-          gin = gin * nhmc_in1(pre[c][k]);
-          const float gu = ((gin * c3) * nhmc_in1(uu[c][k])) / c2;
-          gx[k] = gu;
-          gee[k] = c4 * gin + (-gu) * c1;
+          const float gin = wt.w[c] * (wt.s * (wt.u * (-(2.0f * r[k]))));
+          nhmc_mix_vjp_masked(kc, gin, nhmc_in1(pre[c][k]), nhmc_in1(uu[c][k]), gx[k], gee[k]);
         }
         nhmc_stnt(&g_xt[xbase + (int64_t)c * hw4 + q], ox);
         nhmc_stnt(&g_e[ebase + (int64_t)c * hw4 + q], oe);

@@ -11,25 +11,13 @@
 
 namespace {
 
-struct Coef { float c1, c2, c3, c4; };
-
-__device__ __forceinline__ Coef coef(const float* at, const float* at_next, int chain) {
-  const float a = at[chain], an = at_next[chain];
-  Coef c;
-  c.c1 = sqrtf(1.0f - a);    // (1 - at).sqrt()
-  c.c2 = sqrtf(a);           // at.sqrt()
-  c.c3 = sqrtf(an);          // at_next.sqrt()
-  c.c4 = sqrtf(1.0f - an);   // (1 - at_next).sqrt()
-  return c;
-}
-
 template <bool W_NEXT, bool W_X0, bool W_ADD>
 __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_fwd(
     const float4* __restrict__ xt, const float4* __restrict__ e, int64_t e_stride4,
     const float* __restrict__ at, const float* __restrict__ at_next, int final_clip,
     float4* __restrict__ xt_next, float4* __restrict__ x0_t, float4* __restrict__ add_up, int64_t n4) {
   const int chain = blockIdx.y;
-  const Coef k = coef(at, at_next, chain);
+  const NhmcMix k = nhmc_mix_coef(at, at_next, chain);
   const int64_t base = (int64_t)chain * n4, ebase = (int64_t)chain * e_stride4;
   const int64_t t0 = (int64_t)blockIdx.x * (NHMC_BLOCK * NHMC_VEC_PER_THREAD) + threadIdx.x;
   float4 xv[NHMC_VEC_PER_THREAD], ev[NHMC_VEC_PER_THREAD];
@@ -50,10 +38,10 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_fwd(
     float* oa = reinterpret_cast<float*>(&o_add);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float u = (xe[c] - ee[c] * k.c1) / k.c2;
+      float u, nx;
+      nhmc_mix_decode(k, xe[c], ee[c], u, nx);
       const float x0 = nhmc_clip1(u);
       const float add = k.c4 * ee[c];
-      float nx = k.c3 * x0 + add;
       if (final_clip) nx = nhmc_clip1(nx);
       on[c] = nx; o0[c] = x0; oa[c] = add;
     }
@@ -89,7 +77,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd(
     const float* __restrict__ at_next, int final_clip, float4* __restrict__ g_xt, float4* __restrict__ g_e,
     int64_t n4, int fill_sigma) {
   const int chain = blockIdx.y;
-  const Coef k = coef(at, at_next, chain);
+  const NhmcMix k = nhmc_mix_coef(at, at_next, chain);
   const int64_t base = (int64_t)chain * n4, ebase = (int64_t)chain * e_stride4;
   const int64_t t0 = (int64_t)blockIdx.x * (NHMC_BLOCK * NHMC_VEC_PER_THREAD) + threadIdx.x;
   float4 gv[NHMC_VEC_PER_THREAD], xv[NHMC_VEC_PER_THREAD], ev[NHMC_VEC_PER_THREAD], sv[NHMC_VEC_PER_THREAD];
@@ -118,46 +106,28 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd(
     float* gee = reinterpret_cast<float*>(&oe);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float u = (xe[c] - ee[c] * k.c1) / k.c2;
+      const float u = nhmc_mix_u(k, xe[c], ee[c]);
       float gin = ge[c];
-      if (final_clip) gin = gin * nhmc_in1(k.c3 * nhmc_clip1(u) + k.c4 * ee[c]);
+      if (final_clip) gin = gin * nhmc_in1(nhmc_mix_pre(k, u, ee[c]));
       // fused step: the gradient reaching x0 is gin*c3 (map_back); split surface: it is handed in
-      const float g0 = SPLIT ? se[c] : gin * k.c3;
-      const float gu = (g0 * nhmc_in1(u)) / k.c2;
-      gx[c] = gu;
-      gee[c] = k.c4 * gin + (-gu) * k.c1;
+      nhmc_mix_vjp_body(k, gin, SPLIT ? se[c] : gin * k.c3, nhmc_in1(u), gx[c], gee[c]);
     }
     nhmc_stnt(&g_xt[base + q], ox);
     if (g_e) nhmc_stnt(&g_e[ebase + q], oe);                 // g_e == nullptr: the score carries no gradient
   }
-  // learned-sigma channels of the score gradient are zero (the forward slices them away); a caller that keeps a
-  // persistent, pre-zeroed g_e buffer passes fill_sigma = 0 and saves this T of writes
-  const int64_t extra = (fill_sigma && g_e) ? e_stride4 - n4 : 0;
-  if (extra > 0) {
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int i = 0; i < NHMC_VEC_PER_THREAD; ++i) {
-      const int64_t q = t0 + (int64_t)i * NHMC_BLOCK;
-      if (q < extra) nhmc_stnt(&g_e[ebase + n4 + q], z);
-    }
-  }
+  nhmc_zero_sigma_half(g_e, ebase, n4, e_stride4, t0, fill_sigma && g_e);
 }
 
 // Last DDIM step VJP fused with the inpainting data term (primary BASELINE config): the clipped decode
 // xt_next = clip(c3*clip(u) + c4*e) is recomputed in registers (bit-identical to k_mix_fwd), the residual
 // r = y[slot] - xt_next and the upstream gradient gin = -2 r are formed on the fly, so the separate data-term pass
 // (R xt_next, W g) and this kernel's read of g disappear: -3T per leapfrog step and one launch.
-// PX = true: whole-pixel mask (what inpaint_random / inpaint_box build): instead of the dense CHW -> y map (a stream of
-// T per chain, L2-served) the kernel reads one 32-pixel mask word and its exclusive prefix count (16 KB of tables for
-// 256 x 256) and derives y index = channels * rank(pixel) + channel with a popcount.
-template <bool PX>
 __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_inpaint(
     const float4* __restrict__ xt, const float4* __restrict__ e, int64_t e_stride4, const float* __restrict__ at,
-    const float* __restrict__ at_next, const float* __restrict__ y, const int4* __restrict__ slot,
-    const uint32_t* __restrict__ mask_words, const int32_t* __restrict__ prefix, int channels, int64_t hw, int64_t m,
+    const float* __restrict__ at_next, const float* __restrict__ y, const int4* __restrict__ slot, int64_t m,
     float4* __restrict__ g_xt, float4* __restrict__ g_e, double* __restrict__ loss_ws, int64_t n4, int fill_sigma) {
   const int chain = blockIdx.y;
-  const Coef k = coef(at, at_next, chain);
+  const NhmcMix k = nhmc_mix_coef(at, at_next, chain);
   const int64_t base = (int64_t)chain * n4, ebase = (int64_t)chain * e_stride4;
   const float* yb = y + (int64_t)chain * m;
   const int64_t t0 = (int64_t)blockIdx.x * (NHMC_BLOCK * NHMC_VEC_PER_THREAD) + threadIdx.x;
@@ -167,24 +137,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_inpaint(
     const int64_t q = t0 + (int64_t)i * NHMC_BLOCK;
     if (q >= n4) continue;
     const float4 xv = nhmc_ldnt(&xt[base + q]), ev = nhmc_ldnt(&e[ebase + q]);
-    int4 sv;
-    if (PX) {
-      const int64_t el = q * 4;                              // first of 4 consecutive pixels of one channel (hw % 32 == 0)
-      const int ch = (int)(el / hw);
-      const int64_t p0 = el - (int64_t)ch * hw;
-      const uint32_t word = mask_words[p0 >> 5];
-      const int b0 = (int)(p0 & 31);
-      int rank = prefix[p0 >> 5] + __popc(word & ((1u << b0) - 1u));
-      int* so = reinterpret_cast<int*>(&sv);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const bool kept = (word >> (b0 + c)) & 1u;
-        so[c] = kept ? rank * channels + ch : -1;
-        rank += kept ? 1 : 0;
-      }
-    } else {
-      sv = slot[q];
-    }
+    const int4 sv = slot[q];
     const float* xe = reinterpret_cast<const float*>(&xv);
     const float* ee = reinterpret_cast<const float*>(&ev);
     const int* se = reinterpret_cast<const int*>(&sv);
@@ -193,39 +146,31 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_inpaint(
     float* gee = reinterpret_cast<float*>(&oe);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float u = (xe[c] - ee[c] * k.c1) / k.c2;
-      const float pre = k.c3 * nhmc_clip1(u) + k.c4 * ee[c];    // decode before the final clip
+      float u, pre;                                              // pre: decode before the final clip
+      nhmc_mix_decode(k, xe[c], ee[c], u, pre);
       float gin = 0.0f;
       if (se[c] >= 0) {
         const float r = yb[se[c]] - nhmc_clip1(pre);
         acc += (double)(r * r);
         gin = -(2.0f * r);
       }
-      gin = gin * nhmc_in1(pre);                                 // final clip mask
-      const float gu = ((gin * k.c3) * nhmc_in1(u)) / k.c2;
-      gx[c] = gu;
-      gee[c] = k.c4 * gin + (-gu) * k.c1;
+      nhmc_mix_vjp_masked(k, gin, nhmc_in1(pre), nhmc_in1(u), gx[c], gee[c]);
     }
     nhmc_stnt(&g_xt[base + q], ox);
     nhmc_stnt(&g_e[ebase + q], oe);
   }
-  const int64_t extra = fill_sigma ? e_stride4 - n4 : 0;
-  if (extra > 0) {
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int i = 0; i < NHMC_VEC_PER_THREAD; ++i) {
-      const int64_t q = t0 + (int64_t)i * NHMC_BLOCK;
-      if (q < extra) nhmc_stnt(&g_e[ebase + n4 + q], z);
-    }
-  }
+  nhmc_zero_sigma_half(g_e, ebase, n4, e_stride4, t0, fill_sigma);
   __shared__ double red[4];
   double v[1] = {acc};
   nhmc_block_sum<1>(v, red);
   if (threadIdx.x == 0) loss_ws[(int64_t)chain * gridDim.x + blockIdx.x] = v[0];
 }
 
-// Whole-pixel-mask form, restructured for latency (round 2; the form above reached 4.6 TB/s = 0.57 of the HBM peak with
-// no wasted traffic, i.e. it was latency / issue bound):
+// Whole-pixel-mask form (what inpaint_random / inpaint_box build): instead of the dense CHW -> y map (a stream of T per
+// chain, L2-served) the kernel reads one 32-pixel mask word and its exclusive prefix count (16 KB of tables for 256 x 256)
+// and derives y index = channels * rank(pixel) + channel with a popcount.  Structured for latency (round 2; round 1 did
+// this inside the kernel above and reached 4.6 TB/s = 0.57 of the HBM peak with no wasted traffic, i.e. it was latency /
+// issue bound):
 //   * grid = (tiles of one channel plane, channel, chain): the channel and the pixel index come from the block index,
 //     no 64-bit division per float4;
 //   * every load that does not depend on data is issued up front, mask tables FIRST: hardware returns loads in issue
@@ -241,7 +186,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_inpaint_px(
     const int32_t* __restrict__ prefix, int channels, int64_t hw4, int64_t m, float4* __restrict__ g_xt,
     float4* __restrict__ g_e, double* __restrict__ loss_ws, int fill_sigma) {
   const int chain = blockIdx.z, ch = blockIdx.y;
-  const Coef k = coef(at, at_next, chain);
+  const NhmcMix k = nhmc_mix_coef(at, at_next, chain);
   const int64_t plane = ((int64_t)chain * channels + ch) * hw4;            // float4 offset of this channel plane
   const int64_t eplane = (int64_t)chain * e_stride4 + (int64_t)ch * hw4;
   const float* yb = y + (int64_t)chain * m + ch;                            // y index = channels * rank(pixel) + channel
@@ -289,18 +234,15 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_inpaint_px(
     float* gee = reinterpret_cast<float*>(&oe);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float u = (xe[c] - ee[c] * k.c1) / k.c2;
-      const float pre = k.c3 * nhmc_clip1(u) + k.c4 * ee[c];    // decode before the final clip
+      float u, pre;                                              // pre: decode before the final clip
+      nhmc_mix_decode(k, xe[c], ee[c], u, pre);
       float gin = 0.0f;
       if ((kept[i] >> c) & 1u) {
         const float r = yv[i][c] - nhmc_clip1(pre);
         acc += (double)(r * r);
         gin = -(2.0f * r);
       }
-      gin = gin * nhmc_in1(pre);                                 // final clip mask
-      const float gu = ((gin * k.c3) * nhmc_in1(u)) / k.c2;
-      gx[c] = gu;
-      gee[c] = k.c4 * gin + (-gu) * k.c1;
+      nhmc_mix_vjp_masked(k, gin, nhmc_in1(pre), nhmc_in1(u), gx[c], gee[c]);
     }
     nhmc_stnt(&g_xt[plane + q], ox);
     nhmc_stnt(&g_e[eplane + q], oe);
@@ -324,7 +266,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_sr(
     const float* __restrict__ at_next, const float* __restrict__ y, float4* __restrict__ g_xt,
     float4* __restrict__ g_e, double* __restrict__ loss_ws, int dim, int channels) {
   const int chain = blockIdx.y;
-  const Coef k = coef(at, at_next, chain);
+  const NhmcMix k = nhmc_mix_coef(at, at_next, chain);
   const int w4 = dim / 4, yd = dim / R;
   const int64_t items = (int64_t)channels * yd * w4;
   const int64_t item = (int64_t)blockIdx.x * NHMC_BLOCK + threadIdx.x;
@@ -365,8 +307,8 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_sr(
       float cl[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const float u = (xe[c] - ee[c] * k.c1) / k.c2;
-        const float pre = k.c3 * nhmc_clip1(u) + k.c4 * ee[c];
+        float u, pre;
+        nhmc_mix_decode(k, xe[c], ee[c], u, pre);
         cl[c] = nhmc_clip1(pre);
         if (LANES == 1) bs[BPS == 1 ? 0 : c / R] += cl[c];
         const unsigned bit = 1u << (((rr & 7) << 2) + c);
@@ -394,11 +336,8 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_sr(
         const unsigned bit = 1u << (((rr & 7) << 2) + c);
         const float mp = ((rr < 8 ? in_pre : in_pre_hi) & bit) ? 1.0f : 0.0f;
         const float mu = ((rr < 8 ? in_u : in_u_hi) & bit) ? 1.0f : 0.0f;
-        float gin = (-(2.0f * resid[BPS == 1 ? 0 : c / R])) * inv;   // data-term gradient (k_sr, no clip mask there)
-        gin = gin * mp;                                               // final clip mask
-        const float gu = ((gin * k.c3) * mu) / k.c2;
-        gx[c] = gu;
-        gee[c] = k.c4 * gin + (-gu) * k.c1;
+        const float gin = (-(2.0f * resid[BPS == 1 ? 0 : c / R])) * inv;   // data-term gradient (k_sr, no clip mask there)
+        nhmc_mix_vjp_masked(k, gin, mp, mu, gx[c], gee[c]);
       }
       nhmc_stnt(&g_xt[xrow0 + (int64_t)rr * w4], ox);
       nhmc_stnt(&g_e[erow0 + (int64_t)rr * w4], oe);
@@ -436,7 +375,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_sr4(
   const int64_t row = (int64_t)(i * R + rr) * w4 + s;
   const int64_t xoff = ((int64_t)chain * channels + plane) * (int64_t)dim * w4 + row;
   const int64_t eoff = ((int64_t)chain * e_channels + plane) * (int64_t)dim * w4 + row;
-  const Coef k = coef(at, at_next, chain);
+  const NhmcMix k = nhmc_mix_coef(at, at_next, chain);
   float4 xv = make_float4(0.f, 0.f, 0.f, 0.f), ev = xv;
   if (live) { xv = nhmc_ldnt(&xt[xoff]); ev = nhmc_ldnt(&e[eoff]); }
   const float* xe = reinterpret_cast<const float*>(&xv);
@@ -446,8 +385,8 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_sr4(
   float* cle = reinterpret_cast<float*>(&cl);
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    const float u = (xe[c] - ee[c] * k.c1) / k.c2;
-    const float pre = k.c3 * nhmc_clip1(u) + k.c4 * ee[c];
+    float u, pre;
+    nhmc_mix_decode(k, xe[c], ee[c], u, pre);
     cle[c] = nhmc_clip1(pre);
     mp[c] = nhmc_in1(pre);
     mu[c] = nhmc_in1(u);
@@ -469,11 +408,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_sr4(
     float* gee = reinterpret_cast<float*>(&oe);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      float gin = (-(2.0f * resid)) * inv;
-      gin = gin * mp[c];
-      const float gu = ((gin * k.c3) * mu[c]) / k.c2;
-      gx[c] = gu;
-      gee[c] = k.c4 * gin + (-gu) * k.c1;
+      nhmc_mix_vjp_masked(k, (-(2.0f * resid)) * inv, mp[c], mu[c], gx[c], gee[c]);
     }
     nhmc_stnt(&g_xt[xoff], ox);
     nhmc_stnt(&g_e[eoff], oe);
@@ -493,7 +428,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_hdr(
     const float* __restrict__ at_next, const float4* __restrict__ y, float4* __restrict__ g_xt,
     float4* __restrict__ g_e, double* __restrict__ loss_ws, int64_t n4, int fill_sigma) {
   const int chain = blockIdx.y;
-  const Coef k = coef(at, at_next, chain);
+  const NhmcMix k = nhmc_mix_coef(at, at_next, chain);
   const int64_t base = (int64_t)chain * n4, ebase = (int64_t)chain * e_stride4;
   const int64_t t0 = (int64_t)blockIdx.x * (NHMC_BLOCK * NHMC_VEC_PER_THREAD) + threadIdx.x;
   double acc = 0.0;                                          // fp32 squares summed in fp64: independent of the tiling
@@ -515,29 +450,18 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_hdr(
     float* gee = reinterpret_cast<float*>(&oe);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float u = (xe[c] - ee[c] * k.c1) / k.c2;
-      const float pre = k.c3 * nhmc_clip1(u) + k.c4 * ee[c];    // decode before the final clip
+      float u, pre;                                              // pre: decode before the final clip
+      nhmc_mix_decode(k, xe[c], ee[c], u, pre);
       const float arg = 2.0f * nhmc_clip1(pre);                 // x / 0.5: exact in fp32
       const float r = ye[c] - nhmc_clip1(arg);
       acc += (double)(r * r);
-      float gin = ((-(2.0f * r)) * nhmc_in1(arg)) * 2.0f;       // clamp backward, then grad / 0.5
-      gin = gin * nhmc_in1(pre);                                 // final clip mask
-      const float gu = ((gin * k.c3) * nhmc_in1(u)) / k.c2;
-      gx[c] = gu;
-      gee[c] = k.c4 * gin + (-gu) * k.c1;
+      const float gin = ((-(2.0f * r)) * nhmc_in1(arg)) * 2.0f; // clamp backward, then grad / 0.5
+      nhmc_mix_vjp_masked(k, gin, nhmc_in1(pre), nhmc_in1(u), gx[c], gee[c]);
     }
     nhmc_stnt(&g_xt[base + q], ox);
     nhmc_stnt(&g_e[ebase + q], oe);
   }
-  const int64_t extra = fill_sigma ? e_stride4 - n4 : 0;
-  if (extra > 0) {
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int i = 0; i < NHMC_VEC_PER_THREAD; ++i) {
-      const int64_t q = t0 + (int64_t)i * NHMC_BLOCK;
-      if (q < extra) nhmc_stnt(&g_e[ebase + n4 + q], z);
-    }
-  }
+  nhmc_zero_sigma_half(g_e, ebase, n4, e_stride4, t0, fill_sigma);
   __shared__ double red[4];
   double v[1] = {acc};
   nhmc_block_sum<1>(v, red);
@@ -629,9 +553,9 @@ extern "C" int nhmc_ddim_mix_bwd_inpaint(const float* xt, const float* e, int e_
       !nhmc_aligned16(g_e))
     return NHMC_ERR_ALIGN;
   dim3 grid((unsigned)nhmc_leapfrog_tiles(n_elem), (unsigned)n_chains), block(NHMC_BLOCK);
-  NHMC_LAUNCH(k_mix_bwd_inpaint<false>, grid, block, 0, nhmc_s(stream), (const float4*)xt, (const float4*)e,
-              (int64_t)e_channels * hw / 4, at, at_next, y, (const int4*)slot, (const uint32_t*)nullptr,
-              (const int32_t*)nullptr, channels, hw, m, (float4*)g_xt, (float4*)g_e, loss_ws, n_elem / 4, fill_sigma);
+  NHMC_LAUNCH(k_mix_bwd_inpaint, grid, block, 0, nhmc_s(stream), (const float4*)xt, (const float4*)e,
+              (int64_t)e_channels * hw / 4, at, at_next, y, (const int4*)slot, m, (float4*)g_xt, (float4*)g_e, loss_ws,
+              n_elem / 4, fill_sigma);
   return nhmc_launch_status();
 }
 

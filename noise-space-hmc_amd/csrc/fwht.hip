@@ -29,22 +29,6 @@ enum { EPI_STORE = 0, EPI_SCATTER = 1, EPI_RESID = 2, EPI_GRAD = 3, EPI_VJP = 4,
 // EPI_VJP: the gradient goes straight through the VJP of the last DDIM step (k_mix_bwd with final_clip = 1); `xt` is then
 // the step's input and e / g_e are [chain][e_channels][d][d]
 struct VjpArgs { const float* e; float* g_e; const float* at; const float* at_next; int e_channels; };
-struct VjpCoef { float c1, c2, c3, c4; };
-__device__ __forceinline__ VjpCoef vjp_coef(const VjpArgs& vj, int64_t chain) {
-  const float a = vj.at[chain], an = vj.at_next[chain];
-  VjpCoef k;
-  k.c1 = sqrtf(1.0f - a); k.c2 = sqrtf(a); k.c3 = sqrtf(an); k.c4 = sqrtf(1.0f - an);
-  return k;
-}
-// one element: data-term value v (already scaled) -> (g_xt, g_e), same op order as k_mix_bwd<false,false>
-__device__ __forceinline__ void vjp_elem(const VjpCoef& k, float v, float x, float ee, float& gx, float& ge) {
-  const float u = (x - ee * k.c1) / k.c2;
-  float gin = -(2.0f * v);
-  gin = gin * nhmc_in1(k.c3 * nhmc_clip1(u) + k.c4 * ee);
-  const float gu = ((gin * k.c3) * nhmc_in1(u)) / k.c2;
-  gx = gu;
-  ge = k.c4 * gin + (-gu) * k.c1;
-}
 
 template <int V> struct Vec;
 template <> struct Vec<1> { typedef float type; };
@@ -154,14 +138,14 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_fwht_rows(const float* __restric
         const int64_t plane = row / d;
         const int c = (int)(plane % channels);
         const int64_t chain = plane / channels;
-        const VjpCoef kc = vjp_coef(vj, chain);
+        const NhmcMix kc = nhmc_mix_coef(vj.at, vj.at_next, chain);
         const int64_t eoff = (chain * vj.e_channels + c) * (int64_t)d * d + (row % d) * d + j0;
         const typename Vec<V>::type ew = *reinterpret_cast<const typename Vec<V>::type*>(&vj.e[eoff]);
         const float* ee = reinterpret_cast<const float*>(&ew);
         typename Vec<V>::type gw;
         float* ge = reinterpret_cast<float*>(&gw);
 #pragma unroll
-        for (int e = 0; e < V; ++e) vjp_elem(kc, v[e] * scale, xe[e], ee[e], we[e], ge[e]);
+        for (int e = 0; e < V; ++e) nhmc_mix_vjp(kc, -(2.0f * (v[e] * scale)), xe[e], ee[e], we[e], ge[e]);
         *reinterpret_cast<typename Vec<V>::type*>(&vj.g_e[eoff]) = gw;
       }
     }
@@ -219,10 +203,10 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_fwht_cols(const float* __restric
       if (ys == ys) { r = ys - v; acc += r * r; }
       out[off] = r;                                                 // zero-filled spectrum of the residual
     } else if (EPI == EPI_VJP) {
-      const VjpCoef k = vjp_coef(vj, chain);
+      const NhmcMix k = nhmc_mix_coef(vj.at, vj.at_next, chain);
       const int64_t eoff = (chain * vj.e_channels + c) * (int64_t)d * d + q;
       float gx, ge;
-      vjp_elem(k, v, xt[off], vj.e[eoff], gx, ge);
+      nhmc_mix_vjp(k, -(2.0f * v), xt[off], vj.e[eoff], gx, ge);
       out[off] = gx;
       vj.g_e[eoff] = ge;
     } else {
@@ -351,7 +335,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_fwht_cols256(const float* __rest
       }
       *reinterpret_cast<nhmc_v4f*>(&out[off]) = r;
     } else if (EPI == EPI_VJP) {
-      const VjpCoef kc = vjp_coef(vj, chain);
+      const NhmcMix kc = nhmc_mix_coef(vj.at, vj.at_next, chain);
       const int64_t eoff = (chain * vj.e_channels + c) * (int64_t)D * D + q;
       const nhmc_v4f xv = *reinterpret_cast<const nhmc_v4f*>(&xt[off]);
       const nhmc_v4f ev = *reinterpret_cast<const nhmc_v4f*>(&vj.e[eoff]);
@@ -359,7 +343,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_fwht_cols256(const float* __rest
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float a, b;
-        vjp_elem(kc, val[e], xv[e], ev[e], a, b);
+        nhmc_mix_vjp(kc, -(2.0f * val[e]), xv[e], ev[e], a, b);
         gx[e] = a; ge[e] = b;
       }
       *reinterpret_cast<nhmc_v4f*>(&out[off]) = gx;

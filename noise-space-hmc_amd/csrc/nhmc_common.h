@@ -91,3 +91,66 @@ __device__ __forceinline__ float nhmc_in1(float v) { return (v >= -1.0f && v <= 
 // Square roots: plain sqrtf.  hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt makes sqrtf and the fp32 division
 // IEEE correctly rounded on gfx950 (no fast-math flag is set in build.py); tests/test_hygiene_gpu.py sweeps all 1001
 // alpha-bar table entries through the kernels against numpy's correctly rounded root.
+
+// ---- the last DDIM step and its VJP: the one definition every fused "data term + last-step VJP" kernel calls ----------
+//   u   = (x - e*c1) / c2         x0 = clip(u)
+//   pre = c3*x0 + c4*e            xt_next = clip(pre)  (final_clip)
+// The per-chain coefficients are the fp32 roots the reference takes on its [n,1,1,1] tensors.
+struct NhmcMix { float c1, c2, c3, c4; };
+
+__device__ __forceinline__ NhmcMix nhmc_mix_coef(const float* at, const float* at_next, int64_t chain) {
+  const float a = at[chain], an = at_next[chain];
+  NhmcMix k;
+  k.c1 = sqrtf(1.0f - a);    // (1 - at).sqrt()
+  k.c2 = sqrtf(a);           // at.sqrt()
+  k.c3 = sqrtf(an);          // at_next.sqrt()
+  k.c4 = sqrtf(1.0f - an);   // (1 - at_next).sqrt()
+  return k;
+}
+
+// decode: (x, e) -> u (x0 before its clip) and pre (the step's output before the final clip)
+__device__ __forceinline__ float nhmc_mix_u(const NhmcMix& k, float x, float e) { return (x - e * k.c1) / k.c2; }
+__device__ __forceinline__ float nhmc_mix_pre(const NhmcMix& k, float u, float e) { return k.c3 * nhmc_clip1(u) + k.c4 * e; }
+__device__ __forceinline__ void nhmc_mix_decode(const NhmcMix& k, float x, float e, float& u, float& pre) {
+  u = nhmc_mix_u(k, x, e);
+  pre = nhmc_mix_pre(k, u, e);
+}
+
+// The VJP's body, in autograd's rounding order: `gin` is the gradient w.r.t. the step's output (after the final clip's
+// mask), `g0` the gradient reaching x0 -- gin*c3 through map_back, except in k_mix_bwd's split form, which is handed it --
+// and `mu` = 1[-1 <= u <= 1] the x0 clip's mask.  Every product and the division are rounded separately
+// (-ffp-contract=off): g_xt = (g0*mu)/c2, g_e = c4*gin + (-g_xt)*c1.
+__device__ __forceinline__ void nhmc_mix_vjp_body(const NhmcMix& k, float gin, float g0, float mu, float& g_xt, float& g_e) {
+  const float gu = (g0 * mu) / k.c2;
+  g_xt = gu;
+  g_e = k.c4 * gin + (-gu) * k.c1;
+}
+
+// Entry for kernels that keep u / pre, or only their mask bits mp = 1[-1 <= pre <= 1] and mu, between two passes.
+// `gin`: the data term's gradient w.r.t. the clipped decode.
+__device__ __forceinline__ void nhmc_mix_vjp_masked(const NhmcMix& k, float gin, float mp, float mu, float& g_xt, float& g_e) {
+  gin = gin * mp;                                            // final clip mask
+  nhmc_mix_vjp_body(k, gin, gin * k.c3, mu, g_xt, g_e);
+}
+
+// Entry for epilogues that recompute everything from (x, e).
+__device__ __forceinline__ void nhmc_mix_vjp(const NhmcMix& k, float gin, float x, float e, float& g_xt, float& g_e) {
+  float u, pre;
+  nhmc_mix_decode(k, x, e, u, pre);
+  nhmc_mix_vjp_masked(k, gin, nhmc_in1(pre), nhmc_in1(u), g_xt, g_e);
+}
+
+// Learned-sigma channels of the score gradient are zero (the forward slices them away): the tail of the streaming kernels
+// whose tile index t0 runs over [0, n4) float4 per chain.  A caller that keeps a persistent, pre-zeroed g_e buffer passes
+// fill = 0 and saves this T of writes.
+__device__ __forceinline__ void nhmc_zero_sigma_half(float4* g_e, int64_t ebase, int64_t n4, int64_t e_stride4, int64_t t0, bool fill) {
+  const int64_t extra = fill ? e_stride4 - n4 : 0;
+  if (extra > 0) {
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int i = 0; i < NHMC_VEC_PER_THREAD; ++i) {
+      const int64_t q = t0 + (int64_t)i * NHMC_BLOCK;
+      if (q < extra) nhmc_stnt(&g_e[ebase + n4 + q], z);
+    }
+  }
+}

@@ -123,14 +123,13 @@ __global__ __launch_bounds__(64 * NW * NW, (NW == 2 && EPI != EPI_NONE) ? 4 : 1)
   // EPI_VJP: aux = the DDIM step's input xt; e / g_e are [chain][e_channels][R][C]
   const float* __restrict__ e_img = nullptr;
   float* __restrict__ ge_img = nullptr;
-  float c1 = 0.f, c2 = 1.f, c3 = 0.f, c4 = 0.f;
+  NhmcMix kc = {0.f, 1.f, 0.f, 0.f};
   if (EPI == EPI_VJP) {
     const int chain = img / channels;
     const int64_t eoff = ((int64_t)chain * vj.e_channels + c) * R * C;
     e_img = vj.e + eoff;
     ge_img = vj.g_e + eoff;
-    const float a = vj.at[chain], an = vj.at_next[chain];
-    c1 = sqrtf(1.0f - a); c2 = sqrtf(a); c3 = sqrtf(an); c4 = sqrtf(1.0f - an);
+    kc = nhmc_mix_coef(vj.at, vj.at_next, chain);
   }
   constexpr int SLAB_V = ((T / NW) * T / 4) / NT;       // float4 per thread per slab
   for (int h = 0; h < NW; ++h) {
@@ -184,19 +183,15 @@ __global__ __launch_bounds__(64 * NW * NW, (NW == 2 && EPI != EPI_NONE) ? 4 : 1)
           q.x = q.x * nhmc_in1(xv.x); q.y = q.y * nhmc_in1(xv.y); q.z = q.z * nhmc_in1(xv.z); q.w = q.w * nhmc_in1(xv.w);
         }
       }
-      if (EPI == EPI_VJP) {                               // same op order as k_mix_bwd<false,false>, final_clip = 1
+      if (EPI == EPI_VJP) {
         const nhmc_v4f xv = *reinterpret_cast<const nhmc_v4f*>(&aux_img[off]);
         const nhmc_v4f ev = *reinterpret_cast<const nhmc_v4f*>(&e_img[off]);
         nhmc_v4f ge;
 #pragma unroll
         for (int k4 = 0; k4 < 4; ++k4) {
-          const float ee = ev[k4];
-          const float u = (xv[k4] - ee * c1) / c2;
-          float gin = -(2.0f * q[k4]);
-          gin = gin * nhmc_in1(c3 * nhmc_clip1(u) + c4 * ee);
-          const float gu = ((gin * c3) * nhmc_in1(u)) / c2;
-          ge[k4] = c4 * gin + (-gu) * c1;
-          q[k4] = gu;
+          float gx, gee;
+          nhmc_mix_vjp(kc, -(2.0f * q[k4]), xv[k4], ev[k4], gx, gee);
+          ge[k4] = gee; q[k4] = gx;
         }
         *reinterpret_cast<nhmc_v4f*>(&ge_img[off]) = ge;
       }
@@ -427,14 +422,13 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void k_pair256(
   const float* __restrict__ aux_img = aux ? aux + (int64_t)img * D * D : nullptr;
   const float* __restrict__ e_img = nullptr;
   float* __restrict__ ge_img = nullptr;
-  float c1 = 0.f, c2 = 1.f, c3 = 0.f, c4 = 0.f;
+  NhmcMix kc = {0.f, 1.f, 0.f, 0.f};
   if (EPI == EPI_VJP) {
     const int chain = img / channels;
     const int64_t eoff = ((int64_t)chain * vj.e_channels + c) * D * D;
     e_img = vj.e + eoff;
     ge_img = vj.g_e + eoff;
-    const float a = vj.at[chain], an = vj.at_next[chain];
-    c1 = sqrtf(1.0f - a); c2 = sqrtf(a); c3 = sqrtf(an); c4 = sqrtf(1.0f - an);
+    kc = nhmc_mix_coef(vj.at, vj.at_next, chain);
   }
   // the epilogue's global operands (multiplier map / observation / clip-mask source / the VJP's xt and e) are requested HERE,
   // before the barrier that ends the staging: the accumulators and the operand ring are dead, so their registers hold the
@@ -491,19 +485,15 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void k_pair256(
         o.x = o.x * nhmc_in1(xv.x); o.y = o.y * nhmc_in1(xv.y); o.z = o.z * nhmc_in1(xv.z); o.w = o.w * nhmc_in1(xv.w);
       }
     }
-    if (EPI == EPI_VJP) {                                   // same op order as k_mix_bwd<false,false>, final_clip = 1
+    if (EPI == EPI_VJP) {
       const nhmc_v4f xv = pre_aux[v];
       const nhmc_v4f ev = pre_e[v];
       nhmc_v4f ge;
 #pragma unroll
       for (int k4 = 0; k4 < 4; ++k4) {
-        const float ee = ev[k4];
-        const float u = (xv[k4] - ee * c1) / c2;
-        float gin = -(2.0f * o[k4]);
-        gin = gin * nhmc_in1(c3 * nhmc_clip1(u) + c4 * ee);
-        const float gu = ((gin * c3) * nhmc_in1(u)) / c2;
-        ge[k4] = c4 * gin + (-gu) * c1;
-        o[k4] = gu;
+        float gx, gee;
+        nhmc_mix_vjp(kc, -(2.0f * o[k4]), xv[k4], ev[k4], gx, gee);
+        ge[k4] = gee; o[k4] = gx;
       }
       *reinterpret_cast<nhmc_v4f*>(&ge_img[off]) = ge;
     }

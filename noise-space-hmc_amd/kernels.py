@@ -183,6 +183,20 @@ def _alpha(a, B, device):
     return a.to(device=device, dtype=torch.float32).contiguous()
 
 
+def _last_vjp_io(xt, e, at, at_next, g_e_out, fills_sigma):
+    """What every fused "data term + last DDIM-step VJP" wrapper starts with -> (B, C, hw, e_channels, at, at_next, g_xt, g_e).
+    fills_sigma: the kernel zero-fills the learned-sigma half of a fresh g_e itself (its fill_sigma argument); the others
+    write channels [0, C) only and get a zeroed one.  A caller's g_e_out is checked before anything is allocated or launched.
+    The callers hold the alpha-bar arrays until after their launch call (see ddim_map_back)."""
+    B, Cc, hw, ec = _mix_shapes(xt, e)
+    if g_e_out is not None and g_e_out.shape != e.shape:
+        raise _lib.NhmcError(f'g_e_out must have the shape of the score output {tuple(e.shape)}, got {tuple(g_e_out.shape)}')
+    at, at_next = _alpha(at, B, xt.device), _alpha(at_next, B, xt.device)
+    g_xt = torch.empty_like(xt)
+    g_e = g_e_out if g_e_out is not None else (torch.empty_like(e) if fills_sigma else torch.zeros_like(e))
+    return B, Cc, hw, ec, at, at_next, g_xt, g_e
+
+
 def ddim_mix_fwd(xt, e, at, at_next, final_clip=False, want=('xt_next',), out=None):
     """Returns a dict with the requested outputs among 'xt_next', 'x0_t', 'add_up'.  out: tensor to write xt_next into."""
     lib = _lib.load()
@@ -229,11 +243,8 @@ def ddim_mix_bwd(gout, xt, e, at, at_next, final_clip=False, gout2=None, g_x0=No
 
 def ddim_mix_bwd_inpaint(xt, e, at, at_next, y, slot, g_e_out=None, loss_out=None):
     """Last-step VJP fused with the inpainting data term -> (loss [B] float64, g_xt, g_e)."""
+    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
     lib = _lib.load()
-    B, Cc, hw, ec = _mix_shapes(xt, e)
-    at, at_next = _alpha(at, B, xt.device), _alpha(at_next, B, xt.device)
-    g_xt = torch.empty_like(xt)
-    g_e = g_e_out if g_e_out is not None else torch.empty_like(e)
     tiles = leapfrog_tiles(Cc * hw)
     ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
     rc = lib.nhmc_ddim_mix_bwd_inpaint(_p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
@@ -245,11 +256,8 @@ def ddim_mix_bwd_inpaint(xt, e, at, at_next, y, slot, g_e_out=None, loss_out=Non
 
 def ddim_mix_bwd_inpaint_px(xt, e, at, at_next, y, mask_words, prefix, g_e_out=None, loss_out=None):
     """Whole-pixel-mask form of ddim_mix_bwd_inpaint: bit mask + prefix counts instead of the dense slot map."""
+    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
     lib = _lib.load()
-    B, Cc, hw, ec = _mix_shapes(xt, e)
-    at, at_next = _alpha(at, B, xt.device), _alpha(at_next, B, xt.device)
-    g_xt = torch.empty_like(xt)
-    g_e = g_e_out if g_e_out is not None else torch.empty_like(e)
     tiles = lib.nhmc_inpaint_px_tiles(Cc, hw)
     ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
     rc = lib.nhmc_ddim_mix_bwd_inpaint_px(_p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
@@ -262,14 +270,11 @@ def ddim_mix_bwd_inpaint_px(xt, e, at, at_next, y, mask_words, prefix, g_e_out=N
 
 def ddim_mix_bwd_sr(xt, e, at, at_next, y, ratio, g_e_out=None, loss_out=None):
     """Last-step VJP fused with the super-resolution data term -> (loss [B] float64, g_xt, g_e)."""
-    lib = _lib.load()
-    B, Cc, hw, ec = _mix_shapes(xt, e)
     dim = xt.shape[2]
     if xt.shape[3] != dim:
         raise _lib.NhmcError('square images only')
-    at, at_next = _alpha(at, B, xt.device), _alpha(at_next, B, xt.device)
-    g_xt = torch.empty_like(xt)
-    g_e = g_e_out if g_e_out is not None else torch.zeros_like(e)          # the kernel writes channels [0, C) only
+    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
+    lib = _lib.load()
     tiles = lib.nhmc_sr_vjp_tiles(Cc, dim, ratio)
     ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
     rc = lib.nhmc_ddim_mix_bwd_sr(_p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
@@ -388,13 +393,10 @@ def data_color(xt, y, w, apply_clip=True, loss_out=None):
 
 def ddim_mix_bwd_color(xt, e, at, at_next, y, w, g_e_out=None, loss_out=None):
     """Last-step VJP fused with the colorization data term -> (loss [B] float64, g_xt, g_e)."""
+    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
     lib = _lib.load()
-    B, Cc, hw, ec = _mix_shapes(xt, e)
-    at, at_next = _alpha(at, B, xt.device), _alpha(at_next, B, xt.device)
     tiles = lib.nhmc_color_tiles(hw)
     ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    g_xt = torch.empty_like(xt)
-    g_e = g_e_out if g_e_out is not None else torch.zeros_like(e)
     wp, keep = _host_w(w, Cc)
     rc = lib.nhmc_ddim_mix_bwd_color(_p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
                                      _p(y, torch.float32, 'y'), wp, _p(g_xt), _p(g_e), _p(ws), B, Cc, hw, _stream())
@@ -463,17 +465,14 @@ def data_cs(xt, y_spec, apply_clip=True, loss_out=None):
 def data_cs_vjp(xt_next, y_spec, xt, e, at, at_next, g_e_out=None, loss_out=None):
     """Walsh-Hadamard CS data term on the clipped decode + VJP of the last DDIM step in the last row pass
     -> (loss [B] float64, g_xt, g_e).  y_spec: as in data_cs."""
+    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
     lib = _lib.load()
-    B, Cc, hw, ec = _mix_shapes(xt, e)
     dim = xt.shape[2]
     if y_spec.numel() != xt.numel():
         raise _lib.NhmcError('data_cs_vjp: y_spec must have one entry per image element (spectrum layout)')
-    at, at_next = _alpha(at, B, xt.device), _alpha(at_next, B, xt.device)
     tiles = lib.nhmc_cs_tiles(Cc, dim)
     ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
     tmp = _cs_tmp(xt, dim)
-    g_xt = torch.empty_like(xt)
-    g_e = g_e_out if g_e_out is not None else torch.zeros_like(e)
     rc = lib.nhmc_data_cs_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y_spec, torch.float32, 'y_spec'),
                               _p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next), _p(g_xt),
                               _p(g_e), _p(ws), _p(tmp), B, Cc, dim, _stream())
@@ -538,16 +537,13 @@ def data_srconv(xt, y, factors, apply_clip=True, loss_out=None):
 def data_srconv_vjp(xt_next, y, factors, xt, e, at, at_next, g_e_out=None, loss_out=None):
     """Bicubic / strided-convolution data term on the clipped decode + VJP of the last DDIM step in the last product's
     epilogue -> (loss [B] float64, g_xt, g_e)."""
+    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
     lib = _lib.load()
-    B, Cc, hw, ec = _mix_shapes(xt, e)
     dim = xt.shape[2]
     sd = _srconv_factors(factors, dim)
-    at, at_next = _alpha(at, B, xt.device), _alpha(at_next, B, xt.device)
     tiles = lib.nhmc_srconv_tiles(Cc, sd)
     ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
     tmp = torch.empty(B * Cc * (dim * sd + 3 * sd * sd), dtype=torch.float32, device=xt.device)
-    g_xt = torch.empty_like(xt)
-    g_e = g_e_out if g_e_out is not None else torch.zeros_like(e)
     rc = lib.nhmc_data_srconv_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y, torch.float32, 'y'),
                                   *[_p(t, torch.float32) for t in factors], _p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec,
                                   _p(at), _p(at_next), _p(g_xt), _p(g_e), _p(ws), _p(tmp), B, Cc, dim, sd, _stream())
@@ -593,15 +589,12 @@ def data_spectral(xt, y, factors, Dmap, apply_clip=True, loss_out=None, projecte
 def data_spectral_vjp(xt_next, y, factors, Dmap, xt, e, at, at_next, g_e_out=None, loss_out=None, projected=False, DmapT=None):
     """Spectral data term on the clipped decode `xt_next` + VJP of the last DDIM step (inputs xt, e) in the last
     product's epilogue -> (loss [B] float64, g_xt, g_e).  y / DmapT / projected: as in data_spectral."""
+    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
     lib = _lib.load()
-    B, Cc, hw, ec = _mix_shapes(xt, e)
     dim = xt.shape[2]
-    at, at_next = _alpha(at, B, xt.device), _alpha(at_next, B, xt.device)
     tiles = lib.nhmc_spectral_tiles(Cc, dim)
     ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
     tmp = torch.empty((1 if projected else 2,) + tuple(xt.shape), dtype=torch.float32, device=xt.device)
-    g_xt = torch.empty_like(xt)
-    g_e = g_e_out if g_e_out is not None else torch.zeros_like(e)          # channels [0, C) are written
     if projected:
         rc = lib.nhmc_data_spectral_proj_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y, torch.float32, 'y'),
                                              _p(factors, torch.float32, 'factors'), _p(Dmap, torch.float32),
@@ -648,14 +641,9 @@ def data_hdr(xt, y, apply_clip=True, loss_out=None):
 
 def mix_bwd_hdr(xt, e, at, at_next, y, g_e_out=None, loss_out=None):
     """Last-step VJP fused with the HDR data term -> (loss [B] float64, g_xt, g_e)."""
+    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
     lib = _lib.load()
-    B, Cc, hw, ec = _mix_shapes(xt, e)
     _dense_y(y, xt)
-    at, at_next = _alpha(at, B, xt.device), _alpha(at_next, B, xt.device)
-    g_xt = torch.empty_like(xt)
-    g_e = g_e_out if g_e_out is not None else torch.empty_like(e)
-    if g_e.shape != e.shape:
-        raise _lib.NhmcError('g_e_out must have the shape of the score output')
     tiles = leapfrog_tiles(Cc * hw)
     ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
     rc = lib.nhmc_mix_bwd_hdr(_p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
@@ -742,20 +730,15 @@ def data_phase(xt, y, fac, pad, apply_clip=True, loss_out=None):
 def data_phase_vjp(xt_next, y, fac, pad, xt, e, at, at_next, g_e_out=None, loss_out=None):
     """Phase-retrieval data term on the clipped decode `xt_next` + VJP of the last DDIM step (inputs xt, e) in the last
     product's epilogue -> (loss [B] float64, g_xt, g_e)."""
+    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
     lib = _lib.load()
-    B, Cc, hw, ec = _mix_shapes(xt, e)
     _, _, dim, n = _phase_shapes(xt, fac, pad)
     _phase_y(y, B, Cc, n)
     if xt_next.shape != xt.shape:
         raise _lib.NhmcError('xt_next must have the shape of xt')
-    at, at_next = _alpha(at, B, xt.device), _alpha(at_next, B, xt.device)
     tiles = lib.nhmc_phase_tiles(Cc, dim, pad)
     ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
     tmp = _phase_tmp(B, Cc, dim, pad, xt.device)
-    g_xt = torch.empty_like(xt)
-    g_e = g_e_out if g_e_out is not None else torch.zeros_like(e)          # channels [0, C) are written
-    if g_e.shape != e.shape:
-        raise _lib.NhmcError('g_e_out must have the shape of the score output')
     rc = lib.nhmc_data_phase_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y, torch.float32, 'y'), _p(fac, torch.float32, 'fac'),
                                  _p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next), _p(g_xt),
                                  _p(g_e, torch.float32, 'g_e'), _p(ws), _p(tmp), B, Cc, dim, pad, _stream())

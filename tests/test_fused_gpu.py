@@ -265,3 +265,67 @@ def test_mid_steps_skip_the_loss_summation_and_change_nothing_else(tiny_score):
     assert torch.equal(xa, xb) and torch.equal(pa, pb)
     _, loss_again = eng.step(K.LF_MID, xa, xa, pa, y, eps, sig, 1.0, ws)
     assert torch.equal(loss_again, loss_full) and stale is not None           # untouched by a MID step: still the last summed loss
+
+
+# ---- every fused wrapper refuses a wrongly shaped g_e_out before it allocates or launches anything -----------------
+def _wrapper_cases():
+    """name -> (degradation or operator factory, image size, call(K, op, t, g_e_out)); t: the shared operands of one case.
+    16 x 16 wherever the entry point takes it; the MFMA forms (spectral, strided convolution, phase retrieval) start at 32."""
+    from nhmc import operators
+
+    def srconv32(dev):          # img_dim and img_dim / stride must be multiples of 32: stride 1 is the 32 x 32 instance
+        return operators.SRConv(operators.bicubic_taps(2), 3, 32, dev, stride=1)
+
+    return {
+        'ddim_mix_bwd_inpaint': ('inpaint_random', 16, lambda K, op, t, b: K.ddim_mix_bwd_inpaint(
+            t.xt, t.e, t.at, t.atn, t.y, op.slot, g_e_out=b)),
+        'ddim_mix_bwd_inpaint_px': ('inpaint_random', 16, lambda K, op, t, b: K.ddim_mix_bwd_inpaint_px(
+            t.xt, t.e, t.at, t.atn, t.y, op.mask_words, op.mask_prefix, g_e_out=b)),
+        'ddim_mix_bwd_sr': ('sr2', 16, lambda K, op, t, b: K.ddim_mix_bwd_sr(t.xt, t.e, t.at, t.atn, t.y, op.ratio, g_e_out=b)),
+        'ddim_mix_bwd_color': ('color', 16, lambda K, op, t, b: K.ddim_mix_bwd_color(
+            t.xt, t.e, t.at, t.atn, t.y, op.w, g_e_out=b)),
+        'data_cs_vjp': ('cs2', 16, lambda K, op, t, b: K.data_cs_vjp(t.cur, t.obs, t.xt, t.e, t.at, t.atn, g_e_out=b)),
+        'data_srconv_vjp': (srconv32, 32, lambda K, op, t, b: K.data_srconv_vjp(
+            t.cur, t.obs, op.factors, t.xt, t.e, t.at, t.atn, g_e_out=b)),
+        'data_spectral_vjp': ('deblur_aniso', 32, lambda K, op, t, b: K.data_spectral_vjp(
+            t.cur, t.obs, op.factors, op.Dmap, t.xt, t.e, t.at, t.atn, g_e_out=b, projected=op.projected, DmapT=op.DmapT)),
+        'mix_bwd_hdr': ('hdr', 16, lambda K, op, t, b: K.mix_bwd_hdr(t.xt, t.e, t.at, t.atn, t.y, g_e_out=b)),
+        'data_phase_vjp': ('phase_retrieval', 32, lambda K, op, t, b: K.data_phase_vjp(
+            t.cur, t.obs, op.factors, op.pad, t.xt, t.e, t.at, t.atn, g_e_out=b)),
+    }
+
+
+@pytest.mark.parametrize('name', ['ddim_mix_bwd_inpaint', 'ddim_mix_bwd_inpaint_px', 'ddim_mix_bwd_sr', 'ddim_mix_bwd_color',
+                                  'data_cs_vjp', 'data_srconv_vjp', 'data_spectral_vjp', 'mix_bwd_hdr', 'data_phase_vjp'])
+def test_fused_wrappers_refuse_a_wrongly_shaped_g_e_out(name, monkeypatch):
+    """B = 1, e with 6 channels, g_e_out [1, 3, d, d]: NhmcError, the buffer keeps its sentinel, and neither the library
+    nor the allocator is reached (the kernels write [B][e_channels][H][W] into whatever they are handed)."""
+    import types
+    import nhmc.kernels as K
+    from nhmc import _lib, operators
+    deg, d, call = _wrapper_cases()[name]
+    g_ = torch.Generator().manual_seed(23)
+    dev = torch.device('cuda')
+    op = deg(dev) if callable(deg) else operators.build_operator(deg, 3, d, dev, generator=g_)
+    t = types.SimpleNamespace(xt=(torch.randn(1, 3, d, d, generator=g_) * 0.5).cuda(), e=torch.randn(1, 6, d, d, generator=g_).cuda())
+    t.y = torch.randn(1, op.M, generator=g_).cuda()
+    b = osched.betas_fp32()
+    t.at, t.atn = osched.alpha_bar(b, torch.full((1,), 250)).cuda(), osched.alpha_bar(b, torch.full((1,), -1)).cuda()
+    t.cur = K.ddim_mix_fwd(t.xt, t.e, t.at, t.atn, final_clip=True)['xt_next']
+    t.obs = {'data_cs_vjp': lambda: op.spectrum_observation(t.y), 'data_srconv_vjp': lambda: op._obs_t(t.y),
+             'data_spectral_vjp': lambda: op._obs(t.y, t.xt.shape), 'data_phase_vjp': lambda: op._obs(t.y)}.get(name, lambda: None)()
+    good = torch.full((1, 6, d, d), 7.0, device='cuda')
+    _, _, g_e = call(K, op, t, good)                               # the case itself is a valid call ...
+    assert g_e is good and not bool((good[:, :3] == 7.0).all())
+    bad = torch.full((1, 3, d, d), 7.0, device='cuda')             # ... and only the buffer's shape is refused
+    torch.cuda.synchronize()
+
+    class NoLibrary:
+        def __getattr__(self, entry):
+            raise AssertionError(f'{entry} reached on the refusing path')
+    monkeypatch.setattr(_lib, 'load', lambda: NoLibrary())
+    allocations = torch.cuda.memory_stats()['allocation.all.allocated']
+    with pytest.raises(_lib.NhmcError, match='g_e_out'):
+        call(K, op, t, bad)
+    assert torch.cuda.memory_stats()['allocation.all.allocated'] == allocations      # no zeros_like, no workspace
+    assert bool((bad == 7.0).all())
