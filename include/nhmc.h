@@ -576,6 +576,58 @@ int nhmc_psnr(const float* xt, const float* x_orig, float* psnr, double* ws,
               int n_chains, int64_t n_elem, nhmc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Report stage: the metrics `sample_image` takes of the collected samples      main_sampling.py:488-561
+ *
+ *   samples : fp32 [n_chains][n_samples][C][H][W] in [-1,1], as the sampler returns them; x_orig : fp32 [n_chains][C][H][W].
+ *   Sample j of chain b (row b * n_samples + j) is compared against x_orig[b]; x_orig is indexed, never expanded.
+ *   Both images pass through the reference's inverse_data_transform, clamp((v+1)/2, 0, 1) in fp32, inside the kernels.
+ *   n_elem = C*H*W with n_elem % 4 == 0, 16-byte aligned image bases, n_chains * n_samples <= 65535, C <= 65535.
+ *   Reductions: per-tile fp64 partials in the caller's workspace plus a fixed-order second pass; equal inputs, equal bits.
+ *   Validation, before any launch: null pointer / non-positive size -> ARG, alignment or n_elem % 4 -> ALIGN, then SHAPE.
+ *
+ * nhmc_psnr_samples: PSNR of every sample against its chain's original (:517-519), one launch pair for the whole block;
+ *   the arithmetic is nhmc_psnr's (same kernels), so psnr[b * n_samples + j] has the bits nhmc_psnr gives for that pair.
+ *   ws: double[n_chains * n_samples][nhmc_data_tiles(n_elem)].
+ * nhmc_sample_range: range[i] = max - min of transformed sample i over all channels, the fp32 difference the reference
+ *   passes as `data_range` (:520: the SAMPLE's range, not the original's).
+ *   ws: double[n_chains * n_samples][nhmc_data_tiles(n_elem)][2]; nhmc_ssim_ws_bytes covers it.
+ * nhmc_ssim: skimage.metrics.structural_similarity(sample, orig, data_range=range[i], channel_axis=0) at its defaults
+ *   (:520): 7x7 uniform window, NP = 49, sample covariance (cov_norm = 49/48), K1 = 0.01, K2 = 0.03,
+ *   C1 = (K1 R)^2, C2 = (K2 R)^2; per channel plane, with ux, uy, uxx, uyy, uxy the window means of x, y, xx, yy, xy:
+ *     vx = cov_norm (uxx - ux^2), vy = cov_norm (uyy - uy^2), vxy = cov_norm (uxy - ux uy),
+ *     S = ((2 ux uy + C1)(2 vxy + C2)) / ((ux^2 + uy^2 + C1)(vx + vy + C2)),
+ *   the plane's value is the mean of S over the plane cropped by 3 pixels on every side (only windows wholly inside the
+ *   image count, so no border mode enters) and a sample's SSIM is the mean of its planes' values.  fp64 from the products
+ *   on (fp32 inputs: the products are exact); ssim is double[n_chains * n_samples].  range[i] = 0 is not special-cased.
+ *   One block per (tile, channel, sample): nhmc_ssim_tiles(h, w) tiles of 16 x 32 window positions per plane.
+ *   H < 7 or W < 7: NHMC_ERR_SHAPE (nhmc_ssim_tiles returns 0).
+ *   ws: double[n_chains * n_samples][C][nhmc_ssim_tiles(h, w)]; nhmc_ssim_ws_bytes(n, c, h, w) is the larger of this and
+ *   nhmc_sample_range's need for n = n_chains * n_samples samples, so one workspace serves both calls in turn.
+ * nhmc_sample_moments: per chain, over its n_samples >= 2 samples (:494 guards with len(xt) > 1; fewer: NHMC_ERR_SHAPE):
+ *     mean    [n_chains][C][H][W]  mean of the RAW samples (the posterior-mean image), fp64 sum rounded once to fp32;
+ *     std_map [n_chains][H][W]     x.std(dim=0).mean(dim=0) of the TRANSFORMED samples (:495-496): per pixel and channel
+ *                                  the two-pass unbiased std in fp64 (mean, then squared deviations), averaged over the
+ *                                  channels, rounded once to fp32;
+ *     minmax  [n_chains][2]        the map's minimum and maximum (:497), fp32.
+ *   ws: double[n_chains][nhmc_moments_tiles(h * w)][2].
+ * nhmc_std_map_normalise: out = (std_map - min) / (max - min) in fp32 (:497), the picture saved as std_dev_map_{idx}.png.
+ * Not served: LPIPS (:521) needs the lpips package and its VGG weights.
+ * ---------------------------------------------------------------------------------- */
+int nhmc_psnr_samples(const float* samples, const float* x_orig, float* psnr, double* ws, int n_chains, int n_samples,
+                      int64_t n_elem, nhmc_stream_t stream);
+int nhmc_ssim_tiles(int h, int w);
+size_t nhmc_ssim_ws_bytes(int n_total_samples, int c, int h, int w);
+int nhmc_sample_range(const float* samples, float* range, double* ws, int n_total_samples, int64_t n_elem,
+                      nhmc_stream_t stream);
+int nhmc_ssim(const float* samples, const float* x_orig, const float* range, double* ssim, double* ws, int n_chains,
+              int n_samples, int c, int h, int w, nhmc_stream_t stream);
+int nhmc_moments_tiles(int64_t hw);
+int nhmc_sample_moments(const float* samples, float* mean, float* std_map, float* minmax, double* ws, int n_chains,
+                        int n_samples, int c, int h, int w, nhmc_stream_t stream);
+int nhmc_std_map_normalise(const float* std_map, const float* minmax, float* out, int n_chains, int64_t hw,
+                           nhmc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * a1  Momentum / accept noise: Philox4x32-10 keyed by seed, counted by
  *     (element quad, chain_id0 + chain, draw, tag) -- independent of how chains are sharded.
  *     Replaces torch.randn_like (main_sampling.py:692) and torch.rand(1) (:720).

@@ -10,6 +10,7 @@ include/nhmc.h.  Import as `nhmc` (see /nhmc.py); the directory keeps the projec
     sampler    hmc(...) with the reference signature, iterative_sampling, the per-chain engine
     unet       guided-diffusion FFHQ U-Net architecture (PyTorch-ROCm; loads ffhq_10m.pt)
     sharding   chain partition over ranks + the single end-of-run gather
+    metrics    the report of the collected samples: PSNR, SSIM, posterior mean and per-pixel std map, on the device
 """
 __version__ = '0.1.0'
 

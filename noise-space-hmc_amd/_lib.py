@@ -100,6 +100,14 @@ SIGNATURES = {
     'nhmc_conv3x3_wino_covers': (I, [I, I, I, I, I]),
     'nhmc_conv3x3_wino_prefers': (I, [I, I, I, I, I, I]),
     'nhmc_psnr':(I, [P, P, P, P, I, I64, P]),
+    'nhmc_psnr_samples': (I, [P, P, P, P, I, I, I64, P]),
+    'nhmc_ssim_tiles': (I, [I, I]),
+    'nhmc_ssim_ws_bytes': (SZ, [I, I, I, I]),
+    'nhmc_sample_range': (I, [P, P, P, I, I64, P]),
+    'nhmc_ssim': (I, [P, P, P, P, P, I, I, I, I, I, P]),
+    'nhmc_moments_tiles': (I, [I64]),
+    'nhmc_sample_moments': (I, [P, P, P, P, P, I, I, I, I, I, P]),
+    'nhmc_std_map_normalise': (I, [P, P, P, I, I64, P]),
     'nhmc_randn_philox': (I, [P, U64, U32, U32, F, I, I64, P]),
     'nhmc_copy_probe': (I, [P, P, I64, P]),
     'nhmc_uniform_philox': (I, [P, U64, U32, U32, I, P]),

@@ -27,8 +27,7 @@ import random
 import numpy as np
 import torch
 
-from . import ldm, operators, plugin, sampler, schedule, sharding, unet
-from . import kernels as K
+from . import ldm, metrics, operators, plugin, sampler, schedule, sharding, unet
 
 
 def get_parser(latent=False):
@@ -63,6 +62,8 @@ def get_parser(latent=False):
     p.add_argument('--synthetic', type=int, default=0, help='use this many synthetic images')
     p.add_argument('--philox', action='store_true', help='counter-based, shard-invariant noise')
     p.add_argument('--save_images', action='store_true')
+    p.add_argument('--metrics_out', type=str, default=None,
+                   help='write the per-image report (PSNR, SSIM, std-map range) as a JSON list to this path')
     p.add_argument('--spectral_projected', action='store_true',
                    help='deblur_aniso / deblur_gauss: residual in the left singular basis, 4 products instead of 8 (rounds differently)')
     p.add_argument('--graph', dest='use_graph', action='store_true',
@@ -200,23 +201,48 @@ def _setup(opt, latent):
     return config, rank, world, device, op, seq, [-1] + seq[:-1], images
 
 
-def _report(rows, n_images, rank, world, device):
-    local = torch.tensor(rows, dtype=torch.float32, device=device).reshape(-1, 3)
-    table = sharding.gather_chains(local, n_images, rank, world).cpu()
+COLUMNS = ('image', 'psnr_mean', 'psnr_std', 'ssim_mean', 'ssim_std', 'std_map_min', 'std_map_max', 'n_samples')
+
+
+def _report(rows, n_images, rank, world, device, metrics_out=None):
+    """Gathers the per-image rows (COLUMNS) over the ranks in global image order, prints the report on rank 0 and returns
+    the [n, 3] table (image, PSNR mean, PSNR std over its samples)."""
+    local = torch.tensor(rows, dtype=torch.float64, device=device).reshape(-1, len(COLUMNS))
+    full = sharding.gather_chains(local, n_images, rank, world).cpu()
+    table = full[:, :3].float()
     if rank == 0:
-        for idx, mean, std in table.tolist():
+        for (idx, mean, std), (_, _, _, s_mean, s_std, _, _, _) in zip(table.tolist(), full.tolist()):
             print(f'image {int(idx)}: PSNR {mean:.3f} (std over samples {std:.4f})' if mean == mean else
                   f'image {int(idx)}: no sample was collected (every proposal of the final phase was rejected)')
+            if mean == mean:
+                print(f'image {int(idx)}: SSIM {s_mean:.5f} (std over samples {s_std:.5f})')
         print(f'Total Average PSNR: {float(table[:, 1].nanmean()):.3f}  images: {table.shape[0]}')
+        # main_sampling.py:560: the average over the images, and in parentheses the mean over the images of each
+        # image's std over its samples
+        print('Total Average SSIM: {:.5f} ({:.5f})'.format(float(full[:, 3].nanmean()), float(full[:, 4].nanmean())))
+        if metrics_out:
+            import json
+            as_json = lambda k, v: int(v) if k in ('image', 'n_samples') else (v if v == v else None)
+            os.makedirs(os.path.dirname(metrics_out) or '.', exist_ok=True)
+            with open(metrics_out, 'w') as f:
+                json.dump([{k: as_json(k, v) for k, v in zip(COLUMNS, row)} for row in full.tolist()], f, indent=1)
     sharding.barrier()
     return table
 
 
-def _psnr_row(s, samples, x_orig_1):
-    if samples.shape[0] == 0:
-        return [float(s), float('nan'), 0.0]
-    ps = torch.stack([K.psnr(samples[j:j + 1].contiguous(), x_orig_1)[0] for j in range(samples.shape[0])])
-    return [float(s), float(ps.mean()), float(ps.std()) if ps.numel() > 1 else 0.0]
+def _metric_rows(batch, summary):
+    """One COLUMNS row per image of `batch` from a `metrics.summarize` result (chain i of it for image i)."""
+    return [[float(s)] + [float(summary[c][i]) for c in COLUMNS[1:-1]] + [float(summary['n_samples'])]
+            for i, s in enumerate(batch)]
+
+
+def _save_report_images(summary, k, s, one_sample, folder):
+    """`{s}_mean.png` and, with two samples or more, `std_dev_map_{s}.png` (main_sampling.py:494-507)."""
+    if summary['mean'] is None:
+        sampler._save_png(one_sample, os.path.join(folder, f'{s}_mean.png'))
+        return
+    sampler._save_png(summary['mean'][k], os.path.join(folder, f'{s}_mean.png'))
+    metrics.save_std_map(summary['std_map_normalised'][k], os.path.join(folder, f'std_dev_map_{s}.png'))
 
 
 def main(argv=None):
@@ -264,11 +290,12 @@ def main(argv=None):
         opt.chain_id0 = batch[0]
         out = run_with_oom_backoff(opt, lambda: sampler.hmc(x, n, b, seq, seq_next, algo, opt, y_0, op, x_orig))
         samples = out[None] if n == 1 else out                              # [n, 20, C, H, W]
-        for k, s in enumerate(batch):
-            rows.append(_psnr_row(s, samples[k], x_orig[k:k + 1]))
-            if opt.save_images:
-                sampler._save_png(samples[k].mean(0), os.path.join(opt.image_folder, f'{s}_mean.png'))
-    return _report(rows, images.shape[0], rank, world, device)
+        summary = metrics.summarize(samples.contiguous(), x_orig)
+        rows += _metric_rows(batch, summary)
+        if opt.save_images and samples.shape[1]:
+            for k, s in enumerate(batch):
+                _save_report_images(summary, k, s, samples[k, 0], opt.image_folder)
+    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out)
 
 
 def main_latent(argv=None):
@@ -303,10 +330,13 @@ def main_latent(argv=None):
         per_chain = [out] if n == 1 else out                               # latents [<=10, C, h, w] per chain
         for k, s in enumerate(batch):
             imgs = model.decode_first_stage(per_chain[k]) if per_chain[k].shape[0] else per_chain[k]
-            rows.append(_psnr_row(s, imgs, x_orig[k:k + 1]))
+            if imgs.shape[0] == 0:                                         # nothing to decode: [0, C, h, w] latents
+                imgs = x_orig.new_empty((0,) + tuple(x_orig.shape[1:]))
+            summary = metrics.summarize(imgs.contiguous(), x_orig[k:k + 1])    # per chain: the sample count is ragged
+            rows += _metric_rows([s], summary)
             if opt.save_images and imgs.shape[0]:
-                sampler._save_png(imgs.mean(0), os.path.join(opt.image_folder, f'{s}_mean.png'))
-    return _report(rows, images.shape[0], rank, world, device)
+                _save_report_images(summary, 0, s, imgs[0], opt.image_folder)
+    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out)
 
 
 if __name__ == '__main__':

@@ -159,16 +159,17 @@ __global__ void k_schedule_end_latent(const int32_t* __restrict__ accept, int32_
 // ---- PSNR -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(NHMC_BLOCK) void k_psnr_partial(const float4* __restrict__ xt,
                                                              const float4* __restrict__ xo, double* __restrict__ ws,
-                                                             int64_t n4) {
+                                                             int64_t n4, int rows_per_ref) {
   const int chain = blockIdx.y;
   const int64_t base = (int64_t)chain * n4;
+  const int64_t obase = (int64_t)(chain / rows_per_ref) * n4;   // nhmc_psnr_samples: a chain's samples share its original
   const int64_t t0 = (int64_t)blockIdx.x * (NHMC_BLOCK * NHMC_VEC_PER_THREAD) + threadIdx.x;
   float acc = 0.0f;
 #pragma unroll
   for (int i = 0; i < NHMC_VEC_PER_THREAD; ++i) {
     const int64_t q = t0 + (int64_t)i * NHMC_BLOCK;
     if (q >= n4) continue;
-    const float4 a = nhmc_ldnt(&xt[base + q]), b = nhmc_ldnt(&xo[base + q]);
+    const float4 a = nhmc_ldnt(&xt[base + q]), b = nhmc_ldnt(&xo[obase + q]);
     const float* ae = reinterpret_cast<const float*>(&a);
     const float* be = reinterpret_cast<const float*>(&b);
 #pragma unroll
@@ -363,9 +364,23 @@ extern "C" int nhmc_psnr(const float* xt, const float* x_orig, float* psnr, doub
   if ((n_elem & 3) || !nhmc_aligned16(xt) || !nhmc_aligned16(x_orig)) return NHMC_ERR_ALIGN;
   const int tiles = nhmc_data_tiles(n_elem);
   NHMC_LAUNCH(k_psnr_partial, dim3((unsigned)tiles, (unsigned)n_chains), dim3(NHMC_BLOCK), 0, nhmc_s(stream),
-                     (const float4*)xt, (const float4*)x_orig, ws, n_elem / 4);
+                     (const float4*)xt, (const float4*)x_orig, ws, n_elem / 4, 1);
   NHMC_LAUNCH(k_psnr_final, wave_grid(n_chains), dim3(256), 0, nhmc_s(stream), ws, tiles, n_elem, psnr,
                      n_chains);
+  return nhmc_launch_status();
+}
+
+// main_sampling.py:517-519 for every collected sample at once: row b * n_samples + j against x_orig[b], through the
+// kernels of nhmc_psnr (so with its bits).
+extern "C" int nhmc_psnr_samples(const float* samples, const float* x_orig, float* psnr, double* ws, int n_chains,
+                                 int n_samples, int64_t n_elem, nhmc_stream_t stream) {
+  if (!samples || !x_orig || !psnr || !ws || n_chains <= 0 || n_samples <= 0 || n_elem <= 0) return NHMC_ERR_ARG;
+  if ((n_elem & 3) || !nhmc_aligned16(samples) || !nhmc_aligned16(x_orig)) return NHMC_ERR_ALIGN;
+  if ((int64_t)n_chains * n_samples > 65535) return NHMC_ERR_SHAPE;
+  const int rows = n_chains * n_samples, tiles = nhmc_data_tiles(n_elem);
+  NHMC_LAUNCH(k_psnr_partial, dim3((unsigned)tiles, (unsigned)rows), dim3(NHMC_BLOCK), 0, nhmc_s(stream),
+              (const float4*)samples, (const float4*)x_orig, ws, n_elem / 4, n_samples);
+  NHMC_LAUNCH(k_psnr_final, wave_grid(rows), dim3(256), 0, nhmc_s(stream), ws, tiles, n_elem, psnr, rows);
   return nhmc_launch_status();
 }
 

@@ -1086,6 +1086,86 @@ def psnr(xt, x_orig):
     return out
 
 
+# ---- report stage (nhmc.h "Report stage") ------------------------------------------------------
+def _sample_block(samples, x_orig=None):
+    """samples [B, S, C, H, W] (and x_orig [B, C, H, W]) -> (B, S, C, H, W)"""
+    if samples.dim() != 5:
+        raise _lib.NhmcError(f'samples must be [chains, samples, C, H, W], got {tuple(samples.shape)}')
+    if x_orig is not None and (x_orig.dim() != 4 or x_orig.shape[0] != samples.shape[0] or x_orig.shape[1:] != samples.shape[2:]):
+        raise _lib.NhmcError(f'x_orig {tuple(x_orig.shape)} does not match samples {tuple(samples.shape)}')
+    return tuple(samples.shape)
+
+
+def psnr_samples(samples, x_orig):
+    """PSNR of samples[b, j] against x_orig[b] -> float32 [B, S], the bits `psnr` gives pair by pair, in one launch pair."""
+    lib = _lib.load()
+    B, S, Cc, H, W = _sample_block(samples, x_orig)
+    N = Cc * H * W
+    ws = torch.empty(B * S * lib.nhmc_data_tiles(N), dtype=torch.float64, device=samples.device)
+    out = torch.empty((B, S), dtype=torch.float32, device=samples.device)
+    _lib.check(lib.nhmc_psnr_samples(_p(samples, torch.float32, 'samples'), _p(x_orig, torch.float32, 'x_orig'), _p(out),
+                                     _p(ws), B, S, N, _stream()), 'nhmc_psnr_samples')
+    return out
+
+
+def ssim_ws(n_total_samples, Cc, H, W, device):
+    return torch.empty(_lib.load().nhmc_ssim_ws_bytes(n_total_samples, Cc, H, W) // 8, dtype=torch.float64, device=device)
+
+
+def sample_range(samples, ws=None):
+    """max - min of every transformed sample over all its channels -> float32 [B, S] (the reference's `data_range`)."""
+    lib = _lib.load()
+    B, S, Cc, H, W = _sample_block(samples)
+    ws = ssim_ws(B * S, Cc, H, W, samples.device) if ws is None else ws
+    out = torch.empty((B, S), dtype=torch.float32, device=samples.device)
+    _lib.check(lib.nhmc_sample_range(_p(samples, torch.float32, 'samples'), _p(out), _p(ws, torch.float64, 'ws'), B * S,
+                                     Cc * H * W, _stream()), 'nhmc_sample_range')
+    return out
+
+
+def ssim(samples, x_orig, data_range=None):
+    """skimage's default SSIM (channel_axis=0) of samples[b, j] against x_orig[b] with data_range = the sample's own range
+    -> float64 [B, S]."""
+    lib = _lib.load()
+    B, S, Cc, H, W = _sample_block(samples, x_orig)
+    ws = ssim_ws(B * S, Cc, H, W, samples.device)
+    if data_range is None:
+        data_range = sample_range(samples, ws)
+    elif data_range.shape != (B, S):
+        raise _lib.NhmcError(f'data_range must be [{B}, {S}]')
+    out = torch.empty((B, S), dtype=torch.float64, device=samples.device)
+    _lib.check(lib.nhmc_ssim(_p(samples, torch.float32, 'samples'), _p(x_orig, torch.float32, 'x_orig'),
+                             _p(data_range, torch.float32, 'data_range'), _p(out), _p(ws, torch.float64, 'ws'), B, S, Cc, H, W,
+                             _stream()), 'nhmc_ssim')
+    return out
+
+
+def sample_moments(samples):
+    """-> (mean [B, C, H, W] of the raw samples, std_map [B, H, W] of the transformed ones, minmax [B, 2] of the map)"""
+    lib = _lib.load()
+    B, S, Cc, H, W = _sample_block(samples)
+    dev = samples.device
+    mean = torch.empty((B, Cc, H, W), dtype=torch.float32, device=dev)
+    std_map = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    minmax = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    ws = torch.empty(B * lib.nhmc_moments_tiles(H * W) * 2, dtype=torch.float64, device=dev)
+    _lib.check(lib.nhmc_sample_moments(_p(samples, torch.float32, 'samples'), _p(mean), _p(std_map), _p(minmax), _p(ws),
+                                       B, S, Cc, H, W, _stream()), 'nhmc_sample_moments')
+    return mean, std_map, minmax
+
+
+def std_map_normalise(std_map, minmax):
+    """(std_map - min) / (max - min) per chain -> float32 [B, H, W]"""
+    lib = _lib.load()
+    if std_map.dim() != 3 or minmax.shape != (std_map.shape[0], 2):
+        raise _lib.NhmcError('std_map must be [B, H, W] and minmax [B, 2]')
+    out = torch.empty_like(std_map)
+    _lib.check(lib.nhmc_std_map_normalise(_p(std_map, torch.float32, 'std_map'), _p(minmax, torch.float32, 'minmax'), _p(out),
+                                          std_map.shape[0], std_map.shape[1] * std_map.shape[2], _stream()),
+               'nhmc_std_map_normalise')
+    return out
+
+
 # ---- a1 -------------------------------------------------------------------------------------
 def randn_philox(shape, seed, chain_id0, draw, scale=1.0, device='cuda', out=None):
     lib = _lib.load()
