@@ -628,6 +628,47 @@ int nhmc_std_map_normalise(const float* std_map, const float* minmax, float* out
                            nhmc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Convergence of replica chains: split R-hat and effective sample size per element, on the device.
+ *
+ *   samples : fp32 [n_groups * n_replicas][n_samples][n_elem], the block the sampler returns; chain g * n_replicas + r is
+ *             replica r of image (group) g.  rhat, ess : fp32 [n_groups][n_elem], each rounded once from fp64.
+ *   summary : fp64 [n_groups][6].  ws : double, nhmc_chain_diag_ws_bytes(n_groups, n_elem) bytes: 8 partials for each of
+ *             the nhmc_chain_diag_tiles(n_elem) tiles (256 elements each) of every group.
+ *   Validation, before any launch: null pointer / non-positive size -> ARG; samples, rhat or ess not 16-byte aligned or
+ *   n_elem % 4 != 0 -> ALIGN; n_samples < 4, n_samples / 2 > 32, n_replicas * n_samples > 4096 or n_groups > 65535 -> SHAPE.
+ *   n_replicas = 1 is allowed: split R-hat of one chain is defined.
+ *
+ * Definition, per element e of group g, with S = n_samples and K = n_replicas.  All arithmetic is fp64 on the fp32 inputs.
+ *   Split chains.  n = S / 2 (integer division) and M = 2K.  Split chain 2r is draws [0, n) of replica r, split chain
+ *     2r+1 is draws [S - n, S); for odd S the middle draw is dropped.
+ *   Per split chain m.  Mean mu_m: a sum over n divided once.  Deviations d = x - mu_m.  Biased autocovariances
+ *     a_m[t] = (1/n) sum_{i=0}^{n-1-t} d_i d_{i+t}  for t = 0 and for 1 <= t <= n - 2.
+ *   Variances.  W = (1/M) sum_m a_m[0] * n/(n-1).  Bn = the ddof = 1 variance of the M means (taken about the first split
+ *     chain's mean, which leaves the value unchanged and makes chains that sit at one common value give exactly 0).
+ *     V = W (n-1)/n + Bn.
+ *   R-hat.  V == 0: the element is *constant* (clipped pixels make this common): rhat = ess = NaN.
+ *     V > 0 and W == 0 (chains stuck at different constants): rhat = +inf, ess = NaN.  Otherwise rhat = sqrt(V / W).
+ *   Autocorrelations.  rho_0 = 1 and rho_t = 1 - (W - (1/M) sum_m a_m[t]) / V for t >= 1.
+ *   ESS: Geyer's initial monotone sequence as in the Stan reference manual, on the raw draws (no rank normalisation).
+ *     For k = 0, 1, ... while 2k + 1 <= n - 2: P_k = rho_{2k} + rho_{2k+1}; stop at the first k with P_k <= 0; each kept
+ *     P_k is replaced by min(P_k, P_{k-1}).  tau = -1 + 2 sum of the kept P_k, tau = max(tau, 1 / log10(M n)),
+ *     ess = M n / tau.  So S < 6 (n = 2: no P_k exists) always yields the cap M n log10(M n).
+ *   Summary per group, from the fp64 values before rounding:
+ *     [0] rhat_max         over the non-constant elements; may be +inf; NaN when every element is constant
+ *     [1] rhat_mean        over the finite values
+ *     [2] rhat_frac_above  share of the non-constant elements with rhat > rhat_threshold (+inf counts)
+ *     [3] ess_min, [4] ess_mean   over the non-NaN values
+ *     [5] n_constant       number of constant elements
+ *     A mean or share over no element is NaN.
+ *   Reductions: per-tile fp64 partials in ws and a fixed-order second pass; equal inputs give equal bits, no atomics.
+ *   Every sample value is read once: K S 4 bytes per element read, 8 written.
+ * ---------------------------------------------------------------------------------- */
+int nhmc_chain_diag_tiles(int64_t n_elem);
+size_t nhmc_chain_diag_ws_bytes(int n_groups, int64_t n_elem);
+int nhmc_chain_diag(const float* samples, float* rhat, float* ess, double* summary, double* ws, int n_groups,
+                    int n_replicas, int n_samples, int64_t n_elem, double rhat_threshold, nhmc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * a1  Momentum / accept noise: Philox4x32-10 keyed by seed, counted by
  *     (element quad, chain_id0 + chain, draw, tag) -- independent of how chains are sharded.
  *     Replaces torch.randn_like (main_sampling.py:692) and torch.rand(1) (:720).

@@ -108,6 +108,9 @@ SIGNATURES = {
     'nhmc_moments_tiles': (I, [I64]),
     'nhmc_sample_moments': (I, [P, P, P, P, P, I, I, I, I, I, P]),
     'nhmc_std_map_normalise': (I, [P, P, P, I, I64, P]),
+    'nhmc_chain_diag_tiles': (I, [I64]),
+    'nhmc_chain_diag_ws_bytes': (SZ, [I, I64]),
+    'nhmc_chain_diag': (I, [P, P, P, P, P, I, I, I, I64, D, P]),
     'nhmc_randn_philox': (I, [P, U64, U32, U32, F, I, I64, P]),
     'nhmc_copy_probe': (I, [P, P, I64, P]),
     'nhmc_uniform_philox': (I, [P, U64, U32, U32, I, P]),

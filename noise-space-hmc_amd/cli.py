@@ -17,6 +17,12 @@ generator keyed by (seed, s) -- never from the global stream -- so with `--philo
 image's result does not depend on the number of ranks (nor, up to the score network's batch-size-dependent
 convolution rounding, on `--chains`).  `--spectral_projected` switches the two blur operators to the four-product data
 term (operators.Deblurring2D).
+
+`--replicas K` spends the chains on K replica chains per image instead (a batch then holds `--chains` // K images, chain
+i * K + r being replica r of the batch's image i): all replicas see the same measurement, replica 0 starts where the
+single chain starts, replicas r >= 1 start from their own N(0,1) draw keyed by (seed, s, r), and the Philox stream of
+replica r of image s is s * K + r.  The report pools an image's K * S samples and adds the split R-hat / ESS line
+(nhmc.metrics.convergence).  With K = 1, the default, nothing changes.
 """
 import argparse
 import glob
@@ -70,6 +76,12 @@ def get_parser(latent=False):
                    help='replay each decode+gradient chunk as a hipGraph (helps single-chain runs: ~1.2x)')
     p.add_argument('--hmc_epochs', type=int, default=60, help='annealing epochs (reference: 60, main_sampling.py:665)')
     p.add_argument('--hmc_sampling', type=int, default=20, help='collected samples (reference: 20, :666)')
+    p.add_argument('--replicas', type=int, default=1,
+                   help='replica chains per image, from overdispersed starts; --chains must be a multiple of it. The report '
+                        'pools their samples and adds split R-hat and ESS per pixel')
+    p.add_argument('--rhat_threshold', type=float, default=1.1,
+                   help="R-hat above which a pixel counts as not converged (Gelman's classic 1.1; with the 10 draws per "
+                        'split chain of a 20-sample run the stricter 1.01 flags sampling noise)')
     return p
 
 
@@ -167,9 +179,44 @@ def draw_inputs(seed, s, y_clean, sigma_0, x_shape):
     return y_clean + sigma_0 * noise.to(y_clean.device), x.to(y_clean.device)
 
 
+def replica_generator(seed, s, r):
+    """Generator of the start point of replica r >= 1 of image s, keyed by (seed, s, r) on the host; replica 0 uses
+    `image_generator(seed, s)`.  The multiplier differs from image_generator's, so no (s, r) lands on an image's key."""
+    return torch.Generator().manual_seed(((int(seed) * 1000003 + int(s)) * 998244353 + int(r)) & 0x7FFFFFFFFFFFFFFF)
+
+
+def replica_inputs(seed, s, K, y_clean, sigma_0, x_shape):
+    """-> (y_0 [K, M], x_start [K, *x_shape]) for the K replica chains of image s.  All replicas share one measurement,
+    the y_0 of `draw_inputs`; replica 0 starts at `draw_inputs`' start point (its bits), replica r >= 1 at an N(0,1)
+    draw from `replica_generator(seed, s, r)` -- starts that are overdispersed against the posterior.  Nothing here
+    depends on the batch the image is sampled in."""
+    y_0, x0 = draw_inputs(seed, s, y_clean, sigma_0, x_shape)
+    xs = [x0] + [torch.randn(x_shape, generator=replica_generator(seed, s, r)).to(y_clean.device) for r in range(1, K)]
+    return y_0[None].expand(K, *y_0.shape), torch.stack(xs)
+
+
+def common_samples(replicas):
+    """The latent sampler's sample count is ragged over chains: an image's replicas [S_r, ...] are cut to the last
+    S_c = min S_r samples of each -> ([K * S_c, ...] replica-major, S_c)."""
+    s_c = min(z.shape[0] for z in replicas)
+    return torch.cat([z[z.shape[0] - s_c:] for z in replicas]), s_c
+
+
+def chain_id_base(batch, K=1):
+    """Philox stream id of the batch's first chain: replica r of image s has the global chain id s * K + r."""
+    return batch[0] * K
+
+
+def check_replicas(opt):
+    """--chains must hold whole images; raised before anything touches the GPU."""
+    if opt.replicas < 1 or opt.chains % opt.replicas:
+        raise SystemExit(f'--chains {opt.chains} must be a positive multiple of --replicas {opt.replicas}: a batch holds '
+                         f'chains // replicas images, each with all its replicas')
+
+
 def image_batches(n_images, rank, world, chains):
     """Global image indices this rank samples, in batches of `chains`: contiguous block partition over ranks
-    (sharding.chain_range), batches never straddle ranks."""
+    (sharding.chain_range), batches never straddle ranks.  With K replicas per image pass `chains // K`."""
     lo, hi = sharding.chain_range(n_images, rank, world)
     return [list(range(s, min(hi, s + chains))) for s in range(lo, hi, chains)]
 
@@ -202,37 +249,51 @@ def _setup(opt, latent):
 
 
 COLUMNS = ('image', 'psnr_mean', 'psnr_std', 'ssim_mean', 'ssim_std', 'std_map_min', 'std_map_max', 'n_samples')
+REPLICA_COLUMNS = ('replicas',) + metrics.CONVERGENCE_KEYS          # appended to COLUMNS with --replicas K > 1
+INT_COLUMNS = ('image', 'n_samples', 'replicas', 'n_constant')
 
 
-def _report(rows, n_images, rank, world, device, metrics_out=None):
-    """Gathers the per-image rows (COLUMNS) over the ranks in global image order, prints the report on rank 0 and returns
-    the [n, 3] table (image, PSNR mean, PSNR std over its samples)."""
-    local = torch.tensor(rows, dtype=torch.float64, device=device).reshape(-1, len(COLUMNS))
+def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, rhat_threshold=1.1):
+    """Gathers the per-image rows (COLUMNS, with K > 1 replicas + REPLICA_COLUMNS) over the ranks in global image order,
+    prints the report on rank 0 and returns the [n, 3] table (image, PSNR mean, PSNR std over its samples)."""
+    columns = COLUMNS + (REPLICA_COLUMNS if replicas > 1 else ())
+    local = torch.tensor(rows, dtype=torch.float64, device=device).reshape(-1, len(columns))
     full = sharding.gather_chains(local, n_images, rank, world).cpu()
     table = full[:, :3].float()
     if rank == 0:
-        for (idx, mean, std), (_, _, _, s_mean, s_std, _, _, _) in zip(table.tolist(), full.tolist()):
+        for (idx, mean, std), row in zip(table.tolist(), full.tolist()):
+            s_mean, s_std = row[3], row[4]
             print(f'image {int(idx)}: PSNR {mean:.3f} (std over samples {std:.4f})' if mean == mean else
                   f'image {int(idx)}: no sample was collected (every proposal of the final phase was rejected)')
             if mean == mean:
                 print(f'image {int(idx)}: SSIM {s_mean:.5f} (std over samples {s_std:.5f})')
+            c = dict(zip(columns, row))
+            if replicas > 1 and mean == mean and c['n_constant'] != c['n_constant']:
+                print(f'image {int(idx)}: no R-hat / ESS: fewer than 4 samples per replica ({int(c["n_samples"])} draws in all)')
+            elif replicas > 1 and mean == mean:
+                print(f'image {int(idx)}: R-hat max {c["rhat_max"]:.3f} mean {c["rhat_mean"]:.4f} '
+                      f'(> {rhat_threshold:g}: {100.0 * c["rhat_frac_above"]:.2f}%)  ESS min {c["ess_min"]:.1f} '
+                      f'mean {c["ess_mean"]:.1f} of {int(c["n_samples"])} draws, constant elements {int(c["n_constant"])}')
         print(f'Total Average PSNR: {float(table[:, 1].nanmean()):.3f}  images: {table.shape[0]}')
         # main_sampling.py:560: the average over the images, and in parentheses the mean over the images of each
         # image's std over its samples
         print('Total Average SSIM: {:.5f} ({:.5f})'.format(float(full[:, 3].nanmean()), float(full[:, 4].nanmean())))
         if metrics_out:
             import json
-            as_json = lambda k, v: int(v) if k in ('image', 'n_samples') else (v if v == v else None)
+            as_json = lambda k, v: (int(v) if k in INT_COLUMNS and v == v else (v if v == v else None))
             os.makedirs(os.path.dirname(metrics_out) or '.', exist_ok=True)
             with open(metrics_out, 'w') as f:
-                json.dump([{k: as_json(k, v) for k, v in zip(COLUMNS, row)} for row in full.tolist()], f, indent=1)
+                json.dump([{k: as_json(k, v) for k, v in zip(columns, row)} for row in full.tolist()], f, indent=1)
     sharding.barrier()
     return table
 
 
 def _metric_rows(batch, summary):
-    """One COLUMNS row per image of `batch` from a `metrics.summarize` result (chain i of it for image i)."""
-    return [[float(s)] + [float(summary[c][i]) for c in COLUMNS[1:-1]] + [float(summary['n_samples'])]
+    """One COLUMNS row per image of `batch` from a `metrics.summarize` result (entry i of it for image i); a pooled
+    summary (replicas > 1) appends REPLICA_COLUMNS."""
+    pooled = summary.get('replicas', 1) > 1
+    return [[float(s)] + [float(summary[c][i]) for c in COLUMNS[1:-1]] + [float(summary['n_samples'])] +
+            ([float(summary['replicas'])] + [float(summary[c][i]) for c in metrics.CONVERGENCE_KEYS] if pooled else [])
             for i, s in enumerate(batch)]
 
 
@@ -243,6 +304,8 @@ def _save_report_images(summary, k, s, one_sample, folder):
         return
     sampler._save_png(summary['mean'][k], os.path.join(folder, f'{s}_mean.png'))
     metrics.save_std_map(summary['std_map_normalised'][k], os.path.join(folder, f'std_dev_map_{s}.png'))
+    if summary.get('rhat') is not None:
+        metrics.save_rhat_map(summary['rhat'][k], os.path.join(folder, f'rhat_map_{s}.png'))
 
 
 def main(argv=None):
@@ -251,6 +314,7 @@ def main(argv=None):
         raise NotImplementedError('--algo hmc_latent is served by main_sampling_latent.py (nhmc.cli.main_latent), as in the reference')
     if opt.algo != 'hmc':
         raise NotImplementedError(f"--algo {opt.algo}: this build serves the noise-space HMC path (--algo hmc) only")
+    check_replicas(opt)
     config, rank, world, device, op, seq, seq_next, images = _setup(opt, latent=False)
     size, ch = config['data']['image_size'], config['data']['channels']
     mc = dict(config['model'])
@@ -280,22 +344,23 @@ def main(argv=None):
             torch.autograd.grad(out, xw, torch.ones_like(out))
             torch.cuda.synchronize()
         sharding.barrier()
-    rows = []
-    for batch in image_batches(images.shape[0], rank, world, opt.chains):
+    rows, K = [], opt.replicas
+    for batch in image_batches(images.shape[0], rank, world, opt.chains // K):
         x_orig = images[batch[0]:batch[-1] + 1].to(device).contiguous()
-        n = x_orig.shape[0]
-        drawn = [draw_inputs(opt.seed, s, yk, opt.sigma_0, (ch, size, size)) for s, yk in zip(batch, op.H(x_orig))]
-        y_0 = torch.stack([d_[0] for d_ in drawn]).contiguous()
-        x = torch.stack([d_[1] for d_ in drawn]).contiguous()
-        opt.chain_id0 = batch[0]
-        out = run_with_oom_backoff(opt, lambda: sampler.hmc(x, n, b, seq, seq_next, algo, opt, y_0, op, x_orig))
+        n = x_orig.shape[0] * K                                             # chains: image-major, replica r of image i at i * K + r
+        drawn = [replica_inputs(opt.seed, s, K, yk, opt.sigma_0, (ch, size, size)) for s, yk in zip(batch, op.H(x_orig))]
+        y_0 = torch.cat([d_[0] for d_ in drawn]).contiguous()
+        x = torch.cat([d_[1] for d_ in drawn]).contiguous()
+        x_chain = x_orig if K == 1 else x_orig.repeat_interleave(K, dim=0)   # the sampler's PSNR trace wants one per chain
+        opt.chain_id0 = chain_id_base(batch, K)
+        out = run_with_oom_backoff(opt, lambda: sampler.hmc(x, n, b, seq, seq_next, algo, opt, y_0, op, x_chain))
         samples = out[None] if n == 1 else out                              # [n, 20, C, H, W]
-        summary = metrics.summarize(samples.contiguous(), x_orig)
+        summary = metrics.summarize(samples.contiguous(), x_orig, replicas=K, rhat_threshold=opt.rhat_threshold)
         rows += _metric_rows(batch, summary)
         if opt.save_images and samples.shape[1]:
             for k, s in enumerate(batch):
-                _save_report_images(summary, k, s, samples[k, 0], opt.image_folder)
-    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out)
+                _save_report_images(summary, k, s, samples[k * K, 0], opt.image_folder)
+    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out, K, opt.rhat_threshold)
 
 
 def main_latent(argv=None):
@@ -305,6 +370,7 @@ def main_latent(argv=None):
     opt, _unknown = get_parser(latent=True).parse_known_args(argv)
     if opt.algo != 'hmc_latent':
         raise NotImplementedError(f"--algo {opt.algo}: the latent entry serves --algo hmc_latent only")
+    check_replicas(opt)
     config, rank, world, device, op, seq, seq_next, images = _setup(opt, latent=True)
     model = ldm.create_latent_model(config['model'], ckpt='models/ldm/model.ckpt', quiet=rank != 0).to(device)
     algo = plugin.HMCLatent(model, op, opt.sigma_0)
@@ -318,25 +384,27 @@ def main_latent(argv=None):
     opt.score_chunk = auto_score_chunk(opt, device, probe, world)
     if world > 1:
         sharding.barrier()
-    rows = []
-    for batch in image_batches(images.shape[0], rank, world, opt.chains):
+    rows, K = [], opt.replicas
+    for batch in image_batches(images.shape[0], rank, world, opt.chains // K):
         x_orig = images[batch[0]:batch[-1] + 1].to(device).contiguous()
-        n = x_orig.shape[0]
-        drawn = [draw_inputs(opt.seed, s, yk, opt.sigma_0, (zc, zs, zs)) for s, yk in zip(batch, op.H(x_orig))]
-        y_0 = torch.stack([d_[0] for d_ in drawn]).contiguous()
-        x = torch.stack([d_[1] for d_ in drawn]).contiguous()
-        opt.chain_id0 = batch[0]
-        out = run_with_oom_backoff(opt, lambda: sampler.hmc_latent(x, n, seq, seq_next, algo, opt, y_0, op, x_orig))
+        n = x_orig.shape[0] * K
+        drawn = [replica_inputs(opt.seed, s, K, yk, opt.sigma_0, (zc, zs, zs)) for s, yk in zip(batch, op.H(x_orig))]
+        y_0 = torch.cat([d_[0] for d_ in drawn]).contiguous()
+        x = torch.cat([d_[1] for d_ in drawn]).contiguous()
+        x_chain = x_orig if K == 1 else x_orig.repeat_interleave(K, dim=0)
+        opt.chain_id0 = chain_id_base(batch, K)
+        out = run_with_oom_backoff(opt, lambda: sampler.hmc_latent(x, n, seq, seq_next, algo, opt, y_0, op, x_chain))
         per_chain = [out] if n == 1 else out                               # latents [<=10, C, h, w] per chain
         for k, s in enumerate(batch):
-            imgs = model.decode_first_stage(per_chain[k]) if per_chain[k].shape[0] else per_chain[k]
-            if imgs.shape[0] == 0:                                         # nothing to decode: [0, C, h, w] latents
-                imgs = x_orig.new_empty((0,) + tuple(x_orig.shape[1:]))
-            summary = metrics.summarize(imgs.contiguous(), x_orig[k:k + 1])    # per chain: the sample count is ragged
+            lat, s_c = common_samples(per_chain[k * K:(k + 1) * K])
+            imgs = model.decode_first_stage(lat) if s_c else x_orig.new_empty((0,) + tuple(x_orig.shape[1:]))
+            imgs = imgs.reshape((K, s_c) + tuple(imgs.shape[1:])).contiguous()
+            summary = metrics.summarize(imgs if K > 1 else imgs[0], x_orig[k:k + 1], replicas=K,
+                                        rhat_threshold=opt.rhat_threshold)
             rows += _metric_rows([s], summary)
-            if opt.save_images and imgs.shape[0]:
-                _save_report_images(summary, 0, s, imgs[0], opt.image_folder)
-    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out)
+            if opt.save_images and s_c:
+                _save_report_images(summary, 0, s, imgs[0, 0], opt.image_folder)
+    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out, K, opt.rhat_threshold)
 
 
 if __name__ == '__main__':

@@ -224,6 +224,167 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_std_map_normalise(const float* _
   out[(int64_t)chain * hw + p] = (std_map[(int64_t)chain * hw + p] - lo) / (hi - lo);     // :497
 }
 
+// ---- split R-hat and ESS of K replica chains per element (nhmc.h "Convergence of replica chains") ----------------------
+// Thread = one element of one image; lanes hold consecutive elements, so every (replica, draw) load of a wave is one
+// contiguous 256-byte row and each sample value leaves HBM once.  The n draws of the current split chain sit in registers
+// (NMAX is a compile-time bound on n: every index below is a constant after unrolling, nothing goes to scratch), the next
+// split chain's draws are already in flight while this one's autocovariances are summed.  acc[t] = sum over the split
+// chains of sum_i d_i d_{i+t} (the 1/n is applied once at the end); the means enter as offsets from the first split
+// chain's mean, so chains stuck at one common value give Bn = 0 exactly whatever that value is.
+constexpr int DIAG_WS = 8;       // per-tile partials: rhat max, sum, finite count, count above; ess min, sum, count; constant
+
+template <int NMAX>
+__device__ __forceinline__ void diag_load(float (&x)[NMAX], const float* __restrict__ p, int n, int64_t stride) {
+#pragma unroll
+  for (int i = 0; i < NMAX; ++i) x[i] = i < n ? __builtin_nontemporal_load(p + (int64_t)i * stride) : 0.0f;
+}
+
+__device__ __forceinline__ const float* diag_split(const float* base, int m, int S, int n, int64_t n_elem) {
+  return base + ((int64_t)(m >> 1) * S + ((m & 1) ? S - n : 0)) * n_elem;      // split 2r: draws [0, n); 2r+1: [S-n, S)
+}
+
+// Block-level min of lo and max of hi (256 threads, doubles); result valid in thread 0.
+__device__ __forceinline__ void block_minmax_f64(double& lo, double& hi, double* lds /* [8] */) {
+  const int lane = threadIdx.x & (NHMC_WAVE - 1), wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int off = NHMC_WAVE / 2; off > 0; off >>= 1) {
+    lo = fmin(lo, __shfl_down(lo, off, NHMC_WAVE));
+    hi = fmax(hi, __shfl_down(hi, off, NHMC_WAVE));
+  }
+  if (lane == 0) { lds[wave * 2] = lo; lds[wave * 2 + 1] = hi; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    lo = fmin(fmin(lds[0], lds[2]), fmin(lds[4], lds[6]));
+    hi = fmax(fmax(lds[1], lds[3]), fmax(lds[5], lds[7]));
+  }
+}
+
+template <int NMAX>
+__global__ __launch_bounds__(NHMC_BLOCK) void k_chain_diag(const float* __restrict__ samples, float* __restrict__ rhat,
+                                                           float* __restrict__ ess, double* __restrict__ ws, int K, int S,
+                                                           int n, int64_t n_elem, double threshold) {
+  const int g = blockIdx.y;
+  const int64_t e = (int64_t)blockIdx.x * NHMC_BLOCK + threadIdx.x;
+  const int M = 2 * K;
+  double part[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // rhat sum, finite rhats, rhats above, ess sum, ess count, constant
+  double r_max = -INFINITY, e_min = INFINITY;
+  if (e < n_elem) {
+    const float* base = samples + (int64_t)g * K * S * n_elem + e;
+    double acc[NMAX - 1];
+#pragma unroll
+    for (int t = 0; t < NMAX - 1; ++t) acc[t] = 0.0;
+    double mu0 = 0.0, sm = 0.0, sq = 0.0;
+    float cur[NMAX], nxt[NMAX];
+    diag_load<NMAX>(cur, diag_split(base, 0, S, n, n_elem), n, n_elem);
+    for (int m = 0; m < M; ++m) {
+      if (m + 1 < M) diag_load<NMAX>(nxt, diag_split(base, m + 1, S, n, n_elem), n, n_elem);
+      double sum = 0.0;
+#pragma unroll
+      for (int i = 0; i < NMAX; ++i) sum += (double)cur[i];               // entries past n are zero
+      const double mu = sum / (double)n;
+      double d[NMAX];
+#pragma unroll
+      for (int i = 0; i < NMAX; ++i) d[i] = i < n ? (double)cur[i] - mu : 0.0;
+#pragma unroll
+      for (int t = 0; t < NMAX - 1; ++t) {
+        if (t <= n - 2 || t == 0) {                                       // wave-uniform
+          double s = 0.0;
+#pragma unroll
+          for (int i = 0; i + t < NMAX; ++i) s = fma(d[i], d[i + t], s);
+          acc[t] += s;
+        }
+      }
+      if (m == 0) mu0 = mu;
+      const double dm = mu - mu0;
+      sm += dm;
+      sq = fma(dm, dm, sq);
+      if (m + 1 < M) {
+#pragma unroll
+        for (int i = 0; i < NMAX; ++i) cur[i] = nxt[i];
+      }
+    }
+    const double dn = (double)n, dM = (double)M;
+    const double W = (acc[0] / dn / dM) * (dn / (dn - 1.0));
+    const double Bn = fmax((sq - sm * sm / dM) / (dM - 1.0), 0.0);
+    const double V = W * (dn - 1.0) / dn + Bn;
+    double r = NAN, es = NAN;
+    if (V == 0.0) {
+      part[5] = 1.0;
+    } else if (W == 0.0) {
+      r = INFINITY;
+    } else {
+      r = sqrt(V / W);
+      double sum_p = 0.0, prev = INFINITY;
+      bool go = true;
+#pragma unroll
+      for (int k = 0; 2 * k + 1 <= NMAX - 2; ++k) {
+        if (2 * k + 1 <= n - 2) {                                         // wave-uniform
+          const double rho0 = k == 0 ? 1.0 : 1.0 - (W - acc[2 * k] / dn / dM) / V;
+          const double rho1 = 1.0 - (W - acc[2 * k + 1] / dn / dM) / V;
+          double p = rho0 + rho1;
+          go = go && p > 0.0;
+          if (go) {
+            p = fmin(p, prev);
+            prev = p;
+            sum_p += p;
+          }
+        }
+      }
+      const double tau = fmax(-1.0 + 2.0 * sum_p, 1.0 / log10(dM * dn));
+      es = dM * dn / tau;
+    }
+    rhat[(int64_t)g * n_elem + e] = (float)r;
+    ess[(int64_t)g * n_elem + e] = (float)es;
+    if (r == r) {
+      r_max = r;
+      if (r < INFINITY) { part[0] = r; part[1] = 1.0; }
+      if (r > threshold) part[2] = 1.0;
+    }
+    if (es == es) { e_min = es; part[3] = es; part[4] = 1.0; }
+  }
+  __shared__ double red[24], red_mm[8];
+  nhmc_block_sum<6>(part, red);
+  block_minmax_f64(e_min, r_max, red_mm);
+  if (threadIdx.x == 0) {
+    double* out = ws + ((int64_t)g * gridDim.x + blockIdx.x) * DIAG_WS;
+    out[0] = r_max; out[1] = part[0]; out[2] = part[1]; out[3] = part[2];
+    out[4] = e_min; out[5] = part[3]; out[6] = part[4]; out[7] = part[5];
+  }
+}
+
+// One wave per image: the tiles' partials in a fixed order -> the six summaries.
+__global__ void k_chain_diag_final(const double* __restrict__ ws, int tiles, int64_t n_elem, double* __restrict__ summary,
+                                   int n_groups) {
+  const int g = blockIdx.x * (blockDim.x / NHMC_WAVE) + (threadIdx.x >> 6);
+  if (g >= n_groups) return;
+  const int lane = threadIdx.x & 63;
+  const double* part = ws + (int64_t)g * tiles * DIAG_WS;
+  double r_max = -INFINITY, e_min = INFINITY, s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int t = lane; t < tiles; t += NHMC_WAVE) {
+    const double* p = part + (int64_t)t * DIAG_WS;
+    r_max = fmax(r_max, p[0]);
+    e_min = fmin(e_min, p[4]);
+    s[0] += p[1]; s[1] += p[2]; s[2] += p[3]; s[3] += p[5]; s[4] += p[6]; s[5] += p[7];
+  }
+#pragma unroll
+  for (int off = NHMC_WAVE / 2; off > 0; off >>= 1) {
+    r_max = fmax(r_max, __shfl_down(r_max, off, NHMC_WAVE));
+    e_min = fmin(e_min, __shfl_down(e_min, off, NHMC_WAVE));
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) s[i] = nhmc_wave_sum(s[i]);
+  if (lane == 0) {
+    const double varying = (double)n_elem - s[5];
+    double* out = summary + (int64_t)g * 6;
+    out[0] = varying > 0.0 ? r_max : NAN;
+    out[1] = s[0] / s[1];
+    out[2] = s[2] / varying;
+    out[3] = s[4] > 0.0 ? e_min : NAN;
+    out[4] = s[3] / s[4];
+    out[5] = s[5];
+  }
+}
+
 inline dim3 wave_grid(int n) { return dim3((unsigned)((n + 3) / 4)); }
 inline int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }
 
@@ -293,5 +454,38 @@ extern "C" int nhmc_std_map_normalise(const float* std_map, const float* minmax,
   if (n_chains > 65535) return NHMC_ERR_SHAPE;
   NHMC_LAUNCH(k_std_map_normalise, dim3((unsigned)nhmc_moments_tiles(hw), (unsigned)n_chains), dim3(NHMC_BLOCK), 0,
               nhmc_s(stream), std_map, minmax, out, hw);
+  return nhmc_launch_status();
+}
+
+extern "C" int nhmc_chain_diag_tiles(int64_t n_elem) {
+  if (n_elem <= 0) return 0;
+  const int64_t t = (n_elem + NHMC_BLOCK - 1) / NHMC_BLOCK;
+  return t > INT32_MAX ? 0 : (int)t;
+}
+
+extern "C" size_t nhmc_chain_diag_ws_bytes(int n_groups, int64_t n_elem) {
+  if (n_groups <= 0 || n_elem <= 0) return 0;
+  return (size_t)n_groups * (size_t)nhmc_chain_diag_tiles(n_elem) * DIAG_WS * sizeof(double);
+}
+
+extern "C" int nhmc_chain_diag(const float* samples, float* rhat, float* ess, double* summary, double* ws, int n_groups,
+                               int n_replicas, int n_samples, int64_t n_elem, double rhat_threshold, nhmc_stream_t stream) {
+  if (!samples || !rhat || !ess || !summary || !ws || n_groups <= 0 || n_replicas <= 0 || n_samples <= 0 || n_elem <= 0)
+    return NHMC_ERR_ARG;
+  if ((n_elem & 3) || !nhmc_aligned16(samples) || !nhmc_aligned16(rhat) || !nhmc_aligned16(ess)) return NHMC_ERR_ALIGN;
+  const int n = n_samples / 2;
+  const int tiles = nhmc_chain_diag_tiles(n_elem);
+  if (n_samples < 4 || n > 32 || (int64_t)n_replicas * n_samples > 4096 || n_groups > 65535 || tiles <= 0)
+    return NHMC_ERR_SHAPE;
+  const dim3 grid((unsigned)tiles, (unsigned)n_groups);
+#define NHMC_DIAG(NMAX)                                                                                             \
+  NHMC_LAUNCH(k_chain_diag<NMAX>, grid, dim3(NHMC_BLOCK), 0, nhmc_s(stream), samples, rhat, ess, ws, n_replicas, \
+              n_samples, n, n_elem, rhat_threshold)
+  if (n <= 4) NHMC_DIAG(4);
+  else if (n <= 10) NHMC_DIAG(10);
+  else if (n <= 16) NHMC_DIAG(16);
+  else NHMC_DIAG(32);
+#undef NHMC_DIAG
+  NHMC_LAUNCH(k_chain_diag_final, wave_grid(n_groups), dim3(256), 0, nhmc_s(stream), ws, tiles, n_elem, summary, n_groups);
   return nhmc_launch_status();
 }

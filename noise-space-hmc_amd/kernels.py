@@ -1166,6 +1166,25 @@ def std_map_normalise(std_map, minmax):
     return out
 
 
+def chain_diag(samples, n_replicas, rhat_threshold=1.1):
+    """Split R-hat and ESS per element over the replicas of every image (nhmc.h "Convergence of replica chains").
+    samples [G * n_replicas, S, C, H, W], chain g * n_replicas + r being replica r of image g
+    -> (rhat [G, C, H, W], ess [G, C, H, W] float32, summary [G, 6] float64)."""
+    lib = _lib.load()
+    B, S, Cc, H, W = _sample_block(samples)
+    K = int(n_replicas)
+    if K < 1 or B % K:
+        raise _lib.NhmcError(f'chain_diag: {B} chains are not a multiple of {n_replicas} replicas')
+    G, N, dev = B // K, Cc * H * W, samples.device
+    rhat = torch.empty((G, Cc, H, W), dtype=torch.float32, device=dev)
+    ess = torch.empty((G, Cc, H, W), dtype=torch.float32, device=dev)
+    summary = torch.empty((G, 6), dtype=torch.float64, device=dev)
+    ws = torch.empty(lib.nhmc_chain_diag_ws_bytes(G, N) // 8, dtype=torch.float64, device=dev)
+    _lib.check(lib.nhmc_chain_diag(_p(samples, torch.float32, 'samples'), _p(rhat), _p(ess), _p(summary), _p(ws), G, K, S, N,
+                                   float(rhat_threshold), _stream()), 'nhmc_chain_diag')
+    return rhat, ess, summary
+
+
 # ---- a1 -------------------------------------------------------------------------------------
 def randn_philox(shape, seed, chain_id0, draw, scale=1.0, device='cuda', out=None):
     lib = _lib.load()

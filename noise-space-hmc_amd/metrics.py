@@ -6,6 +6,11 @@ on the device.
     sample_moments(samples)          posterior-mean image, per-pixel std map, its min-max normalised picture (:494-497)
     summarize(samples, x_orig)       per-chain means and ddof=1 stds (:526-538) + the maps, one device->host read
     save_std_map(map01, path)        the `std_dev_map_{idx}.png` picture (:499-507)
+    convergence(samples, replicas)   split R-hat and ESS per element over an image's replica chains, with summaries
+    save_rhat_map(rhat, path)        the `rhat_map_{idx}.png` picture
+
+With K replica chains per image (not in the reference, which runs one chain) the block is [G * K, S, C, H, W], chain
+g * K + r being replica r of image g, and `summarize(..., replicas=K)` pools an image's K * S samples.
 
 `samples` is what `sampler.hmc` returns for B chains, float32 [B, S, C, H, W] in [-1, 1], with `x_orig` [B, C, H, W]; one
 chain may be passed as [S, C, H, W] with a [1, C, H, W] (or [C, H, W]) original.  The kernels (csrc/metrics.hip) apply the
@@ -65,31 +70,79 @@ def _moments(samples):
     return mean, std_map, minmax, K.std_map_normalise(std_map, minmax), squeeze
 
 
-def summarize(samples, x_orig):
+CONVERGENCE_KEYS = ('rhat_max', 'rhat_mean', 'rhat_frac_above', 'ess_min', 'ess_mean', 'n_constant')
+
+
+def convergence(samples, replicas, rhat_threshold=1.1):
+    """Split R-hat and effective sample size per element over the `replicas` chains of every image (the definition is
+    in include/nhmc.h).  samples [G * K, S, C, H, W] with 4 <= S <= 65 -> dict: rhat, ess (device, float32 [G, C, H, W];
+    NaN where the element is constant, rhat +inf where the chains sit at different constants) and CONVERGENCE_KEYS as
+    float64 numpy [G], with one device->host read."""
+    samples, _, _ = _block(samples)
+    rhat, ess, summary = K.chain_diag(samples, replicas, rhat_threshold)
+    host = summary.cpu().numpy()
+    return dict(rhat=rhat, ess=ess, **{k: host[:, i].copy() for i, k in enumerate(CONVERGENCE_KEYS)})
+
+
+def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1):
     """Everything the report prints or saves for B chains with S samples each, with one device->host read.
 
     -> dict of float64 numpy arrays [B]: psnr_mean, psnr_std, ssim_mean, ssim_std (np.mean / np.std(ddof=1) over the
     chain's samples, :526-538; std is 0 for S = 1), std_map_min, std_map_max; `n_samples` (int); and the device tensors
     mean [B, C, H, W], std_map, std_map_normalised [B, H, W].  S = 1: PSNR and SSIM but no map (the reference's
     `len(xt) > 1`): the three tensors are None and the map's min / max NaN.  S = 0: all scalars NaN but the stds, which
-    are 0 -- the CLI's row for a chain whose final phase collected nothing."""
+    are 0 -- the CLI's row for a chain whose final phase collected nothing.
+
+    replicas = K > 1: samples is [G * K, S, C, H, W] (chain g * K + r is replica r of image g) and x_orig [G, C, H, W].
+    Everything above is then per image over its K * S pooled samples (`n_samples` = K * S; the block is contiguous, so
+    pooling is a view), and the dict gains `replicas`, CONVERGENCE_KEYS as float64 numpy [G] and the device maps `rhat`,
+    `ess` [G, C, H, W].  With S < 4 split R-hat is undefined: the summaries are NaN and the two maps None."""
+    replicas = int(replicas)
+    if replicas == 1:
+        return _summarize(samples, x_orig)
+    samples, x_orig, _ = _block(samples, x_orig)
+    B, S = samples.shape[:2]
+    if replicas < 1 or B % replicas:
+        raise _lib.NhmcError(f'summarize: {B} chains are not a multiple of {replicas} replicas')
+    G = B // replicas
+    diag = K.chain_diag(samples, replicas, rhat_threshold) if S >= 4 else None
+    out = _summarize(samples.reshape((G, replicas * S) + tuple(samples.shape[2:])), x_orig,
+                     extra=None if diag is None else diag[2])
+    conv = out.pop('extra', None)
+    out['replicas'] = replicas
+    out['rhat'], out['ess'] = (None, None) if diag is None else diag[:2]
+    for i, k in enumerate(CONVERGENCE_KEYS):
+        out[k] = np.full(G, np.nan) if conv is None else conv[:, i].copy()
+    return out
+
+
+def _summarize(samples, x_orig, extra=None):
+    """`summarize` for one replica per image; `extra` (float64 [B, n] on the device) rides along in the one read and
+    comes back as out['extra']."""
     samples, x_orig, _ = _block(samples, x_orig)
     B, S = samples.shape[:2]
     nan, zero = np.full(B, np.nan), np.zeros(B)
     out = dict(psnr_mean=nan, psnr_std=zero, ssim_mean=nan.copy(), ssim_std=zero.copy(), std_map_min=nan.copy(),
                std_map_max=nan.copy(), n_samples=S, mean=None, std_map=None, std_map_normalised=None)
+    if extra is not None:
+        out['extra'] = None
     if S == 0:
         return out
     cols = [psnr(samples, x_orig).double(), ssim(samples, x_orig)]
     if S > 1:
         out['mean'], out['std_map'], minmax, out['std_map_normalised'], _ = _moments(samples)
         cols.append(minmax.double())
-    host = torch.cat(cols, dim=1).cpu().numpy()                              # the one read: [B, 2S (+2)]
+    n_own = sum(c.shape[1] for c in cols)
+    if extra is not None:
+        cols.append(extra)
+    host = torch.cat(cols, dim=1).cpu().numpy()                              # the one read: [B, 2S (+2) (+n)]
     ps, ss = host[:, :S], host[:, S:2 * S]
     out['psnr_mean'], out['ssim_mean'] = ps.mean(axis=1), ss.mean(axis=1)
     if S > 1:
         out['psnr_std'], out['ssim_std'] = ps.std(axis=1, ddof=1), ss.std(axis=1, ddof=1)
         out['std_map_min'], out['std_map_max'] = host[:, 2 * S], host[:, 2 * S + 1]
+    if extra is not None:
+        out['extra'] = host[:, n_own:]
     return out
 
 
@@ -113,5 +166,20 @@ def save_std_map(map01, path):
     from PIL import Image
     if isinstance(map01, torch.Tensor):
         map01 = map01.detach().cpu().numpy()
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    Image.fromarray(hot_colours(map01)).save(path)
+
+
+def save_rhat_map(rhat, path):
+    """The R-hat map of one image, [C, H, W] (or [H, W]), as an 8-bit PNG in the `hot` colours: the maximum over the
+    channels, mapped clip((r - 1) / 0.5, 0, 1) -- black at R-hat <= 1, white from 1.5.  A constant element (NaN) maps to 0,
+    chains stuck at different constants (+inf) to 1."""
+    from PIL import Image
+    if isinstance(rhat, torch.Tensor):
+        rhat = rhat.detach().cpu().numpy()
+    r = np.asarray(rhat, dtype=np.float64)
+    if r.ndim == 3:
+        r = np.fmax.reduce(r, axis=0)                                        # the maximum that ignores NaN
+    map01 = np.clip((np.nan_to_num(r, nan=1.0, posinf=np.inf) - 1.0) / 0.5, 0.0, 1.0)
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
     Image.fromarray(hot_colours(map01)).save(path)
