@@ -691,13 +691,20 @@ def hmc_latent_chains(x, seq, seq_next, algo, opt, y_0, H_funcs, x_orig=None, *,
         K.latent_commit(accept, st, final, sampling, x, out['x_prop'], xt_last, out['xt'], ring)
         K.schedule_end_latent(accept, st, sig_next, final)
     count = st['count'].cpu().tolist()
-    samples = []
-    for c in range(B):                                                       # last `sampling` pushes, oldest first
-        k = min(count[c], sampling)
-        order = [(count[c] - k + j) % sampling for j in range(k)]
-        samples.append(ring[c, order])
+    samples = ring_samples(ring, count, sampling)
     return SimpleNamespace(samples=samples, x=x, n_accept=st['n_accept'], count=count, trace=trace, xt=xt_last, L=L,
                            ladders=engine.n_ladders, chain_ladders=engine.n_chain_ladders)
+
+
+def ring_samples(ring, count, keep):
+    """Read-out of the latent sampler's per-chain sample rings: ring [B, keep, ...] where push i of a chain went to slot
+    i % keep, count[c] pushes so far.  -> per chain its last min(count[c], keep) pushes, oldest first."""
+    samples = []
+    for c in range(ring.shape[0]):
+        k = min(count[c], keep)
+        order = [(count[c] - k + j) % keep for j in range(k)]
+        samples.append(ring[c, order])
+    return samples
 
 
 def hmc_latent(x, n, seq, seq_next, algo, opt, y_0, H_funcs, x_orig):

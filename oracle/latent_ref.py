@@ -79,6 +79,8 @@ def hmc_latent_reference(x, seq, seq_next, model, Hop, y_0, x_orig, *, sigma_y, 
             trace.setdefault('accept', []).append(bool(accept))
             trace.setdefault('sigma_y', []).append(float(sigma_y))
             trace.setdefault('eps', []).append(float(epsilon))
+            trace.setdefault('x_prop', []).append(xp.detach().clone())      # the proposal and its decode (state_ref.LatentBook)
+            trace.setdefault('xt_prop', []).append(xt.clone())
         if accept:
             rejected = 0
             if epoch < epochs:
@@ -122,6 +124,28 @@ def trajectory_latent(x, p, seq, seq_next, model, Hop, y_0, *, sigma_y, eps, m, 
     return dict(x=xp, p=p, xt=xt, loss=loss_b, H0=H0, H1=H1)
 
 
+class F64Latent(torch.nn.Module):
+    """TinyLatentModel evaluated in fp64 and rounded to fp32 (see F64Score in oracle/tiny_score.py): removes the
+    CPU-vs-GPU convolution noise that a many-trajectory comparison would otherwise amplify."""
+
+    def __init__(self):
+        super().__init__()
+        self.m = TinyLatentModel().double()
+        self.alphas_cumprod = self.m.alphas_cumprod.float()
+        self.alphas_cumprod_prev = self.m.alphas_cumprod_prev.float()
+
+    def to(self, dev):
+        self.m = self.m.to(dev)
+        self.alphas_cumprod, self.alphas_cumprod_prev = self.alphas_cumprod.to(dev), self.alphas_cumprod_prev.to(dev)
+        return self
+
+    def apply_model(self, x, t, cond=None):
+        return self.m.apply_model(x.double(), t.double(), cond).float()
+
+    def differentiable_decode_first_stage(self, z):
+        return self.m.differentiable_decode_first_stage(z.double()).float()
+
+
 class TinyLatentModel(torch.nn.Module):
     """Duck-typed stand-in for the LatentDiffusion object (its real class needs pytorch_lightning + taming,
     absent offline): a tiny score network on the latent and a tiny x4 decoder, seeded weights."""
@@ -148,3 +172,22 @@ class TinyLatentModel(torch.nn.Module):
     def differentiable_decode_first_stage(self, z):
         h = torch.nn.functional.interpolate(z, scale_factor=4, mode='nearest')
         return torch.tanh(self.up2(torch.tanh(self.up1(h))))
+
+
+class PointwiseLatent(torch.nn.Module):
+    """Batch-invariant stand-in for the latent model: the pointwise score of oracle.tiny_score.PointwiseScore and a
+    decoder of nearest x4 upsampling followed by a pointwise tanh; the LDM "linear" alpha tables of TinyLatentModel."""
+
+    def __init__(self, steps=1000):
+        super().__init__()
+        betas = torch.linspace(0.0015 ** 0.5, 0.0195 ** 0.5, steps, dtype=torch.float64) ** 2
+        ac = torch.cumprod(1 - betas, dim=0)
+        self.register_buffer('alphas_cumprod', ac.float())
+        self.register_buffer('alphas_cumprod_prev', torch.cat([torch.ones(1, dtype=torch.float64), ac[:-1]]).float())
+
+    def apply_model(self, x, t, cond=None):
+        return torch.tanh(x * 0.7) * (0.5 + (t / 1000.0).view(-1, 1, 1, 1))
+
+    def differentiable_decode_first_stage(self, z):
+        return torch.tanh(torch.nn.functional.interpolate(z, scale_factor=4, mode='nearest') * 0.9)
+

@@ -97,4 +97,6 @@ def hmc_mass_reference(x, b, seq, seq_next, model, Hop, y_0, x_orig, *, tau, eps
             if rejected >= 2:
                 tau = tau * 0.95
                 epsilon = epsilon * 0.95
+    if trace is not None:
+        trace['x'] = x.detach().clone()                 # where the chain ended
     return torch.stack(finals)

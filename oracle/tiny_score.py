@@ -106,3 +106,14 @@ class GridF64Score(nn.Module):
 
     def forward(self, x, t):
         return _GridNet.apply(x, t, self.net, self.bits, self.absolute)
+
+
+class PointwiseScore(nn.Module):
+    """Stand-in score with no cross-sample and no cross-pixel operation: bitwise batch-invariant, so a chain's run
+    through it can be compared bit for bit between batch sizes (learn_sigma layout: 2C output channels)."""
+
+    def forward(self, x, t):
+        a = (t / 1000.0).view(-1, 1, 1, 1)
+        e = torch.tanh(x * 0.7) * (0.5 + a)
+        return torch.cat([e, torch.zeros_like(e)], dim=1)
+

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import latent_ref, operators as oops
+from oracle.latent_ref import F64Latent
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
@@ -16,28 +17,6 @@ SEQ, SEQ_NEXT = [250, 500, 750], [-1, 250, 500]
 def rel(a, b):
     a, b = a.double().cpu(), b.double().cpu()
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
-
-
-class F64Latent(torch.nn.Module):
-    """TinyLatentModel evaluated in fp64 and rounded to fp32 (see F64Score in test_sampler_gpu.py): removes the
-    CPU-vs-GPU convolution noise that a 70-trajectory comparison would otherwise amplify."""
-
-    def __init__(self):
-        super().__init__()
-        self.m = latent_ref.TinyLatentModel().double()
-        self.alphas_cumprod = self.m.alphas_cumprod.float()
-        self.alphas_cumprod_prev = self.m.alphas_cumprod_prev.float()
-
-    def to(self, dev):
-        self.m = self.m.to(dev)
-        self.alphas_cumprod, self.alphas_cumprod_prev = self.alphas_cumprod.to(dev), self.alphas_cumprod_prev.to(dev)
-        return self
-
-    def apply_model(self, x, t, cond=None):
-        return self.m.apply_model(x.double(), t.double(), cond).float()
-
-    def differentiable_decode_first_stage(self, z):
-        return self.m.differentiable_decode_first_stage(z.double()).float()
 
 
 def test_first_latent_trajectory_of_the_reference_run(golden):
@@ -95,3 +74,73 @@ def test_latent_loop_takes_the_oracles_decisions():
                              types.SimpleNamespace(**vars(opt), noise_source=sampler.TapeNoise(lambda it: P[it], lambda it: U[it])),
                              y.to(dev), op, x_orig.to(dev))
     assert torch.equal(out, res.samples[0])
+
+
+def test_latent_loop_with_several_chains_takes_each_oracle_runs_decisions():
+    """Five chains in one call, each with its own problem and tape, against five batch-1 oracle runs (epochs 10, sampling
+    3): decisions, per-epoch sigma_y / eps, ragged sample counts and the returned latents per chain.  Measured on the CPU
+    where the chains were chosen: final-phase accepts 0, 4, 1, 5, 3 (an empty result, a wrapped ring, a ragged count, an
+    exactly full ring), smallest margins 0.117, 0.067, 0.245, 0.020, 0.065; chain 0 also ends with a shrunk eps."""
+    from nhmc import operators, plugin, sampler
+    from oracle import chain_cases as cc
+    chains, keep, o = cc.LATENT_CHAINS, cc.LATENT_SAMPLING, cc.LATENT_OPT
+    cases = [cc.latent_chain(c) for c in chains]
+    for c, k in zip(chains, cases):
+        print(f'latent chain {c}: final-phase accepts {k.final_accepts}, accepts {sum(k.trace["accept"])}, '
+              f'min margin {min(k.margins):.4f}, last eps {k.trace["eps"][-1]:.6f}')
+    # from the oracle traces alone: no decision of these inputs is inside the band the comparison excuses ...
+    assert all(min(k.margins) >= 5e-3 for k in cases)
+    # ... and the bookkeeping branches are there
+    counts = [k.final_accepts for k in cases]
+    assert len(set(counts)) > 1 and 0 in counts and max(counts) > keep
+    assert any(e not in (o['epsilon'], 0.01) for k in cases for e in k.trace['eps'])          # a chain shrank eps
+    dev = torch.device('cuda')
+    op = operators.Inpainting(3, 64, cc.latent_mask(), dev)
+    algo = plugin.HMCLatent(F64Latent().to(dev), op, o['sigma_0'])
+    opt = types.SimpleNamespace(**o)
+    x, y, x_orig = (torch.cat([getattr(k, a) for k in cases]).to(dev) for a in ('x', 'y', 'x_orig'))
+    tape = sampler.TapeNoise(lambda it: torch.cat([k.P[it] for k in cases]), lambda it: torch.cat([k.U[it] for k in cases]))
+    res = sampler.hmc_latent_chains(x, SEQ, SEQ_NEXT, algo, opt, y, op, x_orig, noise=tape, epochs=cc.LATENT_EPOCHS,
+                                    sampling=keep, collect_trace=True)
+    n_accept = res.n_accept.cpu().tolist()
+    for j, (c, k) in enumerate(zip(chains, cases)):
+        got_acc = [bool(r['accept'][j]) for r in res.trace]
+        for it, (a, b) in enumerate(zip(k.trace['accept'], got_acc)):
+            assert a == b or k.margins[it] < 1e-3, (c, it, a, b, k.margins[it])
+        assert [float(r['sigma_y'][j]) for r in res.trace] == k.trace['sigma_y'], c
+        assert [float(r['eps'][j]) for r in res.trace] == k.trace['eps'], c
+        assert res.count[j] == k.final_accepts and n_accept[j] == sum(k.trace['accept']), c
+        assert res.samples[j].shape == k.want.shape, (c, res.samples[j].shape)
+        if k.final_accepts:
+            err = rel(res.samples[j], k.want)
+            print(f'latent chain {c}: returned latents rel err {err:.2e}')
+            assert err < 1e-4, c
+
+
+def test_latent_chain_does_not_depend_on_its_neighbours():
+    """A B = 4 call equals four B = 1 calls on the same per-chain tapes, bit for bit (batch-invariant stand-in model)."""
+    from nhmc import operators, plugin, sampler
+    dev = torch.device('cuda')
+    g_ = torch.Generator().manual_seed(61)
+    B, dim, epochs, keep = 4, 8, 6, 3
+    op = operators.Inpainting(3, 4 * dim, oops.random_inpaint_missing(4 * dim, generator=g_), dev)
+    algo = plugin.HMCLatent(latent_ref.PointwiseLatent().to(dev), op, 0.1)
+    x = torch.randn(B, 3, dim, dim, generator=g_).to(dev)
+    y = (torch.randn(B, op.M, generator=g_) * 0.5).to(dev)
+    P = [torch.randn(B, 3, dim, dim, generator=g_) for _ in range(epochs + 2 * keep)]
+    U = [torch.rand(B, generator=g_) for _ in range(epochs + 2 * keep)]
+    opt = types.SimpleNamespace(tau=0.3, epsilon=0.1, m=1.0, sigma_0=0.1, sigma_y=0.5)
+
+    def run(lo, hi):
+        tape = sampler.TapeNoise(lambda it: P[it][lo:hi], lambda it: U[it][lo:hi])
+        return sampler.hmc_latent_chains(x[lo:hi], SEQ, SEQ_NEXT, algo, opt, y[lo:hi], op, noise=tape, epochs=epochs,
+                                         sampling=keep)
+
+    full = run(0, B)
+    print('neighbour test, latent: counts', full.count, 'accepts', full.n_accept.cpu().tolist())
+    assert int(full.n_accept.sum()) > 0
+    for c in range(B):
+        one = run(c, c + 1)
+        assert one.count[0] == full.count[c] and int(one.n_accept[0]) == int(full.n_accept[c]), c
+        assert torch.equal(one.x[0], full.x[c]) and torch.equal(one.xt[0], full.xt[c]), c
+        assert one.samples[0].shape == full.samples[c].shape and torch.equal(one.samples[0], full.samples[c]), c

@@ -155,3 +155,84 @@ def test_mass_loop_takes_the_oracles_decisions(tiny_score):
     err = rel(res.samples[0], want)
     print(f'mass loop: returned samples rel err {err:.2e}')
     assert res.samples.shape[1] == 35 and err < 1e-3
+
+
+def test_mass_loop_with_several_chains_takes_each_oracle_runs_decisions():
+    """Three chains in one call, each with its own problem and tape, against three batch-1 oracle runs (burn 2, epochs 9,
+    sampling 2: 19 epochs, 8 returned images).  The chains finish at different iterations (71, 75, 80 where they were
+    chosen, smallest margins 0.0155, 0.0105, 0.0056); past its own end a chain is handed non-zero momentum and u = 0,
+    which a missing `active` guard would accept."""
+    from nhmc import operators, plugin, sampler
+    from oracle import chain_cases as cc
+    chains = cc.MASS_CHAINS
+    cases = [cc.mass_chain(c) for c in chains]
+    for c, k in zip(chains, cases):
+        print(f'mass chain {c}: {k.iters} trajectories, {sum(k.trace["accept"])} accepts, min margin {min(k.margins):.4f}')
+    assert all(min(k.margins) >= 5e-3 for k in cases)                     # no decision of these inputs is excused below
+    assert len({k.iters for k in cases}) == len(cases)                    # the chains finish at different iterations
+    total = cc.MASS_BURN + cc.MASS_EPOCHS + 4 * cc.MASS_SAMPLING
+    n = max(k.iters for k in cases)
+    pad = torch.Generator().manual_seed(78)
+    P = [torch.cat([k.P[it] if it < k.iters else torch.randn(1, 3, cc.MASS_DIM, cc.MASS_DIM, generator=pad) for k in cases])
+         for it in range(n)]
+    U = [torch.tensor([float(k.U[it]) if it < k.iters else 0.0 for k in cases]) for it in range(n)]
+    dev = torch.device('cuda')
+    op = operators.Inpainting(3, cc.MASS_DIM, cc.mass_mask(), dev)
+    algo = plugin.HMC(cc.mass_score().to(dev), op, cc.MASS_OPT['sigma_0'])
+    opt = types.SimpleNamespace(**cc.MASS_OPT)
+    x, y, x_orig = (torch.cat([getattr(k, a) for k in cases]).to(dev) for a in ('x', 'y', 'x_orig'))
+    res = sampler.hmc_mass_chains(x, osched.betas_fp32().to(dev), SEQ, SEQ_NEXT, algo, opt, y, op, x_orig,
+                                  noise=sampler.TapeNoise(lambda it: P[it], lambda it: U[it]), burn=cc.MASS_BURN,
+                                  epochs=cc.MASS_EPOCHS, sampling=cc.MASS_SAMPLING, collect_trace=True, max_iters=n)
+    assert res.iters == n
+    epoch, n_accept, n_reject = (v.cpu().tolist() for v in (res.epoch, res.n_accept, res.n_reject))
+    for j, (c, k) in enumerate(zip(chains, cases)):
+        for it, rec in enumerate(res.trace):
+            if it < k.iters:
+                a, b = k.trace['accept'][it], bool(rec['accept'][j])
+                assert a == b or k.margins[it] < 1e-3, (c, it, a, b, k.margins[it])
+                assert int(rec['epoch'][j]) == k.trace['epoch'][it], (c, it)
+            else:                                                          # finished: frozen whatever it is handed
+                assert not bool(rec['accept'][j]) and int(rec['epoch'][j]) == total, (c, it)
+        acc = sum(k.trace['accept'])
+        assert epoch[j] == total and n_accept[j] == acc and n_reject[j] == k.iters - acc, c
+        err, err_x = rel(res.samples[j], k.want), rel(res.x[j], k.trace['x'][0])
+        print(f'mass chain {c}: returned samples rel err {err:.2e}, final position rel err {err_x:.2e}')
+        assert res.samples[j].shape == k.want.shape and err < 1e-3 and err_x < 1e-3, c
+
+
+def test_mass_chain_does_not_depend_on_its_neighbours():
+    """A B = 4 call, ragged in iteration count, equals four B = 1 calls on the same per-chain tapes, bit for bit
+    (batch-invariant stand-in score).  Past its own end a chain of the batch gets u = 0 and keeps getting momentum."""
+    from nhmc import operators, plugin, sampler
+    from oracle.tiny_score import PointwiseScore
+    dev = torch.device('cuda')
+    B, dim, cap = 4, 16, 96
+    kw = dict(burn=2, epochs=9, sampling=2)
+    total = 2 + 9 + 4 * 2
+    op = operators.build_operator('inpaint_random', 3, dim, dev, generator=torch.Generator().manual_seed(24))
+    algo = plugin.HMC(PointwiseScore().to(dev), op, 0.1)
+    b = osched.betas_fp32().to(dev)
+    g_ = torch.Generator().manual_seed(62)
+    x = torch.randn(B, 3, dim, dim, generator=g_).to(dev)
+    x_orig = (torch.rand(B, 3, dim, dim, generator=g_) * 2 - 1).to(dev)
+    y = op.H(x_orig) + 0.1 * torch.randn(B, op.M, generator=g_).to(dev)
+    P = [torch.randn(B, 3, dim, dim, generator=g_) for _ in range(cap)]
+    U = [torch.rand(B, generator=g_) for _ in range(cap)]
+    opt = types.SimpleNamespace(tau=0.2, epsilon=0.05, sigma_0=0.1)
+    ones = [sampler.hmc_mass_chains(x[c:c + 1], b, SEQ, SEQ_NEXT, algo, opt, y[c:c + 1], op, x_orig[c:c + 1], max_iters=cap,
+                                    noise=sampler.TapeNoise(lambda it, c=c: P[it][c:c + 1], lambda it, c=c: U[it][c:c + 1]), **kw)
+            for c in range(B)]
+    iters = [r.iters for r in ones]
+    print('neighbour test, mass: trajectories per chain', iters, 'epochs', [int(r.epoch[0]) for r in ones])
+    assert all(int(r.epoch[0]) == total for r in ones) and len(set(iters)) > 1          # all finished, at different iterations
+    n = max(iters)
+    ends = torch.tensor(iters)
+    full = sampler.hmc_mass_chains(x, b, SEQ, SEQ_NEXT, algo, opt, y, op, x_orig, max_iters=n,
+                                   noise=sampler.TapeNoise(lambda it: P[it], lambda it: torch.where(it < ends, U[it], torch.zeros(B))),
+                                   **kw)
+    assert full.iters == n
+    for c, one in enumerate(ones):
+        for k in ('epoch', 'n_accept', 'n_reject'):
+            assert int(getattr(one, k)[0]) == int(getattr(full, k)[c]), (c, k)
+        assert torch.equal(one.x[0], full.x[c]) and torch.equal(one.samples[0], full.samples[c]), c

@@ -178,12 +178,7 @@ def test_reference_entry_point_shapes_and_shard_invariance():
     """hmc(...) keeps the reference's return shape at n = 1; with Philox noise a chain's result does not
     depend on which launch (shard) it ran in."""
     from nhmc import operators, plugin, sampler
-
-    class PointwiseScore(torch.nn.Module):           # no cross-sample / cross-pixel op: bitwise batch-invariant
-        def forward(self, x, t):
-            a = (t / 1000.0).view(-1, 1, 1, 1)
-            e = torch.tanh(x * 0.7) * (0.5 + a)
-            return torch.cat([e, torch.zeros_like(e)], dim=1)
+    from oracle.tiny_score import PointwiseScore       # no cross-sample / cross-pixel op: bitwise batch-invariant
 
     dim = 16
     dev = torch.device('cuda')
