@@ -107,6 +107,8 @@ class LeapfrogEngine:
         self.update_events = None              # bench: list collecting (start, end, chains) event pairs of each update launch
         self.n_ladders = 0                     # decode + gradient ladders launched (one per chunk) ...
         self.n_chain_ladders = 0               # ... and the chains they carried (score evaluations = n_steps x this)
+        self.graphs_captured = 0               # hipGraphs captured so far ...
+        self.graphs_live_max = 0               # ... and the most that were alive at once (see `retain_chunks_of`)
         steps = list(zip(reversed(seq), reversed(seq_next)))
         from .schedule import alpha_bar_table
         table = alpha_table.to(device).float() if alpha_table is not None else alpha_bar_table(b)
@@ -129,6 +131,24 @@ class LeapfrogEngine:
     def _chunks(self, B):
         c = self.chunk or B
         return [(s, min(B, s + c)) for s in range(0, B, c)]
+
+    def retain_chunks_of(self, B):
+        """Forget everything kept per chunk size that a batch of B chains cannot use: the captured graphs (each pins the
+        score network's autograd state of one chunk in a private pool), the persistent g_e buffers and the per-chain
+        tables they replay on.  hmc_chains calls this when compaction shrinks the batch, BEFORE the next capture, so the
+        larger graphs' pools are free when the smaller graph is captured."""
+        keep = {hi - lo for lo, hi in self._chunks(B)}
+        stale = [k for k in self._graphs if k[0][0] not in keep]
+        if stale:
+            torch.cuda.current_stream().synchronize()            # the last replay of a dropped graph has finished
+        for k in stale:
+            del self._graphs[k]
+        self._ge = {k: v for k, v in self._ge.items() if k[0] in keep}
+        self._per_n = {n: v for n, v in self._per_n.items() if n in keep}
+
+    def _count(self, n):
+        self.n_ladders += 1
+        self.n_chain_ladders += n
 
     def _out_buffers(self, x):
         """Batch-wide decode / loss buffers, kept per shape: the kernels of every chunk write their slice directly."""
@@ -215,13 +235,16 @@ class LeapfrogEngine:
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):                       # warm-up: solver selection, allocator pools
                 for _ in range(2):
-                    self._decode_and_grad_chunk(sx, sy, sxt, sloss)
+                    self._ladder(sx, sy, sxt, sloss)
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                grads = self._decode_and_grad_chunk(sx, sy, sxt, sloss)
+                grads = self._ladder(sx, sy, sxt, sloss)
             rec = self._graphs[key] = (g, sx, sy, sxt, sloss, grads)
+            self.graphs_captured += 1
+            self.graphs_live_max = max(self.graphs_live_max, len(self._graphs))
         g, sx, sy, sxt, sloss, grads = rec
+        self._count(x.shape[0])                                 # one ladder per replay; warm-ups and the capture are none
         sx.copy_(x)
         sy.copy_(y)
         g.replay()
@@ -231,12 +254,15 @@ class LeapfrogEngine:
         return grads                                            # the graph's own buffers: valid until its next replay
 
     def _decode_and_grad_chunk(self, x, y, xt_out, loss_out):
+        """One eager ladder: counted per call, as a replay of the captured one is in `_graphed_chunk`."""
+        self._count(x.shape[0])
+        return self._ladder(x, y, xt_out, loss_out)
+
+    def _ladder(self, x, y, xt_out, loss_out):
         """Writes the clipped decode and the per-chain loss of this chunk into xt_out / loss_out (views of the
         batch-wide buffers) and returns the chunk's gradient pieces (g_direct, g_score or None)."""
         n = x.shape[0]
         S = self.n_steps
-        self.n_ladders += 1
-        self.n_chain_ladders += n
         tab = self._tables(n)
         ins, outs = [], []
         cur = x
@@ -408,7 +434,10 @@ def hmc_chains(x, b, seq, seq_next, algo, opt, y_0, H_funcs, x_orig=None, *, noi
         n_accept, n_reject, epoch [B]    int32
         psnr    [B] or None              PSNR of the last accepted decode against x_orig
         iters   int                      trajectories run
-        ladders, chain_ladders           decode+gradient ladders launched / chains they carried (score calls = 3 x)
+        ladders, chain_ladders           decode+gradient ladders launched / chains they carried (score calls = 3 x);
+                                         under graph=True one per replay (warm-ups and captures are not counted)
+        graphs_captured, graphs_live_max hipGraphs captured over the run / most alive at once (graphs whose chunk size
+                                         the compacted batch cannot use are dropped before the next capture)
         chain_trajectories               sum over trajectories of the chains that ran it
         trace   list of dicts (dH, accept, epoch per iteration) when collect_trace
     """
@@ -495,6 +524,8 @@ def hmc_chains(x, b, seq, seq_next, algo, opt, y_0, H_funcs, x_orig=None, *, noi
             ids = [ids[s_] for s_ in order]
             ids_dev = torch.tensor(ids, device=device)
             n_run = want
+            if graph:
+                engine.retain_chunks_of(n_run)                              # before the smaller graphs are captured
     if ids_dev is not None:                                                 # back to the caller's chain order
         inv = torch.empty(B, dtype=torch.int64)
         inv[torch.tensor(ids)] = torch.arange(B)
@@ -506,7 +537,8 @@ def hmc_chains(x, b, seq, seq_next, algo, opt, y_0, H_funcs, x_orig=None, *, noi
     return SimpleNamespace(samples=samples, x=x, n_accept=state['n_accept'], n_reject=state['n_reject'],
                            epoch=state['epoch'], psnr=psnr, iters=it, trace=trace, xt=xt_last, L=L,
                            ladders=engine.n_ladders, chain_ladders=engine.n_chain_ladders,
-                           chain_trajectories=chain_trajectories)
+                           chain_trajectories=chain_trajectories, graphs_captured=engine.graphs_captured,
+                           graphs_live_max=engine.graphs_live_max)
 
 
 def hmc(x, n, b, seq, seq_next, algo, opt, y_0, H_funcs, x_orig):
