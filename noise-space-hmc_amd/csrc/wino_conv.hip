@@ -2,17 +2,22 @@
 // per-frequency products on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact k-ascending fp32 FMA chains).
 //
 //   y[n,k,h,w] = sum_c sum_rs x[n,c,h+r-1,w+s-1] w[k,c,r,s]      NCHW fp32
-//   U = G w G^T   [16][C][K], built once per weight tensor by k_wino_weights (forward, or backward-data: the flipped,
+//   U = G w G^T   [C][K][16], built once per weight tensor by k_wino_weights (forward, or backward-data: the flipped,
 //                 transposed filter, so that dx = conv(dy, w') runs on the same kernel)
 //   V = B^T d B   from a halo patch of x, zero padding by predicate, staged in LDS per chunk of 8 channels (never in HBM)
 //   M_f[k, tile] += U_f[c, k] V_f[c, tile]   for f = 0..15, c ascending, no atomics: two runs give the same bits
 //   Y = A^T M A   in registers, stored as 256-byte row segments; optional epilogue (acc + bias[k]) + add, k_bias_add2's order
 //
+// Frequency index: f = 4 b + a, a the vertical and b the horizontal frequency, innermost in U and in both LDS operands.
+//
 // Workgroup: 256 threads own 64 output channels x 64 tiles (2 tile rows x 32 tile columns = 4 x 64 outputs) x 16 frequencies.
 // Wave (kh, th) holds channels 32 kh .. + 31 of tile row th for all 16 frequencies: 16 accumulator tiles = 256 registers,
 // one wave per SIMD; every lane has all 16 frequencies of its outputs, so the output transform needs no exchange.
-// LDS: two buffers of U[16][8][64] + V[16][8][64] = 128 KB.  While chunk i is multiplied, chunk i + 1 is loaded into
-// registers (first half of the chunk's MFMAs), transformed and written to the other buffer (second half).
+// LDS: two buffers of U[8][64][16] + V[8][64][16] = 128 KB: a row (c, k or tile) is the 16 frequencies = 64 bytes, so a
+// lane fetches the eight A or B values of one MFMA group with two ds_read_b128.  Rows of 64 bytes alone would put the 16
+// lanes of a b128 group on 4 of the 16 slots of a bank row; the 16-byte granule g of row R is stored at granule
+// g ^ ((R >> 2) & 3), which spreads every group over all 16.  While chunk i is multiplied, chunk i + 1 is loaded into
+// registers, transformed and written to the other buffer.
 #include "nhmc_common.h"
 
 namespace {
@@ -32,7 +37,7 @@ struct WinoArgs {
 };
 
 __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
-  extern __shared__ float lds[];
+  extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
   const int kh = wave & 1, th = wave >> 1;
   const int C = a.C, K = a.K, H = a.H, W = a.W, HW = H * W;
@@ -63,9 +68,11 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
     }
   }
   const float* xn = a.x + (int64_t)n * C * HW;
-  // U stage: 2048 float4 = rows (f, c) of 64 channels; thread takes float4 tid + 256 i: f = (tid >> 7) + 2 i, c = (tid >> 4) & 7
-  const float* ub = a.U + ((int64_t)(tid >> 7) * C + ((tid >> 4) & 7)) * K + kb * WC_KBLK + (tid & 15) * 4;
-  const int64_t ustep = (int64_t)2 * C * K;
+  // U stage: the chunk's 8 x 64 rows of this K block are 8 contiguous pieces of 4 KB; thread takes float4 tid of piece i
+  const char* un = reinterpret_cast<const char*>(a.U + (int64_t)kb * WC_KBLK * 16);
+  const unsigned uoff = 16u * tid;
+  const int uw = (tid & ~3) * 4 + (((tid & 3) ^ ((tid >> 4) & 3)) << 2);          // row tid >> 2, swizzled granule
+  const int vw = (lc * 64 + ltx) * 16, vswz = (ltx >> 2) & 3;
 
   float xr[6][4];
   nhmc_v4f ur[8];
@@ -75,12 +82,20 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
     for (int r = 0; r < 6; ++r)
 #pragma unroll
       for (int s = 0; s < 4; ++s) xr[r][s] = xs[voff[r][s]];
-    const float* us = ub + (int64_t)ch * WC_CHUNK * K;
+    const char* us = un + (int64_t)ch * WC_CHUNK * K * 64;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) ur[i] = *reinterpret_cast<const nhmc_v4f*>(us + i * ustep);
+    for (int i = 0; i < 8; ++i) ur[i] = *reinterpret_cast<const nhmc_v4f*>(us + (int64_t)i * K * 64 + uoff);
+  };
+  // the loaded patch is first touched here, three units after its loads were issued: without the pin the selects and the
+  // first-level differences of all four columns move to the head of the chunk, and the chunk starts with a wait on the loads
+  auto pin_patch = [&]() {
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(xr[r][s]));
   };
   auto d = [&](int r, int s) { return (okmask >> (r * 4 + s)) & 1u ? xr[r][s] : 0.0f; };
-  // column b of V = B^T d B for both tiles of the thread, and a quarter of the U stage -> LDS stage `st`
+  // column b of V = B^T d B for both tiles of the thread (one granule each), and a quarter of the U stage -> LDS stage `st`
   auto stage_part = [&](int st, int b) {
     float* Us = lds + st * 2 * WC_OPER;
     float* Vs = Us + WC_OPER;
@@ -91,15 +106,12 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
 #pragma unroll
     for (int ty = 0; ty < 2; ++ty) {
       const int r0 = 2 * ty;
-      const float v0 = e[r0] - e[r0 + 2], v1 = e[r0 + 1] + e[r0 + 2], v2 = e[r0 + 2] - e[r0 + 1], v3 = e[r0 + 1] - e[r0 + 3];
-      float* vp = Vs + lc * 64 + ty * 32 + ltx;
-      vp[(0 * 4 + b) * WC_CHUNK * 64] = v0;
-      vp[(1 * 4 + b) * WC_CHUNK * 64] = v1;
-      vp[(2 * 4 + b) * WC_CHUNK * 64] = v2;
-      vp[(3 * 4 + b) * WC_CHUNK * 64] = v3;
+      nhmc_v4f v;
+      v.x = e[r0] - e[r0 + 2]; v.y = e[r0 + 1] + e[r0 + 2]; v.z = e[r0 + 2] - e[r0 + 1]; v.w = e[r0 + 1] - e[r0 + 3];
+      *reinterpret_cast<nhmc_v4f*>(Vs + vw + ty * 32 * 16 + ((b ^ vswz) << 2)) = v;
     }
 #pragma unroll
-    for (int i = 2 * b; i < 2 * b + 2; ++i) *reinterpret_cast<nhmc_v4f*>(Us + (tid + 256 * i) * 4) = ur[i];
+    for (int i = 2 * b; i < 2 * b + 2; ++i) *reinterpret_cast<nhmc_v4f*>(Us + uw + 1024 * i) = ur[i];
   };
 
   f32x16 acc[16];
@@ -108,32 +120,29 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[f][r] = 0.0f;
 
-  // one chunk: 8 units of 8 MFMAs (k-step u / 2, frequencies 8 (u & 1) .. + 7); the operands of unit u + 1 are read from LDS
-  // before the MFMAs of unit u issue, and the following chunk is staged behind units 4 .. 7
-  const int aoff = lh * 64 + kh * 32 + lr, boff = lh * 64 + th * 32 + lr;
-  auto compute = [&](int st) {
-    const float* Us = lds + st * 2 * WC_OPER + aoff;
-    const float* Vs = lds + st * 2 * WC_OPER + WC_OPER + boff;
-    float av[2][8], bv[2][8];
-    auto fetch = [&](int u, float (&fa)[8], float (&fb)[8]) {
+  // one chunk: 8 units of 8 MFMAs (k-step u / 2, frequencies 8 (u & 1) .. + 7 = granules 2 (u & 1), + 1 of the lane's A and B
+  // rows); the operands of unit u + 1 are read from LDS before the MFMAs of unit u issue.  The following chunk is staged
+  // behind units 3 .. 6; the workgroup meets between units 6 and 7, when unit 7's operands are in registers, so that the
+  // first operands of the following chunk are read behind the MFMAs of unit 7 and no MFMA waits on the read before it
+  const int swz = (lr >> 2) & 3;
+  const int arow = (lh * 64 + kh * 32 + lr) * 16, brow = WC_OPER + (lh * 64 + th * 32 + lr) * 16;
+  float av[2][8], bv[2][8];
+  auto fetch = [&](int st, int u, float (&fa)[8], float (&fb)[8]) {
+    const float* S = lds + st * 2 * WC_OPER + (u >> 1) * 2 * 64 * 16;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int f = 8 * (u & 1) + j, o = (f * WC_CHUNK + 2 * (u >> 1)) * 64;
-        fa[j] = Us[o];
-        fb[j] = Vs[o];
-      }
-    };
-    fetch(0, av[0], bv[0]);
+    for (int g = 0; g < 2; ++g) {
+      const int go = ((2 * (u & 1) + g) ^ swz) << 2;
+      const nhmc_v4f va = *reinterpret_cast<const nhmc_v4f*>(S + arow + go);
+      const nhmc_v4f vb = *reinterpret_cast<const nhmc_v4f*>(S + brow + go);
+      fa[4 * g + 0] = va.x; fa[4 * g + 1] = va.y; fa[4 * g + 2] = va.z; fa[4 * g + 3] = va.w;
+      fb[4 * g + 0] = vb.x; fb[4 * g + 1] = vb.y; fb[4 * g + 2] = vb.z; fb[4 * g + 3] = vb.w;
+    }
+  };
+  auto unit = [&](int u) {
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      if (u + 1 < 8) fetch(u + 1, av[(u + 1) & 1], bv[(u + 1) & 1]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int f = 8 * (u & 1) + j;
-        acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u & 1][j], bv[u & 1][j], acc[f], 0, 0, 0);
-      }
-      if (u >= 4) stage_part(st ^ 1, u - 4);
+    for (int j = 0; j < 8; ++j) {
+      const int f = 8 * (u & 1) + j;
+      acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u & 1][j], bv[u & 1][j], acc[f], 0, 0, 0);
     }
   };
 
@@ -142,47 +151,77 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
 #pragma unroll
   for (int b = 0; b < 4; ++b) stage_part(0, b);
   __syncthreads();
+  issue_loads(1 < chunks ? 1 : 0);
+  fetch(0, 0, av[0], bv[0]);
   // ONE instance of the chunk body (a second one behind the loop made the register allocator shuffle the 256 accumulators
-  // through scratch): the last chunk stages itself once more into the idle buffer, which nobody reads.  do-while: the
-  // accumulators reach the epilogue from the loop only (C >= 8), not merged with their zero state
+  // through scratch): the last chunk stages itself once more into the idle buffer and reads unit 0 of it, which nobody
+  // uses.  do-while: the accumulators reach the epilogue from the loop only (C >= 8), not merged with their zero state
   int ch = 0, st = 0;
   do {
-    issue_loads(ch + 1 < chunks ? ch + 1 : ch);
-    __builtin_amdgcn_sched_barrier(0);
-    compute(st);
+#pragma unroll
+    for (int u = 0; u < 7; ++u) {
+      fetch(st, u + 1, av[(u + 1) & 1], bv[(u + 1) & 1]);
+      __builtin_amdgcn_sched_barrier(0);
+      unit(u);
+      if (u == 3) pin_patch();
+      if (u >= 3) stage_part(st ^ 1, u - 3);
+    }
     __syncthreads();                                // stage st ^ 1 is complete, and every wave is done reading stage st
     st ^= 1;
+    issue_loads(ch + 2 < chunks ? ch + 2 : chunks - 1);
+    fetch(st, 0, av[0], bv[0]);
+    __builtin_amdgcn_sched_barrier(0);
+    unit(7);
   } while (++ch < chunks);
 
-  // ---- Y = A^T M A per (channel, tile), epilogue, 256-byte row segments (32 lanes x float2)
+  // ---- Y = A^T M A per (channel, tile), epilogue, 256-byte row segments (32 lanes x float2).  bias and add are loaded
+  // for all 16 channels of the lane before the transform (the loaders' registers are free), behind one wait
   const int oh = h0 + 2 * th, ow = w0 + 2 * lr;
+  const bool has_bias = a.bias != nullptr, has_add = a.add != nullptr;
+  const int k0 = kb * WC_KBLK + kh * 32 + 4 * lh;
+  const int64_t at0 = (((int64_t)n * K + k0) * H + oh) * W + ow;
+  float bc[16];
+  wc_v2f ad[16][2];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int k = kb * WC_KBLK + kh * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+    bc[r] = 0.0f;
+    ad[r][0] = ad[r][1] = wc_v2f{0.0f, 0.0f};
+  }
+  if (has_bias) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) bc[r] = a.bias[k0 + (r & 3) + 8 * (r >> 2)];
+  }
+  if (has_add) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        ad[r][i] = *reinterpret_cast<const wc_v2f*>(a.add + at0 + (int64_t)((r & 3) + 8 * (r >> 2)) * HW + i * W);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
     float t[2][4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      t[0][b] = (acc[0 + b][r] + acc[4 + b][r]) + acc[8 + b][r];
-      t[1][b] = (acc[4 + b][r] - acc[8 + b][r]) - acc[12 + b][r];
+      t[0][b] = (acc[4 * b + 0][r] + acc[4 * b + 1][r]) + acc[4 * b + 2][r];
+      t[1][b] = (acc[4 * b + 1][r] - acc[4 * b + 2][r]) - acc[4 * b + 3][r];
     }
-    const float bc = a.bias ? a.bias[k] : 0.0f;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       wc_v2f o;
       o.x = (t[i][0] + t[i][1]) + t[i][2];
       o.y = (t[i][1] - t[i][2]) - t[i][3];
-      const int64_t at = (((int64_t)n * K + k) * H + oh + i) * W + ow;
-      if (a.bias) { o.x = o.x + bc; o.y = o.y + bc; }
-      if (a.add) {
-        const wc_v2f ad = *reinterpret_cast<const wc_v2f*>(a.add + at);
-        o.x = o.x + ad.x; o.y = o.y + ad.y;
-      }
-      __builtin_nontemporal_store(o, reinterpret_cast<wc_v2f*>(a.y + at));
+      o.x = has_bias ? o.x + bc[r] : o.x;
+      o.y = has_bias ? o.y + bc[r] : o.y;
+      o.x = has_add ? o.x + ad[r][i].x : o.x;
+      o.y = has_add ? o.y + ad[r][i].y : o.y;
+      __builtin_nontemporal_store(o, reinterpret_cast<wc_v2f*>(a.y + at0 + (int64_t)((r & 3) + 8 * (r >> 2)) * HW + i * W));
     }
   }
 }
 
-// U[f = 4 a + b][ci][ko] = (G g G^T)[a][b], G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1].
+// U[ci][ko][f = 4 b + a] = (G g G^T)[a][b], G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1].
 // forward: (ci, ko) = (c, k), g = w[k][c];  backward-data: (ci, ko) = (k, c), g[r][s] = w[k][c][2 - r][2 - s].
 __global__ __launch_bounds__(NHMC_BLOCK) void k_wino_weights(const float* __restrict__ w, float* __restrict__ U, int C, int K,
                                                              int backward) {
@@ -197,15 +236,16 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_wino_weights(const float* __rest
     const float g0 = g[backward ? 8 - s : s], g1 = g[backward ? 5 - s : 3 + s], g2 = g[backward ? 2 - s : 6 + s];
     t[0][s] = g0; t[1][s] = 0.5f * ((g0 + g1) + g2); t[2][s] = 0.5f * ((g0 - g1) + g2); t[3][s] = g2;
   }
-  const int64_t plane = (int64_t)CI * KO;
+  nhmc_v4f u[4];                                     // u[b] = the four vertical frequencies a of horizontal frequency b
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    float* u = U + (int64_t)(4 * r) * plane + idx;
-    u[0] = t[r][0];
-    u[plane] = 0.5f * ((t[r][0] + t[r][1]) + t[r][2]);
-    u[2 * plane] = 0.5f * ((t[r][0] - t[r][1]) + t[r][2]);
-    u[3 * plane] = t[r][2];
+    u[0][r] = t[r][0];
+    u[1][r] = 0.5f * ((t[r][0] + t[r][1]) + t[r][2]);
+    u[2][r] = 0.5f * ((t[r][0] - t[r][1]) + t[r][2]);
+    u[3][r] = t[r][2];
   }
+#pragma unroll
+  for (int b = 0; b < 4; ++b) reinterpret_cast<nhmc_v4f*>(U + (int64_t)idx * 16)[b] = u[b];
 }
 
 int wc_covers(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) {
