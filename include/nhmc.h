@@ -562,13 +562,21 @@ int nhmc_bias_add2(const float* h, const float* bias, const float* other, float*
  *   bytes: NHMC_ERR_ALIGN; all before any device work.
  * nhmc_conv3x3_wino_prefers(backward, n, c, k, h, w): 1 when this entry measured at most 0.90 of the vendor library's time
  *   for the shape and direction (c, k: the channels of the convolution that runs, i.e. of dy and dx for backward = 1);
- *   the table is next to its definition.  Only n = 64 was measured; other batch sizes follow the same (c, k, h, w) rows.
+ *   the table is next to its definition and says which rows are convolutions of unet.FFHQ_CONFIG (unet.conv3x3_shapes()).
+ *   Only n = 64 was measured; other batch sizes follow the same (c, k, h, w) rows.
+ * nhmc_conv3x3_wino_narrow, _narrow_covers, _narrow_prefers: the same kernel, arguments, validation order and results for
+ *   images 32 and 16 wide, which the entries above refuse: the workgroup's 64 tiles are 4 x 16 (w = 32, h % 8 == 0) or
+ *   8 x 8 (w = 16, h % 16 == 0) instead of 2 x 32.  Every other width is NHMC_ERR_SHAPE here.  u is shared with the wide entry.
  * ---------------------------------------------------------------------------------- */
 int nhmc_wino_weights(const float* weight, float* u, int backward, int channels_in, int channels_out, nhmc_stream_t stream);
 int nhmc_conv3x3_wino(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c, int k,
                       int h, int w, int stride, int padding, nhmc_stream_t stream);
 int nhmc_conv3x3_wino_covers(int n, int c, int k, int h, int w);
 int nhmc_conv3x3_wino_prefers(int backward, int n, int c, int k, int h, int w);
+int nhmc_conv3x3_wino_narrow(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c,
+                             int k, int h, int w, int stride, int padding, nhmc_stream_t stream);
+int nhmc_conv3x3_wino_narrow_covers(int n, int c, int k, int h, int w);
+int nhmc_conv3x3_wino_narrow_prefers(int backward, int n, int c, int k, int h, int w);
 
 /* PSNR of clamp((xt+1)/2,0,1) against clamp((x_orig+1)/2,0,1)   main_sampling.py:738-739
  * ws: double[n_chains][nhmc_data_tiles(n_elem)]. */

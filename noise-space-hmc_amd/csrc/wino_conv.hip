@@ -13,6 +13,10 @@
 // Workgroup: 256 threads own 64 output channels x 64 tiles (2 tile rows x 32 tile columns = 4 x 64 outputs) x 16 frequencies.
 // Wave (kh, th) holds channels 32 kh .. + 31 of tile row th for all 16 frequencies: 16 accumulator tiles = 256 registers,
 // one wave per SIMD; every lane has all 16 frequencies of its outputs, so the output transform needs no exchange.
+// The 64 tiles are 32 / TC pairs of tile rows x TC tile columns, TC a template parameter: 32 is the 4 x 64 block above,
+// 16 an 8 x 32 block (images 32 wide), 8 a 16 x 16 block (images 16 wide).  Tile t = 32 th + lr of the workgroup is tile row
+// 2 (lr / TC) + th, column lr % TC; only the loader's patch origin, the block origin and the epilogue's output origin
+// know TC, the LDS layout, the main loop and the accumulation order do not.
 // LDS: two buffers of U[8][64][16] + V[8][64][16] = 128 KB: a row (c, k or tile) is the 16 frequencies = 64 bytes, so a
 // lane fetches the eight A or B values of one MFMA group with two ds_read_b128.  Rows of 64 bytes alone would put the 16
 // lanes of a b128 group on 4 of the 16 slots of a bank row; the 16-byte granule g of row R is stored at granule
@@ -26,7 +30,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float wc_v2f __attribute__((ext_vector_type(2)));
 
 constexpr int WC_KBLK = 64;                      // output channels per workgroup
-constexpr int WC_ROWS = 4, WC_COLS = 64;         // output block: 2 x 32 tiles
+constexpr int WC_ROWS = 4, WC_COLS = 64;         // output block of the wide geometry (TC = 32): 2 x 32 tiles
 constexpr int WC_CHUNK = 8;                      // input channels per LDS stage
 constexpr int WC_OPER = 16 * WC_CHUNK * 64;      // floats of one operand (U or V) of one stage
 constexpr int WC_LDS_BYTES = 4 * WC_OPER * 4;    // 2 stages x (U + V)
@@ -36,7 +40,10 @@ struct WinoArgs {
   int C, K, H, W, row_blocks, col_blocks;
 };
 
+template <int TC>
 __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
+  static_assert(TC == 32 || TC == 16 || TC == 8, "64 tiles as 32 / TC row pairs x TC columns");
+  constexpr int BLK_ROWS = 128 / TC, BLK_COLS = 2 * TC;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
   const int kh = wave & 1, th = wave >> 1;
@@ -49,19 +56,20 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
   const int kblocks = K / WC_KBLK;
   const int kb = logical % kblocks, sp = logical / kblocks;
   const int cb = sp % a.col_blocks, rb = (sp / a.col_blocks) % a.row_blocks, n = sp / (a.col_blocks * a.row_blocks);
-  const int h0 = rb * WC_ROWS, w0 = cb * WC_COLS;
+  const int h0 = rb * BLK_ROWS, w0 = cb * BLK_COLS;
 
-  // ---- loader roles: thread (lc, ltx) transforms channel lc of the chunk for the two tiles of tile column ltx
+  // ---- loader roles: thread (lc, ltx) transforms channel lc of the chunk for the two tiles of tile column ltx % TC of
+  // row pair ltx / TC
   const int lc = tid >> 5, ltx = tid & 31;
   int voff[6][4];
   unsigned okmask = 0;
 #pragma unroll
   for (int r = 0; r < 6; ++r) {
-    const int row = h0 - 1 + r;
+    const int row = h0 + 4 * (ltx / TC) - 1 + r;
     const bool rok = (unsigned)row < (unsigned)H;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const int col = w0 + 2 * ltx - 1 + s;
+      const int col = w0 + 2 * (ltx % TC) - 1 + s;
       const bool ok = rok && (unsigned)col < (unsigned)W;
       voff[r][s] = ok ? lc * HW + row * W + col : 0;
       okmask |= ok ? 1u << (r * 4 + s) : 0u;
@@ -174,9 +182,9 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
     unit(7);
   } while (++ch < chunks);
 
-  // ---- Y = A^T M A per (channel, tile), epilogue, 256-byte row segments (32 lanes x float2).  bias and add are loaded
+  // ---- Y = A^T M A per (channel, tile), epilogue, row segments of 8 TC bytes (TC lanes x float2).  bias and add are loaded
   // for all 16 channels of the lane before the transform (the loaders' registers are free), behind one wait
-  const int oh = h0 + 2 * th, ow = w0 + 2 * lr;
+  const int oh = h0 + 4 * (lr / TC) + 2 * th, ow = w0 + 2 * (lr % TC);
   const bool has_bias = a.bias != nullptr, has_add = a.add != nullptr;
   const int k0 = kb * WC_KBLK + kh * 32 + 4 * lh;
   const int64_t at0 = (((int64_t)n * K + k0) * H + oh) * W + ow;
@@ -248,44 +256,100 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_wino_weights(const float* __rest
   for (int b = 0; b < 4; ++b) reinterpret_cast<nhmc_v4f*>(U + (int64_t)idx * 16)[b] = u[b];
 }
 
-int wc_covers(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) {
-  if (n <= 0 || c < WC_CHUNK || c % WC_CHUNK || k < WC_KBLK || k % WC_KBLK || h < WC_ROWS || h % WC_ROWS || w < WC_COLS || w % WC_COLS)
+// Geometry by tile-column count: TC = 32 serves every width that is a multiple of 64 (the wide entries), 16 the width 32
+// and 8 the width 16 (the narrow entries), one column block each; H must be a multiple of the block's 128 / TC rows.
+template <int TC>
+int wc_covers_tc(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) {
+  constexpr int ROWS = 128 / TC, COLS = 2 * TC;
+  if (n <= 0 || c < WC_CHUNK || c % WC_CHUNK || k < WC_KBLK || k % WC_KBLK || h < ROWS || h % ROWS || w < COLS || w % COLS)
     return 0;
+  if (TC != 32 && w != COLS) return 0;
   if (c > 65536 || k > 65536 || h * w > (1 << 24)) return 0;                     // 32-bit offsets inside a chunk / the weights
-  return n * (h / WC_ROWS) * (w / WC_COLS) * (k / WC_KBLK) < (int64_t)1 << 31;
+  return n * (h / ROWS) * (w / COLS) * (k / WC_KBLK) < (int64_t)1 << 31;
+}
+
+int wc_covers(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) { return wc_covers_tc<32>(n, c, k, h, w); }
+
+int wc_narrow_covers(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) {
+  return w == 32 ? wc_covers_tc<16>(n, c, k, h, w) : w == 16 ? wc_covers_tc<8>(n, c, k, h, w) : 0;
+}
+
+static_assert(WC_ROWS == 128 / 32 && WC_COLS == 2 * 32, "the wide geometry");
+
+struct WcRow { int backward, c, k, res; };
+
+template <int N>
+int wc_listed(const WcRow (&table)[N], int backward, int c, int k, int h) {
+  for (const WcRow& r : table)
+    if (r.backward == (backward != 0) && r.c == c && r.k == k && r.res == h) return 1;
+  return 0;
+}
+
+template <int TC>
+int wc_launch(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c, int k, int h, int w,
+              nhmc_stream_t stream) {
+  static bool attr_set[64] = {};                             // raise the dynamic-LDS limit once per device
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wino<TC>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            WC_LDS_BYTES) != hipSuccess)
+      return NHMC_ERR_LAUNCH;
+    if (dev >= 0 && dev < 64) attr_set[dev] = true;
+  }
+  const WinoArgs a{x, u, bias, add, y, c, k, h, w, h / (128 / TC), w / (2 * TC)};
+  const int64_t blocks = (int64_t)n * a.row_blocks * a.col_blocks * (k / WC_KBLK);
+  NHMC_LAUNCH(k_conv3x3_wino<TC>, dim3((unsigned)blocks), dim3(256), WC_LDS_BYTES, nhmc_s(stream), a);
+  return nhmc_launch_status();
 }
 
 }  // namespace
 
 extern "C" int nhmc_conv3x3_wino_covers(int n, int c, int k, int h, int w) { return wc_covers(n, c, k, h, w); }
+extern "C" int nhmc_conv3x3_wino_narrow_covers(int n, int c, int k, int h, int w) { return wc_narrow_covers(n, c, k, h, w); }
 
 // Routing rule: (c, k, h, w) of the convolution that runs (backward-data: c = the gradient's channels, k = the layer's input
 // channels).  A (shape, direction) pair is listed only where tools/conv_bench.py measured this kernel at <= 0.90 of
-// F.conv2d's time at 64 chains on MI355X in the same process (profiles/r05_wino_conv_roofline.txt; the figure behind each
-// row is the larger of the median and the best-of-rounds ratio): a tie is never routed.  Other batch sizes follow the same
-// rows; only n = 64 was measured.
+// F.conv2d's time at 64 chains on MI355X in the same process (the figure behind each row is the larger of the median and
+// the best-of-rounds ratio): a tie is never routed.  Other batch sizes follow the same rows; only n = 64 was measured.
+// The first table holds the 3x3 convolutions of unet.FFHQ_CONFIG (unet.conv3x3_shapes()) with widths that are multiples of
+// 64, all measured in one run: profiles/r07_wino_conv_routing.txt.  The second holds shapes that FFHQ_CONFIG never runs;
+// they are kept because they are real measurements (profiles/r05_wino_conv_roofline.txt) and serve other channel multipliers.
 extern "C" int nhmc_conv3x3_wino_prefers(int backward, int n, int c, int k, int h, int w) {
   if (!wc_covers(n, c, k, h, w) || h != w) return 0;
-  struct Row { int backward, c, k, res; };
-  static const Row table[] = {
-      {0, 128, 128, 256},   // 128->128 forward: 0.694
-      {1, 128, 128, 256},   // 128->128 backward-data: 0.670
-      {0, 256, 128, 256},   // 256->128 forward: 0.693
-      {1, 128, 256, 256},   // 256->128 backward-data: 0.676
+  static const WcRow network[] = {
+      {0, 128, 128, 256},   // 128->128 forward: 0.676
+      {1, 128, 128, 256},   // 128->128 backward-data: 0.651
+      {0, 256, 128, 256},   // 256->128 forward: 0.678
+      {1, 128, 256, 256},   // 256->128 backward-data: 0.653
+      {0, 128, 128, 128},   // 128->128 forward: 0.666
+      {1, 128, 128, 128},   // 128->128 backward-data: 0.665
+      {0, 256, 128, 128},   // 256->128 forward: 0.681
+      {1, 128, 256, 128},   // 256->128 backward-data: 0.655
+      {0, 256, 256, 128},   // 256->256 forward: 0.695
+      {1, 256, 256, 128},   // 256->256 backward-data: 0.680
+      {0, 384, 128, 128},   // 384->128 forward: 0.669
+      {1, 128, 384, 128},   // 384->128 backward-data: 0.655
+      {0, 128, 128, 64},   // 128->128 forward: 0.693
+      {1, 128, 128, 64},   // 128->128 backward-data: 0.666
+      {0, 128, 256, 64},   // 128->256 forward: 0.688
+      {1, 256, 128, 64},   // 128->256 backward-data: 0.668
+      {0, 256, 256, 64},   // 256->256 forward: 0.689
+      {1, 256, 256, 64},   // 256->256 backward-data: 0.657
+      {0, 384, 256, 64},   // 384->256 forward: 0.699
+      {1, 256, 384, 64},   // 384->256 backward-data: 0.688
+      {0, 512, 256, 64},   // 512->256 forward: 0.703
+      {1, 256, 512, 64},   // 512->256 backward-data: 0.696
+  };
+  static const WcRow elsewhere[] = {           // not in FFHQ_CONFIG
       {0, 384, 128, 256},   // 384->128 forward: 0.696
       {1, 128, 384, 256},   // 384->128 backward-data: 0.684
       {0, 128, 256, 128},   // 128->256 forward: 0.706
       {1, 256, 128, 128},   // 128->256 backward-data: 0.678
-      {0, 256, 256, 128},   // 256->256 forward: 0.713
-      {1, 256, 256, 128},   // 256->256 backward-data: 0.699
       {0, 384, 256, 128},   // 384->256 forward: 0.718
       {1, 256, 384, 128},   // 384->256 backward-data: 0.704
       {0, 512, 256, 128},   // 512->256 forward: 0.722
       {1, 256, 512, 128},   // 512->256 backward-data: 0.716
-      {0, 256, 256, 64},   // 256->256 forward: 0.708
-      {1, 256, 256, 64},   // 256->256 backward-data: 0.674
-      {0, 512, 256, 64},   // 512->256 forward: 0.716
-      {1, 256, 512, 64},   // 512->256 backward-data: 0.719
       {0, 256, 512, 64},   // 256->512 forward: 0.725
       {1, 512, 256, 64},   // 256->512 backward-data: 0.704
       {0, 512, 512, 64},   // 512->512 forward: 0.731
@@ -295,9 +359,33 @@ extern "C" int nhmc_conv3x3_wino_prefers(int backward, int n, int c, int k, int 
       {0, 1024, 512, 64},   // 1024->512 forward: 0.734
       {1, 512, 1024, 64},   // 1024->512 backward-data: 0.742
   };
-  for (const Row& r : table)
-    if (r.backward == (backward != 0) && r.c == c && r.k == k && r.res == h) return 1;
-  return 0;
+  return wc_listed(network, backward, c, k, h) || wc_listed(elsewhere, backward, c, k, h);
+}
+
+// The narrow geometries (w = 32 and w = 16) under the same rule and from the same run: the network's nine shapes at 32 and 16.
+extern "C" int nhmc_conv3x3_wino_narrow_prefers(int backward, int n, int c, int k, int h, int w) {
+  if (!wc_narrow_covers(n, c, k, h, w) || h != w) return 0;
+  static const WcRow network[] = {
+      {0, 256, 256, 32},   // 256->256 forward: 0.706
+      {1, 256, 256, 32},   // 256->256 backward-data: 0.656
+      {0, 512, 256, 32},   // 512->256 forward: 0.668
+      {1, 256, 512, 32},   // 512->256 backward-data: 0.646
+      {0, 512, 512, 32},   // 512->512 forward: 0.710
+      {1, 512, 512, 32},   // 512->512 backward-data: 0.704
+      {0, 768, 256, 32},   // 768->256 forward: 0.655
+      {1, 256, 768, 32},   // 768->256 backward-data: 0.687
+      {0, 256, 256, 16},   // 256->256 forward: 0.716
+      {1, 256, 256, 16},   // 256->256 backward-data: 0.660
+      {0, 256, 512, 16},   // 256->512 forward: 0.701
+      {1, 512, 256, 16},   // 256->512 backward-data: 0.703
+      {0, 512, 512, 16},   // 512->512 forward: 0.712
+      {1, 512, 512, 16},   // 512->512 backward-data: 0.702
+      {0, 768, 512, 16},   // 768->512 forward: 0.703
+      {1, 512, 768, 16},   // 768->512 backward-data: 0.701
+      {0, 1024, 512, 16},   // 1024->512 forward: 0.715
+      {1, 512, 1024, 16},   // 1024->512 backward-data: 0.776
+  };
+  return wc_listed(network, backward, c, k, h);
 }
 
 extern "C" int nhmc_wino_weights(const float* weight, float* u, int backward, int channels_in, int channels_out,
@@ -316,17 +404,14 @@ extern "C" int nhmc_conv3x3_wino(const float* x, const float* u, const float* bi
   if (!x || !u || !y || y == x || (add && add == x)) return NHMC_ERR_ARG;
   if (stride != 1 || padding != 1 || !wc_covers(n, c, k, h, w)) return NHMC_ERR_SHAPE;
   if (!nhmc_aligned16(x) || !nhmc_aligned16(u) || !nhmc_aligned16(y) || !nhmc_aligned16(add)) return NHMC_ERR_ALIGN;
-  static bool attr_set[64] = {};                             // raise the dynamic-LDS limit once per device
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wino), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            WC_LDS_BYTES) != hipSuccess)
-      return NHMC_ERR_LAUNCH;
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
-  const WinoArgs a{x, u, bias, add, y, c, k, h, w, h / WC_ROWS, w / WC_COLS};
-  const int64_t blocks = (int64_t)n * a.row_blocks * a.col_blocks * (k / WC_KBLK);
-  NHMC_LAUNCH(k_conv3x3_wino, dim3((unsigned)blocks), dim3(256), WC_LDS_BYTES, nhmc_s(stream), a);
-  return nhmc_launch_status();
+  return wc_launch<32>(x, u, bias, add, y, n, c, k, h, w, stream);
+}
+
+extern "C" int nhmc_conv3x3_wino_narrow(const float* x, const float* u, const float* bias, const float* add, float* y, int n,
+                                        int c, int k, int h, int w, int stride, int padding, nhmc_stream_t stream) {
+  if (!x || !u || !y || y == x || (add && add == x)) return NHMC_ERR_ARG;
+  if (stride != 1 || padding != 1 || !wc_narrow_covers(n, c, k, h, w)) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(x) || !nhmc_aligned16(u) || !nhmc_aligned16(y) || !nhmc_aligned16(add)) return NHMC_ERR_ALIGN;
+  return w == 32 ? wc_launch<16>(x, u, bias, add, y, n, c, k, h, w, stream)
+                 : wc_launch<8>(x, u, bias, add, y, n, c, k, h, w, stream);
 }

@@ -1047,15 +1047,23 @@ def wino_weights(weight, backward=False):
     return u
 
 
+def _wino_narrow(w):
+    """Images 32 and 16 wide run the kernel's narrow geometries, which have entries of their own (nhmc_conv3x3_wino_narrow*)."""
+    return w in (32, 16)
+
+
 def conv3x3_wino_covers(n, c, k, h, w):
-    return bool(_lib.load().nhmc_conv3x3_wino_covers(n, c, k, h, w))
+    lib = _lib.load()
+    return bool((lib.nhmc_conv3x3_wino_narrow_covers if _wino_narrow(w) else lib.nhmc_conv3x3_wino_covers)(n, c, k, h, w))
 
 
 def conv3x3_wino_prefers(backward, n, c, k, h, w):
     """The library's routing rule (nhmc_conv3x3_wino_prefers); NHMC_WINO=0 (the A/B switch, read per call) answers no."""
     if os.environ.get('NHMC_WINO', '1') == '0':
         return False
-    return bool(_lib.load().nhmc_conv3x3_wino_prefers(int(bool(backward)), n, c, k, h, w))
+    lib = _lib.load()
+    prefers = lib.nhmc_conv3x3_wino_narrow_prefers if _wino_narrow(w) else lib.nhmc_conv3x3_wino_prefers
+    return bool(prefers(int(bool(backward)), n, c, k, h, w))
 
 
 def conv3x3_wino(x, weight, bias=None, add=None, backward=False):
@@ -1070,9 +1078,10 @@ def conv3x3_wino(x, weight, bias=None, add=None, backward=False):
     y = torch.empty((N, Kk, H, W), dtype=torch.float32, device=x.device)
     if (bias is not None and bias.numel() != Kk) or (add is not None and add.shape != y.shape):
         raise _lib.NhmcError('conv3x3_wino: bias / add do not match the output')
-    rc = lib.nhmc_conv3x3_wino(_p(x, torch.float32, 'x'), _p(u), _p(bias, torch.float32, 'bias'), _p(add, torch.float32, 'add'),
-                               _p(y), N, Cc, Kk, H, W, 1, 1, _stream())
-    _lib.check(rc, 'nhmc_conv3x3_wino')
+    entry = 'nhmc_conv3x3_wino_narrow' if _wino_narrow(W) else 'nhmc_conv3x3_wino'
+    rc = getattr(lib, entry)(_p(x, torch.float32, 'x'), _p(u), _p(bias, torch.float32, 'bias'), _p(add, torch.float32, 'add'),
+                             _p(y), N, Cc, Kk, H, W, 1, 1, _stream())
+    _lib.check(rc, entry)
     return y
 
 

@@ -416,3 +416,29 @@ def create_model(image_size=256, num_channels=128, num_res_blocks=1, channel_mul
     elif model_path:
         print(f'checkpoint {model_path} not found / randomly initialised')
     return model
+
+
+def conv3x3_shapes(config=None):
+    """[(C, K, resolution, count)] of every 3x3 stride-1 padding-1 Conv2d call of one forward pass of create_model(**config)
+    (default FFHQ_CONFIG) on a [1, 3, image_size, image_size] input, ordered by falling resolution, then C, then K.
+    Found by running the model on the `meta` device with a forward hook on every Conv2d: meta tensors take the unfused
+    path, so each convolution is a module call, and nothing is allocated or computed.  The routing table of the Winograd
+    kernel and tools/conv_bench.py rest on this list."""
+    config = dict(FFHQ_CONFIG if config is None else config)
+    with torch.device('meta'):
+        model = create_model(**config)
+    seen, hooks = {}, []
+
+    def hook(mod, args, out):
+        key = (mod.in_channels, mod.out_channels, args[0].shape[-1])
+        seen[key] = seen.get(key, 0) + 1
+    for mod in model.modules():
+        if isinstance(mod, nn.Conv2d) and tuple(mod.kernel_size) == (3, 3) and tuple(mod.stride) == (1, 1) \
+                and mod.padding == (1, 1):
+            hooks.append(mod.register_forward_hook(hook))
+    size = config.get('image_size', 256)
+    with torch.no_grad():
+        model(torch.empty(1, 3, size, size, device='meta'), torch.zeros(1, device='meta'))
+    for h in hooks:
+        h.remove()
+    return [(c, k, res, n) for (c, k, res), n in sorted(seen.items(), key=lambda kv: (-kv[0][2], kv[0][0], kv[0][1]))]

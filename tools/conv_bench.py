@@ -1,9 +1,11 @@
 """The Winograd MFMA convolution (csrc/wino_conv.hip) against F.conv2d at the FFHQ U-Net's covered 3x3 shapes, forward and
-backward-data, 64 chains, both alternating in one process.  Per (C, K, resolution, direction): 100 warm-up calls of each
-(the clocks ramp for longer than a few calls), then the median of 3 rounds of 10 event-timed launches per variant on
-rotating buffers that together exceed the 256 MiB Infinity Cache.  Prints microseconds, the ratio kernel / F.conv2d and
+backward-data, 64 chains, both alternating in one process.  The shapes are those of the model itself
+(unet.conv3x3_shapes(), a walk over create_model(**FFHQ_CONFIG)) that the kernel covers in both directions.
+Per (C, K, resolution, direction): 100 warm-up calls of each (the clocks ramp for longer than a few calls), then the
+median of 3 rounds of 10 event-timed launches per variant on rotating buffers that together exceed the 256 MiB Infinity
+Cache.  Prints microseconds, the ratio kernel / F.conv2d and
 TFLOP/s in direct-convolution terms (2 * 9 * N * C * K * H * W).  Rows at or below 0.90 are what
-nhmc_conv3x3_wino_prefers may list.
+nhmc_conv3x3_wino_prefers and nhmc_conv3x3_wino_narrow_prefers may list.
 Usage: python tools/conv_bench.py [chains] [rounds] [--epilogue] [--only=C,K,res]
 --epilogue adds, per forward row, the kernel with its (acc + bias) + add epilogue against kernel + k_bias_add2."""
 import sys
@@ -11,15 +13,14 @@ import torch
 import torch.nn.functional as F
 sys.path.insert(0, '.')
 import nhmc.kernels as K
+from nhmc import unet
 
-args = [a for a in sys.argv[1:] if not a.startswith('--')]
-B = int(args[0]) if len(args) > 0 else 64
-ROUNDS = int(args[1]) if len(args) > 1 else 3
-EPILOGUE = '--epilogue' in sys.argv
-dev = torch.device('cuda')
-# (C, K, resolution) of every 3x3 stride-1 convolution of FFHQ_CONFIG with C >= 128 at 64 and above
-SHAPES = ((128, 128, 256), (256, 128, 256), (384, 128, 256), (128, 256, 128), (256, 256, 128), (384, 256, 128),
-          (512, 256, 128), (256, 256, 64), (512, 256, 64), (256, 512, 64), (512, 512, 64), (768, 256, 64), (1024, 512, 64))
+
+def default_shapes(chains=64):
+    """(C, K, resolution) of the 3x3 convolutions of one FFHQ_CONFIG forward pass that the kernel covers forward and
+    backward-data at this chain count, in the order of unet.conv3x3_shapes()."""
+    return tuple((c, k, res) for c, k, res, _ in unet.conv3x3_shapes()
+                 if K.conv3x3_wino_covers(chains, c, k, res, res) and K.conv3x3_wino_covers(chains, k, c, res, res))
 
 
 def timeit(f, bufs, n=10):
@@ -32,46 +33,57 @@ def timeit(f, bufs, n=10):
     return e0.elapsed_time(e1) / n
 
 
-print(f'chains {B}, rounds {ROUNDS}: us wino | us F.conv2d | ratio | TFLOP/s wino | TFLOP/s F.conv2d')
-ONLY = [tuple(int(v) for v in a[7:].split(',')) for a in sys.argv[1:] if a.startswith('--only=')]
-for Cc, Kk, res in ONLY or SHAPES:
-    w = (torch.randn(Kk, Cc, 3, 3, device=dev) / (9 * Cc) ** 0.5)
-    flop = 2 * 9 * B * Cc * Kk * res * res
-    for backward in (False, True):
-        cin = Kk if backward else Cc
-        nbuf = max(2, -(-(320 << 20) // (B * cin * res * res * 4)))
-        bufs = [torch.randn(B, cin, res, res, device=dev) for _ in range(nbuf)]
-        x_shape = (B, Cc, res, res)
-        if backward:
-            vendor = lambda t: torch.nn.grad.conv2d_input(x_shape, w, t, 1, 1)
-        else:
-            vendor = lambda t: F.conv2d(t, w, None, 1, 1)
-        ours = lambda t: K.conv3x3_wino(t, w, backward=backward)
-        for _ in range(100 // nbuf + 1):
-            for t in bufs:
-                ours(t)
-                vendor(t)
-        tv, to = [], []
-        for _ in range(ROUNDS):                     # interleaved rounds: the two variants see the same clocks
-            to.append(timeit(ours, bufs))
-            tv.append(timeit(vendor, bufs))
-        mo, mv = sorted(to)[len(to) // 2], sorted(tv)[len(tv) // 2]
-        line = (f'[{B},{Cc}->{Kk},{res}x{res}] {"bwd" if backward else "fwd"}: {mo * 1e3:8.0f} | {mv * 1e3:8.0f} | {mo / mv:.3f} '
-                f'(best of rounds {min(to) / min(tv):.3f}) | {flop / mo / 1e9:6.1f} | {flop / mv / 1e9:6.1f}')
-        if EPILOGUE and not backward:
-            bias, add = torch.randn(Kk, device=dev), torch.randn(B, Kk, res, res, device=dev)
-            fused = lambda t: K.conv3x3_wino(t, w, bias, add)
-            split = lambda t: K.bias_add2(K.conv3x3_wino(t, w), bias, add)
-            for t in bufs:
-                fused(t)
-                split(t)
-            tf, ts = [], []
-            for _ in range(ROUNDS):
-                tf.append(timeit(fused, bufs))
-                ts.append(timeit(split, bufs))
-            mf, ms = sorted(tf)[len(tf) // 2], sorted(ts)[len(ts) // 2]
-            line += f' | epilogue fused {mf * 1e3:.0f} us vs kernel + bias_add2 {ms * 1e3:.0f} us = {mf / ms:.3f}'
-            del bias, add
-        print(line, flush=True)
-        del bufs
-    del w
+def main():
+    dev = torch.device('cuda')
+    args = [a for a in sys.argv[1:] if not a.startswith('--')]
+    B = int(args[0]) if len(args) > 0 else 64
+    ROUNDS = int(args[1]) if len(args) > 1 else 3
+    EPILOGUE = '--epilogue' in sys.argv
+    SHAPES = default_shapes(B)
+    print(f'chains {B}, rounds {ROUNDS}: us wino | us F.conv2d | ratio | TFLOP/s wino | TFLOP/s F.conv2d')
+    ONLY = [tuple(int(v) for v in a[7:].split(',')) for a in sys.argv[1:] if a.startswith('--only=')]
+    for Cc, Kk, res in ONLY or SHAPES:
+        w = (torch.randn(Kk, Cc, 3, 3, device=dev) / (9 * Cc) ** 0.5)
+        flop = 2 * 9 * B * Cc * Kk * res * res
+        for backward in (False, True):
+            cin = Kk if backward else Cc
+            nbuf = max(2, -(-(320 << 20) // (B * cin * res * res * 4)))
+            bufs = [torch.randn(B, cin, res, res, device=dev) for _ in range(nbuf)]
+            x_shape = (B, Cc, res, res)
+            if backward:
+                vendor = lambda t: torch.nn.grad.conv2d_input(x_shape, w, t, 1, 1)
+            else:
+                vendor = lambda t: F.conv2d(t, w, None, 1, 1)
+            ours = lambda t: K.conv3x3_wino(t, w, backward=backward)
+            for _ in range(100 // nbuf + 1):
+                for t in bufs:
+                    ours(t)
+                    vendor(t)
+            tv, to = [], []
+            for _ in range(ROUNDS):                     # interleaved rounds: the two variants see the same clocks
+                to.append(timeit(ours, bufs))
+                tv.append(timeit(vendor, bufs))
+            mo, mv = sorted(to)[len(to) // 2], sorted(tv)[len(tv) // 2]
+            line = (f'[{B},{Cc}->{Kk},{res}x{res}] {"bwd" if backward else "fwd"}: {mo * 1e3:8.0f} | {mv * 1e3:8.0f} | {mo / mv:.3f} '
+                    f'(best of rounds {min(to) / min(tv):.3f}) | {flop / mo / 1e9:6.1f} | {flop / mv / 1e9:6.1f}')
+            if EPILOGUE and not backward:
+                bias, add = torch.randn(Kk, device=dev), torch.randn(B, Kk, res, res, device=dev)
+                fused = lambda t: K.conv3x3_wino(t, w, bias, add)
+                split = lambda t: K.bias_add2(K.conv3x3_wino(t, w), bias, add)
+                for t in bufs:
+                    fused(t)
+                    split(t)
+                tf, ts = [], []
+                for _ in range(ROUNDS):
+                    tf.append(timeit(fused, bufs))
+                    ts.append(timeit(split, bufs))
+                mf, ms = sorted(tf)[len(tf) // 2], sorted(ts)[len(ts) // 2]
+                line += f' | epilogue fused {mf * 1e3:.0f} us vs kernel + bias_add2 {ms * 1e3:.0f} us = {mf / ms:.3f}'
+                del bias, add
+            print(line, flush=True)
+            del bufs
+        del w
+
+
+if __name__ == '__main__':
+    main()
