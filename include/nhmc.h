@@ -567,6 +567,11 @@ int nhmc_bias_add2(const float* h, const float* bias, const float* other, float*
  * nhmc_conv3x3_wino_narrow, _narrow_covers, _narrow_prefers: the same kernel, arguments, validation order and results for
  *   images 32 and 16 wide, which the entries above refuse: the workgroup's 64 tiles are 4 x 16 (w = 32, h % 8 == 0) or
  *   8 x 8 (w = 16, h % 16 == 0) instead of 2 x 32.  Every other width is NHMC_ERR_SHAPE here.  u is shared with the wide entry.
+ * nhmc_conv3x3_wino_k32, _k32_covers, _k32_prefers: the same kernel, arguments, validation order and results for k % 32 == 0
+ *   (k >= 32) in all three geometries, chosen by w; _k32_covers is 1 wherever _covers or _narrow_covers is.  With k % 64 == 32
+ *   the last block of 64 output channels is half empty: its upper 32 rows of u are not read and nothing is stored for them.
+ *   u is nhmc_wino_weights' with the same (c', k'), no padding.  An output channel's bits do not depend on k, so k % 64 == 0
+ *   gives what the entries above give.  _k32_prefers lists shapes with k % 64 == 32 only, measured at n = 16.
  * ---------------------------------------------------------------------------------- */
 int nhmc_wino_weights(const float* weight, float* u, int backward, int channels_in, int channels_out, nhmc_stream_t stream);
 int nhmc_conv3x3_wino(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c, int k,
@@ -577,6 +582,10 @@ int nhmc_conv3x3_wino_narrow(const float* x, const float* u, const float* bias, 
                              int k, int h, int w, int stride, int padding, nhmc_stream_t stream);
 int nhmc_conv3x3_wino_narrow_covers(int n, int c, int k, int h, int w);
 int nhmc_conv3x3_wino_narrow_prefers(int backward, int n, int c, int k, int h, int w);
+int nhmc_conv3x3_wino_k32(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c, int k,
+                          int h, int w, int stride, int padding, nhmc_stream_t stream);
+int nhmc_conv3x3_wino_k32_covers(int n, int c, int k, int h, int w);
+int nhmc_conv3x3_wino_k32_prefers(int backward, int n, int c, int k, int h, int w);
 
 /* PSNR of clamp((xt+1)/2,0,1) against clamp((x_orig+1)/2,0,1)   main_sampling.py:738-739
  * ws: double[n_chains][nhmc_data_tiles(n_elem)]. */

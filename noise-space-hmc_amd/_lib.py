@@ -102,6 +102,9 @@ SIGNATURES = {
     'nhmc_conv3x3_wino_narrow': (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
     'nhmc_conv3x3_wino_narrow_covers': (I, [I, I, I, I, I]),
     'nhmc_conv3x3_wino_narrow_prefers': (I, [I, I, I, I, I, I]),
+    'nhmc_conv3x3_wino_k32': (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    'nhmc_conv3x3_wino_k32_covers': (I, [I, I, I, I, I]),
+    'nhmc_conv3x3_wino_k32_prefers': (I, [I, I, I, I, I, I]),
     'nhmc_psnr':(I, [P, P, P, P, I, I64, P]),
     'nhmc_psnr_samples': (I, [P, P, P, P, I, I, I64, P]),
     'nhmc_ssim_tiles': (I, [I, I]),

@@ -22,6 +22,10 @@
 // lanes of a b128 group on 4 of the 16 slots of a bank row; the 16-byte granule g of row R is stored at granule
 // g ^ ((R >> 2) & 3), which spreads every group over all 16.  While chunk i is multiplied, chunk i + 1 is loaded into
 // registers, transformed and written to the other buffer.
+// K that is a multiple of 32 but not of 64 (template parameter TAIL, entry nhmc_conv3x3_wino_k32): ceil(K / 64) K blocks, the
+// last one half empty.  U keeps nhmc_wino_weights' layout [C][K][16] with K as it is; the tail block's loads of the upper
+// 32 rows are predicated off and zeros go to LDS instead, so nothing outside U is read.  A channel's MFMA chain is the same
+// A row against the same B rows in the same order whatever K is, so its bits do not depend on K.
 #include "nhmc_common.h"
 
 namespace {
@@ -40,7 +44,7 @@ struct WinoArgs {
   int C, K, H, W, row_blocks, col_blocks;
 };
 
-template <int TC>
+template <int TC, bool TAIL>
 __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
   static_assert(TC == 32 || TC == 16 || TC == 8, "64 tiles as 32 / TC row pairs x TC columns");
   constexpr int BLK_ROWS = 128 / TC, BLK_COLS = 2 * TC;
@@ -53,8 +57,15 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
   const int total = gridDim.x;
   int logical = blockIdx.x;
   if ((total & 7) == 0) logical = (logical & 7) * (total >> 3) + (logical >> 3);
-  const int kblocks = K / WC_KBLK;
+  const int kblocks = TAIL ? (K + WC_KBLK - 1) / WC_KBLK : K / WC_KBLK;
   const int kb = logical % kblocks, sp = logical / kblocks;
+  // TAIL (K % 64 == 32): the last K block owns its lower 32 channels only.  Its kh = 1 waves keep their loader and barrier
+  // roles, issue no MFMA (a scalar branch: the condition goes through readfirstlane) and leave before the epilogue; rows
+  // 32 .. 63 of its U stage are never read from U (they would be the next input channel's, or past the end) and are zeros
+  // in LDS.  A second copy of the loop for those waves cost the other waves 212 bytes of scratch; the branch costs none
+  const bool tail_block = TAIL && kb == kblocks - 1;
+  const bool idle = tail_block && __builtin_amdgcn_readfirstlane(kh) == 1;
+  const bool u_row_ok = !(tail_block && tid >= 128);
   const int cb = sp % a.col_blocks, rb = (sp / a.col_blocks) % a.row_blocks, n = sp / (a.col_blocks * a.row_blocks);
   const int h0 = rb * BLK_ROWS, w0 = cb * BLK_COLS;
 
@@ -92,7 +103,10 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
       for (int s = 0; s < 4; ++s) xr[r][s] = xs[voff[r][s]];
     const char* us = un + (int64_t)ch * WC_CHUNK * K * 64;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) ur[i] = *reinterpret_cast<const nhmc_v4f*>(us + (int64_t)i * K * 64 + uoff);
+    for (int i = 0; i < 8; ++i) {
+      if (!TAIL || u_row_ok) ur[i] = *reinterpret_cast<const nhmc_v4f*>(us + (int64_t)i * K * 64 + uoff);
+      else ur[i] = nhmc_v4f{0.0f, 0.0f, 0.0f, 0.0f};
+    }
   };
   // the loaded patch is first touched here, three units after its loads were issued: without the pin the selects and the
   // first-level differences of all four columns move to the head of the chunk, and the chunk starts with a wait on the loads
@@ -122,6 +136,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
     for (int i = 2 * b; i < 2 * b + 2; ++i) *reinterpret_cast<nhmc_v4f*>(Us + uw + 1024 * i) = ur[i];
   };
 
+  const int chunks = C / WC_CHUNK;
   f32x16 acc[16];
 #pragma unroll
   for (int f = 0; f < 16; ++f)
@@ -150,11 +165,10 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int f = 8 * (u & 1) + j;
-      acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u & 1][j], bv[u & 1][j], acc[f], 0, 0, 0);
+      if (!TAIL || !idle) acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u & 1][j], bv[u & 1][j], acc[f], 0, 0, 0);
     }
   };
 
-  const int chunks = C / WC_CHUNK;
   issue_loads(0);
 #pragma unroll
   for (int b = 0; b < 4; ++b) stage_part(0, b);
@@ -184,6 +198,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
 
   // ---- Y = A^T M A per (channel, tile), epilogue, row segments of 8 TC bytes (TC lanes x float2).  bias and add are loaded
   // for all 16 channels of the lane before the transform (the loaders' registers are free), behind one wait
+  if (TAIL && idle) return;
   const int oh = h0 + 4 * (lr / TC) + 2 * th, ow = w0 + 2 * (lr % TC);
   const bool has_bias = a.bias != nullptr, has_add = a.add != nullptr;
   const int k0 = kb * WC_KBLK + kh * 32 + 4 * lh;
@@ -258,20 +273,26 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_wino_weights(const float* __rest
 
 // Geometry by tile-column count: TC = 32 serves every width that is a multiple of 64 (the wide entries), 16 the width 32
 // and 8 the width 16 (the narrow entries), one column block each; H must be a multiple of the block's 128 / TC rows.
-template <int TC>
+// KM: what K must be a multiple of, 64 (the entries without a tail block) or 32 (nhmc_conv3x3_wino_k32).
+template <int TC, int KM = WC_KBLK>
 int wc_covers_tc(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) {
   constexpr int ROWS = 128 / TC, COLS = 2 * TC;
-  if (n <= 0 || c < WC_CHUNK || c % WC_CHUNK || k < WC_KBLK || k % WC_KBLK || h < ROWS || h % ROWS || w < COLS || w % COLS)
+  if (n <= 0 || c < WC_CHUNK || c % WC_CHUNK || k < KM || k % KM || h < ROWS || h % ROWS || w < COLS || w % COLS)
     return 0;
   if (TC != 32 && w != COLS) return 0;
   if (c > 65536 || k > 65536 || h * w > (1 << 24)) return 0;                     // 32-bit offsets inside a chunk / the weights
-  return n * (h / ROWS) * (w / COLS) * (k / WC_KBLK) < (int64_t)1 << 31;
+  return n * (h / ROWS) * (w / COLS) * ((k + WC_KBLK - 1) / WC_KBLK) < (int64_t)1 << 31;
 }
 
 int wc_covers(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) { return wc_covers_tc<32>(n, c, k, h, w); }
 
 int wc_narrow_covers(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) {
   return w == 32 ? wc_covers_tc<16>(n, c, k, h, w) : w == 16 ? wc_covers_tc<8>(n, c, k, h, w) : 0;
+}
+
+int wc_k32_covers(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) {
+  return w == 32 ? wc_covers_tc<16, 32>(n, c, k, h, w) : w == 16 ? wc_covers_tc<8, 32>(n, c, k, h, w)
+                                                                 : wc_covers_tc<32, 32>(n, c, k, h, w);
 }
 
 static_assert(WC_ROWS == 128 / 32 && WC_COLS == 2 * 32, "the wide geometry");
@@ -285,21 +306,21 @@ int wc_listed(const WcRow (&table)[N], int backward, int c, int k, int h) {
   return 0;
 }
 
-template <int TC>
+template <int TC, bool TAIL = false>
 int wc_launch(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c, int k, int h, int w,
               nhmc_stream_t stream) {
   static bool attr_set[64] = {};                             // raise the dynamic-LDS limit once per device
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wino<TC>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wino<TC, TAIL>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             WC_LDS_BYTES) != hipSuccess)
       return NHMC_ERR_LAUNCH;
     if (dev >= 0 && dev < 64) attr_set[dev] = true;
   }
   const WinoArgs a{x, u, bias, add, y, c, k, h, w, h / (128 / TC), w / (2 * TC)};
-  const int64_t blocks = (int64_t)n * a.row_blocks * a.col_blocks * (k / WC_KBLK);
-  NHMC_LAUNCH(k_conv3x3_wino<TC>, dim3((unsigned)blocks), dim3(256), WC_LDS_BYTES, nhmc_s(stream), a);
+  const int64_t blocks = (int64_t)n * a.row_blocks * a.col_blocks * ((k + WC_KBLK - 1) / WC_KBLK);
+  NHMC_LAUNCH((k_conv3x3_wino<TC, TAIL>), dim3((unsigned)blocks), dim3(256), WC_LDS_BYTES, nhmc_s(stream), a);
   return nhmc_launch_status();
 }
 
@@ -359,7 +380,16 @@ extern "C" int nhmc_conv3x3_wino_prefers(int backward, int n, int c, int k, int 
       {0, 1024, 512, 64},   // 1024->512 forward: 0.734
       {1, 512, 1024, 64},   // 1024->512 backward-data: 0.742
   };
-  return wc_listed(network, backward, c, k, h) || wc_listed(elsewhere, backward, c, k, h);
+  // latent networks, measured at 16 chains (tools/conv_bench.py --latent, profiles/r08_wino_conv_latent.txt): the shapes of
+  // ldm.conv3x3_shapes with K % 64 == 0 that no row above holds.  The score network runs without gradient: forward only
+  static const WcRow latent[] = {
+      {0, 448, 448, 64},    // U-Net 448->448 forward: 0.646
+      {0, 256, 256, 256},   // decoder 256->256 forward: 0.692
+      {1, 256, 256, 256},   // decoder 256->256 backward-data: 0.679
+      {0, 512, 512, 128},   // decoder 512->512 forward: 0.715
+      {1, 512, 512, 128},   // decoder 512->512 backward-data: 0.710
+  };
+  return wc_listed(network, backward, c, k, h) || wc_listed(elsewhere, backward, c, k, h) || wc_listed(latent, backward, c, k, h);
 }
 
 // The narrow geometries (w = 32 and w = 16) under the same rule and from the same run: the network's nine shapes at 32 and 16.
@@ -385,7 +415,37 @@ extern "C" int nhmc_conv3x3_wino_narrow_prefers(int backward, int n, int c, int 
       {0, 1024, 512, 16},   // 1024->512 forward: 0.715
       {1, 512, 1024, 16},   // 1024->512 backward-data: 0.776
   };
-  return wc_listed(network, backward, c, k, h);
+  // latent networks, measured at 16 chains (profiles/r08_wino_conv_latent.txt): the LDM U-Net's K = 448 / 896 layers, forward
+  static const WcRow latent[] = {
+      {0, 224, 448, 32},    // 224->448 forward: 0.752
+      {0, 448, 448, 32},    // 448->448 forward: 0.743
+      {0, 672, 448, 32},    // 672->448 forward: 0.743
+      {0, 896, 448, 32},    // 896->448 forward: 0.728
+      {0, 1120, 448, 32},   // 1120->448 forward: 0.736
+      {0, 896, 896, 16},    // 896->896 forward: 0.675
+  };
+  return wc_listed(network, backward, c, k, h) || wc_listed(latent, backward, c, k, h);
+}
+
+// K % 64 == 32 only; same rule, measured at 16 chains (the latent sampler's chain count) by tools/conv_bench.py --latent:
+// profiles/r08_wino_conv_latent.txt.  The rows are the LDM U-Net's K = 224 / 672 layers, forward only (it runs without
+// gradient).  At 16 x 16 a tail launch has 16 x 11 = 176 workgroups on 256 CUs, one in eleven of them half empty.
+extern "C" int nhmc_conv3x3_wino_k32_covers(int n, int c, int k, int h, int w) { return wc_k32_covers(n, c, k, h, w); }
+
+extern "C" int nhmc_conv3x3_wino_k32_prefers(int backward, int n, int c, int k, int h, int w) {
+  if (!wc_k32_covers(n, c, k, h, w) || h != w || k % WC_KBLK == 0) return 0;
+  static const WcRow latent[] = {
+      {0, 224, 224, 64},    // 224->224 forward: 0.753
+      {0, 448, 224, 64},    // 448->224 forward: 0.742
+      {0, 672, 224, 64},    // 672->224 forward: 0.740
+      {0, 672, 672, 32},    // 672->672 forward: 0.697
+      {0, 448, 672, 16},    // 448->672 forward: 0.873
+      {0, 672, 672, 16},    // 672->672 forward: 0.864
+      {0, 1120, 672, 16},   // 1120->672 forward: 0.854
+      {0, 1344, 672, 16},   // 1344->672 forward: 0.859
+      {0, 1568, 672, 16},   // 1568->672 forward: 0.848
+  };
+  return wc_listed(latent, backward, c, k, h);
 }
 
 extern "C" int nhmc_wino_weights(const float* weight, float* u, int backward, int channels_in, int channels_out,
@@ -414,4 +474,20 @@ extern "C" int nhmc_conv3x3_wino_narrow(const float* x, const float* u, const fl
   if (!nhmc_aligned16(x) || !nhmc_aligned16(u) || !nhmc_aligned16(y) || !nhmc_aligned16(add)) return NHMC_ERR_ALIGN;
   return w == 32 ? wc_launch<16>(x, u, bias, add, y, n, c, k, h, w, stream)
                  : wc_launch<8>(x, u, bias, add, y, n, c, k, h, w, stream);
+}
+
+// Output-channel counts that are multiples of 32, all three geometries, chosen by w.  K % 64 == 0 runs the instantiations of
+// the two entries above (their bits); K % 64 == 32 the TAIL ones.
+extern "C" int nhmc_conv3x3_wino_k32(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c,
+                                     int k, int h, int w, int stride, int padding, nhmc_stream_t stream) {
+  if (!x || !u || !y || y == x || (add && add == x)) return NHMC_ERR_ARG;
+  if (stride != 1 || padding != 1 || !wc_k32_covers(n, c, k, h, w)) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(x) || !nhmc_aligned16(u) || !nhmc_aligned16(y) || !nhmc_aligned16(add)) return NHMC_ERR_ALIGN;
+  if (k % WC_KBLK == 0)
+    return w == 32   ? wc_launch<16>(x, u, bias, add, y, n, c, k, h, w, stream)
+           : w == 16 ? wc_launch<8>(x, u, bias, add, y, n, c, k, h, w, stream)
+                     : wc_launch<32>(x, u, bias, add, y, n, c, k, h, w, stream);
+  return w == 32   ? wc_launch<16, true>(x, u, bias, add, y, n, c, k, h, w, stream)
+         : w == 16 ? wc_launch<8, true>(x, u, bias, add, y, n, c, k, h, w, stream)
+                   : wc_launch<32, true>(x, u, bias, add, y, n, c, k, h, w, stream);
 }

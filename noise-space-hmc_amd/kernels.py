@@ -1066,6 +1066,19 @@ def conv3x3_wino_prefers(backward, n, c, k, h, w):
     return bool(prefers(int(bool(backward)), n, c, k, h, w))
 
 
+def conv3x3_wino_k32_covers(n, c, k, h, w):
+    """nhmc_conv3x3_wino_k32_covers: output-channel counts that are multiples of 32, every geometry; a superset of
+    conv3x3_wino_covers, which keeps its answers."""
+    return bool(_lib.load().nhmc_conv3x3_wino_k32_covers(n, c, k, h, w))
+
+
+def conv3x3_wino_k32_prefers(backward, n, c, k, h, w):
+    """The routing rule for k % 64 == 32 (nhmc_conv3x3_wino_k32_prefers); NHMC_WINO=0 answers no."""
+    if os.environ.get('NHMC_WINO', '1') == '0':
+        return False
+    return bool(_lib.load().nhmc_conv3x3_wino_k32_prefers(int(bool(backward)), n, c, k, h, w))
+
+
 def conv3x3_wino(x, weight, bias=None, add=None, backward=False):
     """conv2d(x, weight, stride 1, padding 1) (+ bias[k]) (+ add) on the Winograd MFMA kernel; backward=True: the
     backward-data pass of that convolution, x being the output gradient [N, K, H, W] -> [N, C, H, W]."""
@@ -1078,7 +1091,7 @@ def conv3x3_wino(x, weight, bias=None, add=None, backward=False):
     y = torch.empty((N, Kk, H, W), dtype=torch.float32, device=x.device)
     if (bias is not None and bias.numel() != Kk) or (add is not None and add.shape != y.shape):
         raise _lib.NhmcError('conv3x3_wino: bias / add do not match the output')
-    entry = 'nhmc_conv3x3_wino_narrow' if _wino_narrow(W) else 'nhmc_conv3x3_wino'
+    entry = 'nhmc_conv3x3_wino_k32' if Kk % 64 else 'nhmc_conv3x3_wino_narrow' if _wino_narrow(W) else 'nhmc_conv3x3_wino'
     rc = getattr(lib, entry)(_p(x, torch.float32, 'x'), _p(u), _p(bias, torch.float32, 'bias'), _p(add, torch.float32, 'add'),
                              _p(y), N, Cc, Kk, H, W, 1, 1, _stream())
     _lib.check(rc, entry)

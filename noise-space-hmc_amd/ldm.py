@@ -31,7 +31,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import kernels as K
-from .unet import AttentionBlock, Stage, _BiasAdd2, conv_nobias, fused_glue, group_norm_act, group_norm_act_fork, sinusoid, sinusoid_freqs
+from .unet import AttentionBlock, Stage, _BiasAdd2, conv_bias, conv_nobias, fused_glue, group_norm_act, group_norm_act_fork, sinusoid, sinusoid_freqs
 
 # configs/config_ffhq_latent.yml:45-80
 FFHQ_LDM_UNET = dict(image_size=64, in_channels=3, out_channels=3, model_channels=224, attention_resolutions=(8, 4, 2),
@@ -59,18 +59,23 @@ class ConvDown(nn.Module):
 
 class ConvUp(nn.Module):
     """openaimodel.py:88-114 with use_conv: nearest x2 then 3x3 convolution, parameter name `conv`."""
+    wino = None              # routing of the convolution (unet.wino_route): None = the measured table, True = forced (tests)
 
     def __init__(self, ch):
         super().__init__()
         self.conv = nn.Conv2d(ch, ch, 3, padding=1)
 
     def forward(self, x):
-        return self.conv(F.interpolate(x, scale_factor=2, mode='nearest'))
+        x = F.interpolate(x, scale_factor=2, mode='nearest')
+        if fused_glue(x, self.conv.weight, self.conv.bias):
+            return conv_bias(self.conv, x, self.wino)
+        return self.conv(x)
 
 
 class AddEmbResBlock(nn.Module):
     """openaimodel.py:157-267 without scale-shift norm: h = conv(silu(gn(x))) + W emb; out = skip(x) + conv(silu(gn(h)))."""
     takes_emb = True
+    wino = None              # routing of the two 3x3 convolutions, as unet.ResBlock.wino
 
     def __init__(self, ch, emb_ch, out_ch):
         super().__init__()
@@ -85,8 +90,8 @@ class AddEmbResBlock(nn.Module):
         if fused_glue(h, conv1.bias, conv2.bias, e):
             # conv1's bias and the embedding term (h = conv(..) + emb_out, openaimodel.py:257) enter the next GroupNorm's
             # load as one [B, C] term; conv2's bias enters the residual add
-            h = group_norm_act(self.out_layers[0], conv_nobias(conv1, h), pre=(e + conv1.bias).contiguous())
-            return _BiasAdd2.apply(conv_nobias(conv2, h), conv2.bias, self.skip_connection(x))
+            h = group_norm_act(self.out_layers[0], conv_nobias(conv1, h, self.wino), pre=(e + conv1.bias).contiguous())
+            return _BiasAdd2.apply(conv_nobias(conv2, h, self.wino), conv2.bias, self.skip_connection(x))
         h = conv1(h) + e[:, :, None, None]
         return self.skip_connection(x) + conv2(group_norm_act(self.out_layers[0], h))
 
@@ -166,6 +171,7 @@ def _swish(x):
 
 class PlainResBlock(nn.Module):
     """model.py:82-141 with temb_channels = 0, dropout 0, 1x1 shortcut."""
+    wino = None              # routing of the two 3x3 convolutions, as unet.ResBlock.wino
 
     def __init__(self, cin, cout):
         super().__init__()
@@ -178,8 +184,8 @@ class PlainResBlock(nn.Module):
         h, x = group_norm_act_fork(self.norm1, x, act_fn=_swish)         # Normalize + x sigmoid(x); x goes on to the shortcut
         sc = self.nin_shortcut(x) if hasattr(self, 'nin_shortcut') else x
         if fused_glue(h, self.conv1.bias, self.conv2.bias):
-            h = group_norm_act(self.norm2, conv_nobias(self.conv1, h), act_fn=_swish, pre=self.conv1.bias)
-            return _BiasAdd2.apply(conv_nobias(self.conv2, h), self.conv2.bias, sc)
+            h = group_norm_act(self.norm2, conv_nobias(self.conv1, h, self.wino), act_fn=_swish, pre=self.conv1.bias)
+            return _BiasAdd2.apply(conv_nobias(self.conv2, h, self.wino), self.conv2.bias, sc)
         h = self.conv2(group_norm_act(self.norm2, self.conv1(h), act_fn=_swish))
         return sc + h
 
@@ -207,13 +213,17 @@ class _Level(nn.Module):
 
 class UpConv(nn.Module):
     """model.py:42-58."""
+    wino = None              # routing of the convolution, as ConvUp.wino
 
     def __init__(self, ch):
         super().__init__()
         self.conv = nn.Conv2d(ch, ch, 3, padding=1)
 
     def forward(self, x):
-        return self.conv(F.interpolate(x, scale_factor=2.0, mode='nearest'))
+        x = F.interpolate(x, scale_factor=2.0, mode='nearest')
+        if fused_glue(x, self.conv.weight, self.conv.bias):
+            return conv_bias(self.conv, x, self.wino)
+        return self.conv(x)
 
 
 class VQDecoder(nn.Module):
@@ -374,6 +384,33 @@ class LatentDiffusion(nn.Module):
             raise KeyError(f'{path}: {len(missing)} keys of the latent model are missing, e.g. {missing[:3]}')
         self.load_state_dict(take)
         return sorted(set(sd) - set(take))
+
+
+def conv3x3_shapes(which):
+    """[(C, K, resolution, count)] of every 3x3 stride-1 padding-1 Conv2d call of one forward pass of the FFHQ latent
+    model's score network (which = 'unet': LDMUNet(**FFHQ_LDM_UNET)) or first-stage decoder ('decoder':
+    VQDecoder(**FFHQ_VQ_F4['ddconfig'])) on a [1, 3, 64, 64] latent, ordered by falling resolution, then C, then K: the walk
+    of unet.conv3x3_shapes (meta device, a forward hook on every Conv2d).  tools/conv_bench.py --latent and the latent rows
+    of the Winograd routing tables rest on this list."""
+    if which not in ('unet', 'decoder'):
+        raise ValueError(f"conv3x3_shapes: 'unet' or 'decoder', got {which!r}")
+    with torch.device('meta'):
+        model = LDMUNet(**FFHQ_LDM_UNET) if which == 'unet' else VQDecoder(**FFHQ_VQ_F4['ddconfig'])
+    seen, hooks = {}, []
+
+    def hook(mod, args, out):
+        key = (mod.in_channels, mod.out_channels, args[0].shape[-1])
+        seen[key] = seen.get(key, 0) + 1
+    for mod in model.modules():
+        if isinstance(mod, nn.Conv2d) and tuple(mod.kernel_size) == (3, 3) and tuple(mod.stride) == (1, 1) \
+                and mod.padding == (1, 1):
+            hooks.append(mod.register_forward_hook(hook))
+    with torch.no_grad():
+        z = torch.empty(1, 3, 64, 64, device='meta')
+        model(z, torch.zeros(1, device='meta')) if which == 'unet' else model(z)
+    for h in hooks:
+        h.remove()
+    return [(c, k, res, n) for (c, k, res), n in sorted(seen.items(), key=lambda kv: (-kv[0][2], kv[0][0], kv[0][1]))]
 
 
 def _params(cfg):

@@ -198,8 +198,9 @@ class _Conv3x3Wino(torch.autograd.Function):
         ctx.route_bwd, ctx.x_shape = route[1], tuple(x.shape)
         if route[0]:
             return K.conv3x3_wino(xc, weight, bias, add)
-        h = F.conv2d(xc, weight, None, 1, 1)
-        return h if add is None else K.bias_add2(h, bias, add)
+        if add is None:                                     # bias-only callers (conv_bias): the vendor kernel adds it
+            return F.conv2d(xc, weight, bias, 1, 1)
+        return K.bias_add2(F.conv2d(xc, weight, None, 1, 1), bias, add)
 
     @staticmethod
     def backward(ctx, g):
@@ -223,9 +224,10 @@ def wino_route(conv, x, wino=None):
         return None
     n, c, h, w = x.shape
     k = conv.out_channels
-    fwd, bwd = K.conv3x3_wino_covers(n, c, k, h, w), K.conv3x3_wino_covers(n, k, c, h, w)
-    if not wino:
-        fwd, bwd = fwd and K.conv3x3_wino_prefers(0, n, c, k, h, w), bwd and K.conv3x3_wino_prefers(1, n, k, c, h, w)
+    fwd, bwd = K.conv3x3_wino_k32_covers(n, c, k, h, w), K.conv3x3_wino_k32_covers(n, k, c, h, w)
+    if not wino:                                        # a shape is in one table only: k32's rows have k % 64 == 32
+        fwd = fwd and (K.conv3x3_wino_prefers(0, n, c, k, h, w) or K.conv3x3_wino_k32_prefers(0, n, c, k, h, w))
+        bwd = bwd and (K.conv3x3_wino_prefers(1, n, k, c, h, w) or K.conv3x3_wino_k32_prefers(1, n, k, c, h, w))
     bwd = bwd and x.requires_grad and torch.is_grad_enabled()
     return (fwd, bwd) if fwd or bwd else None
 
@@ -236,6 +238,15 @@ def conv_nobias(conv, x, wino=None):
     if route is not None:
         return _Conv3x3Wino.apply(x, conv.weight, None, None, route)
     return F.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
+
+
+def conv_bias(conv, x, wino=None):
+    """conv(x) with its bias and no residual (the convolution behind an upsample): the bias is added in the Winograd
+    kernel's epilogue where that takes the forward pass, by the vendor library's convolution otherwise."""
+    route = wino_route(conv, x, wino)
+    if route is not None:
+        return _Conv3x3Wino.apply(x, conv.weight, conv.bias, None, route)
+    return F.conv2d(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups)
 
 
 def conv_bias_add2(conv, x, other, wino=None):

@@ -6,14 +6,18 @@ median of 3 rounds of 10 event-timed launches per variant on rotating buffers th
 Cache.  Prints microseconds, the ratio kernel / F.conv2d and
 TFLOP/s in direct-convolution terms (2 * 9 * N * C * K * H * W).  Rows at or below 0.90 are what
 nhmc_conv3x3_wino_prefers and nhmc_conv3x3_wino_narrow_prefers may list.
-Usage: python tools/conv_bench.py [chains] [rounds] [--epilogue] [--only=C,K,res]
---epilogue adds, per forward row, the kernel with its (acc + bias) + add epilogue against kernel + k_bias_add2."""
+Usage: python tools/conv_bench.py [chains] [rounds] [--epilogue] [--only=C,K,res] [--latent]
+--epilogue adds, per forward row, the kernel with its (acc + bias) + add epilogue against kernel + k_bias_add2.
+--latent measures the latent sampler's two networks instead (ldm.conv3x3_shapes; chains defaults to 16, the chain count of
+BASELINE configs[4]): the score network's covered shapes forward only (it is evaluated without gradient), the first-stage
+decoder's forward and backward-data.  Rows at or below 0.90 with K % 64 == 32 are what nhmc_conv3x3_wino_k32_prefers may
+list; the others go to the two tables above."""
 import sys
 import torch
 import torch.nn.functional as F
 sys.path.insert(0, '.')
 import nhmc.kernels as K
-from nhmc import unet
+from nhmc import ldm, unet
 
 
 def default_shapes(chains=64):
@@ -21,6 +25,16 @@ def default_shapes(chains=64):
     backward-data at this chain count, in the order of unet.conv3x3_shapes()."""
     return tuple((c, k, res) for c, k, res, _ in unet.conv3x3_shapes()
                  if K.conv3x3_wino_covers(chains, c, k, res, res) and K.conv3x3_wino_covers(chains, k, c, res, res))
+
+
+def latent_shapes(chains=16):
+    """(C, K, resolution, directions) of the 3x3 convolutions of the latent sampler's networks that the kernel covers at this
+    chain count, in the order of ldm.conv3x3_shapes: the U-Net's forward only (directions = (False,)), then the decoder's,
+    forward and backward-data (covered in both)."""
+    rows = [(c, k, res, (False,)) for c, k, res, _ in ldm.conv3x3_shapes('unet') if K.conv3x3_wino_k32_covers(chains, c, k, res, res)]
+    rows += [(c, k, res, (False, True)) for c, k, res, _ in ldm.conv3x3_shapes('decoder')
+             if K.conv3x3_wino_k32_covers(chains, c, k, res, res) and K.conv3x3_wino_k32_covers(chains, k, c, res, res)]
+    return tuple(rows)
 
 
 def timeit(f, bufs, n=10):
@@ -36,16 +50,17 @@ def timeit(f, bufs, n=10):
 def main():
     dev = torch.device('cuda')
     args = [a for a in sys.argv[1:] if not a.startswith('--')]
-    B = int(args[0]) if len(args) > 0 else 64
+    LATENT = '--latent' in sys.argv
+    B = int(args[0]) if len(args) > 0 else 16 if LATENT else 64
     ROUNDS = int(args[1]) if len(args) > 1 else 3
     EPILOGUE = '--epilogue' in sys.argv
-    SHAPES = default_shapes(B)
+    SHAPES = latent_shapes(B) if LATENT else tuple(s + ((False, True),) for s in default_shapes(B))
     print(f'chains {B}, rounds {ROUNDS}: us wino | us F.conv2d | ratio | TFLOP/s wino | TFLOP/s F.conv2d')
     ONLY = [tuple(int(v) for v in a[7:].split(',')) for a in sys.argv[1:] if a.startswith('--only=')]
-    for Cc, Kk, res in ONLY or SHAPES:
+    for Cc, Kk, res, directions in [o + ((False, True),) for o in ONLY] or SHAPES:
         w = (torch.randn(Kk, Cc, 3, 3, device=dev) / (9 * Cc) ** 0.5)
         flop = 2 * 9 * B * Cc * Kk * res * res
-        for backward in (False, True):
+        for backward in directions:
             cin = Kk if backward else Cc
             nbuf = max(2, -(-(320 << 20) // (B * cin * res * res * 4)))
             bufs = [torch.randn(B, cin, res, res, device=dev) for _ in range(nbuf)]
