@@ -39,6 +39,26 @@ constexpr int WC_CHUNK = 8;                      // input channels per LDS stage
 constexpr int WC_OPER = 16 * WC_CHUNK * 64;      // floats of one operand (U or V) of one stage
 constexpr int WC_LDS_BYTES = 4 * WC_OPER * 4;    // 2 stages x (U + V)
 
+// Phase stamps, in the diagnostic build of tools/wino_stamps.hip only (NHMC_WINO_STAMPS; libnhmc.so holds none): every wave
+// keeps the shader clock of its phase boundaries in scalar registers and lane 0 writes them behind the epilogue, 24 values
+// per wave, into a buffer of their own.  WC_T64: 0 kernel start, 1 behind the prologue barrier, 2 loop start, 3 loop end,
+// 4 kernel end; 5, 6 the constant-rate clock at loop start and end.  WC_T32 (low words, of chunk nhmc_wino_stamp_chunk
+// only): 0 .. 6 the head of unit u, 7 / 8 around the wait for the patch, 9 / 10 around the chunk's barrier, 11 the head
+// of unit 7 (10 -> 11 held all 32 loads of a chunk while they were issued in one piece), 12 the chunk's end
+#ifdef NHMC_WINO_STAMPS
+__device__ unsigned long long* nhmc_wino_stamps;
+__device__ int nhmc_wino_stamp_chunk;
+#define WC_FENCE() __builtin_amdgcn_sched_barrier(0)
+#define WC_T64(i) do { WC_FENCE(); t64[i] = __builtin_amdgcn_s_memtime(); WC_FENCE(); } while (0)
+#define WC_R64(i) do { WC_FENCE(); t64[i] = __builtin_amdgcn_s_memrealtime(); WC_FENCE(); } while (0)
+#define WC_T32(i) do { WC_FENCE(); const unsigned now_ = (unsigned)__builtin_amdgcn_s_memtime(); \
+                       t32[i] = ch == stamp_ch ? now_ : t32[i]; WC_FENCE(); } while (0)
+#else
+#define WC_T64(i)
+#define WC_R64(i)
+#define WC_T32(i)
+#endif
+
 struct WinoArgs {
   const float* x; const float* U; const float* bias; const float* add; float* y;
   int C, K, H, W, row_blocks, col_blocks;
@@ -52,6 +72,12 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
   const int kh = wave & 1, th = wave >> 1;
   const int C = a.C, K = a.K, H = a.H, W = a.W, HW = H * W;
+#ifdef NHMC_WINO_STAMPS
+  unsigned long long t64[7] = {};
+  unsigned t32[13] = {};
+  const int stamp_ch = nhmc_wino_stamp_chunk < C / WC_CHUNK ? nhmc_wino_stamp_chunk : C / WC_CHUNK - 1;
+#endif
+  WC_T64(0);
 
   // the K blocks of one spatial block, then the next spatial block, follow each other on one XCD (they share the input)
   const int total = gridDim.x;
@@ -72,7 +98,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
   // ---- loader roles: thread (lc, ltx) transforms channel lc of the chunk for the two tiles of tile column ltx % TC of
   // row pair ltx / TC
   const int lc = tid >> 5, ltx = tid & 31;
-  int voff[6][4];
+  unsigned voff[6][4];                                   // bytes from the chunk's first channel: the load's 32-bit offset
   unsigned okmask = 0;
 #pragma unroll
   for (int r = 0; r < 6; ++r) {
@@ -82,7 +108,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
     for (int s = 0; s < 4; ++s) {
       const int col = w0 + 2 * (ltx % TC) - 1 + s;
       const bool ok = rok && (unsigned)col < (unsigned)W;
-      voff[r][s] = ok ? lc * HW + row * W + col : 0;
+      voff[r][s] = ok ? 4u * (unsigned)(lc * HW + row * W + col) : 0u;
       okmask |= ok ? 1u << (r * 4 + s) : 0u;
     }
   }
@@ -93,20 +119,29 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
   const int uw = (tid & ~3) * 4 + (((tid & 3) ^ ((tid >> 4) & 3)) << 2);          // row tid >> 2, swizzled granule
   const int vw = (lc * 64 + ltx) * 16, vswz = (ltx >> 2) & 3;
 
+  // A chunk's 32 loads per thread, numbered in the order they are issued and consumed: 0 .. 23 the patch (row i / 4, column
+  // i % 4; all of it is needed at unit 3), 24 .. 31 the U pieces (piece 2 b, 2 b + 1 at unit 3 + b).  Scalar base + 32-bit
+  // lane offset, no address arithmetic per load.  The offset passes through an empty asm next to its load: hoisted out of the
+  // loop, its zero extension became a register pair per load (48 registers) and a 64-bit add in front of every load
   float xr[6][4];
   nhmc_v4f ur[8];
-  auto issue_loads = [&](int ch) {
-    const float* xs = xn + (int64_t)ch * WC_CHUNK * HW;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) xr[r][s] = xs[voff[r][s]];
-    const char* us = un + (int64_t)ch * WC_CHUNK * K * 64;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      if (!TAIL || u_row_ok) ur[i] = *reinterpret_cast<const nhmc_v4f*>(us + (int64_t)i * K * 64 + uoff);
-      else ur[i] = nhmc_v4f{0.0f, 0.0f, 0.0f, 0.0f};
+  auto load_one = [&](int ch, int i) {
+    if (i < 24) {
+      const char* xs = reinterpret_cast<const char*>(xn + (int64_t)ch * WC_CHUNK * HW);
+      unsigned off = voff[i >> 2][i & 3];
+      asm volatile("" : "+v"(off));
+      xr[i >> 2][i & 3] = *reinterpret_cast<const float*>(xs + off);
+    } else {
+      const char* us = un + (int64_t)ch * WC_CHUNK * K * 64 + (int64_t)(i - 24) * K * 64;
+      unsigned off = uoff;
+      asm volatile("" : "+v"(off));
+      if (!TAIL || u_row_ok) ur[i - 24] = *reinterpret_cast<const nhmc_v4f*>(us + off);
+      else ur[i - 24] = nhmc_v4f{0.0f, 0.0f, 0.0f, 0.0f};
     }
+  };
+  auto issue_loads = [&](int ch, int first, int last) {
+#pragma unroll
+    for (int i = first; i < last; ++i) load_one(ch, i);
   };
   // the loaded patch is first touched here, three units after its loads were issued: without the pin the selects and the
   // first-level differences of all four columns move to the head of the chunk, and the chunk starts with a wait on the loads
@@ -168,47 +203,84 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
       if (!TAIL || !idle) acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u & 1][j], bv[u & 1][j], acc[f], 0, 0, 0);
     }
   };
+  // The loads of chunk `cl` are spread over the gaps between the MFMAs of the four units that follow the barrier, at most two
+  // per gap, instead of all 32 behind the barrier (where the four waves of the CU, released together, queued 128 of them on
+  // the one address path and no MFMA issued until the last was accepted): unit 7 the patch's rows 0 - 2, unit 0 of the next
+  // body its rows 3 - 5 and U pieces 0, 1, unit 1 pieces 2 - 5, unit 2 pieces 6, 7.  Every gap is fenced, so the placement
+  // is the scheduler's too
+  auto unit_loading = [&](int u, int cl) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int f = 8 * (u & 1) + j;
+      if (!TAIL || !idle) acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u & 1][j], bv[u & 1][j], acc[f], 0, 0, 0);
+      if (u == 7) issue_loads(cl, (3 * j) / 2, (3 * j + 3) / 2);                     // 1, 2, 1, 2, ... : 12 loads
+      if (u == 0 && j < 6) issue_loads(cl, 12 + 2 * j, 14 + 2 * j);
+      if (u == 0 && j >= 6) issue_loads(cl, 18 + j, 19 + j);                         // pieces 0, 1
+      if (u == 1 && (j & 1) == 0) issue_loads(cl, 26 + j / 2, 27 + j / 2);           // pieces 2 .. 5
+      if (u == 2 && (j == 0 || j == 2)) issue_loads(cl, 30 + j / 2, 31 + j / 2);     // pieces 6, 7
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
 
-  issue_loads(0);
+  issue_loads(0, 0, 32);
 #pragma unroll
   for (int b = 0; b < 4; ++b) stage_part(0, b);
   __syncthreads();
-  issue_loads(1 < chunks ? 1 : 0);
+  WC_T64(1);
+  int cl = 1 < chunks ? 1 : 0;                      // the chunk being loaded
+  issue_loads(cl, 0, 12);
   fetch(0, 0, av[0], bv[0]);
   // ONE instance of the chunk body (a second one behind the loop made the register allocator shuffle the 256 accumulators
   // through scratch): the last chunk stages itself once more into the idle buffer and reads unit 0 of it, which nobody
   // uses.  do-while: the accumulators reach the epilogue from the loop only (C >= 8), not merged with their zero state
   int ch = 0, st = 0;
+  WC_T64(2);
+  WC_R64(5);
   do {
 #pragma unroll
     for (int u = 0; u < 7; ++u) {
+      WC_T32(u);
       fetch(st, u + 1, av[(u + 1) & 1], bv[(u + 1) & 1]);
       __builtin_amdgcn_sched_barrier(0);
-      unit(u);
-      if (u == 3) pin_patch();
+      if (u < 3) unit_loading(u, cl);
+      else unit(u);
+      if (u == 3) {
+        WC_T32(7);
+        pin_patch();
+        WC_T32(8);
+      }
       if (u >= 3) stage_part(st ^ 1, u - 3);
     }
+    WC_T32(9);
     __syncthreads();                                // stage st ^ 1 is complete, and every wave is done reading stage st
+    WC_T32(10);
     st ^= 1;
-    issue_loads(ch + 2 < chunks ? ch + 2 : chunks - 1);
+    cl = ch + 2 < chunks ? ch + 2 : chunks - 1;
+    WC_T32(11);
     fetch(st, 0, av[0], bv[0]);
     __builtin_amdgcn_sched_barrier(0);
-    unit(7);
+    unit_loading(7, cl);
+    WC_T32(12);
   } while (++ch < chunks);
+  WC_T64(3);
+  WC_R64(6);
 
-  // ---- Y = A^T M A per (channel, tile), epilogue, row segments of 8 TC bytes (TC lanes x float2).  bias and add are loaded
+  // ---- Y = A^T M A per (channel, tile), epilogue, row segments of 8 TC bytes (TC / 2 lanes x float4).  bias and add are loaded
   // for all 16 channels of the lane before the transform (the loaders' registers are free), behind one wait
   if (TAIL && idle) return;
   const int oh = h0 + 4 * (lr / TC) + 2 * th, ow = w0 + 2 * (lr % TC);
   const bool has_bias = a.bias != nullptr, has_add = a.add != nullptr;
   const int k0 = kb * WC_KBLK + kh * 32 + 4 * lh;
-  const int64_t at0 = (((int64_t)n * K + k0) * H + oh) * W + ow;
+  // the lane's 2 x 2 patch and that of lane lr ^ 1, two columns further, are exchanged by halves (DPP, within the quad): the
+  // even lane stores row 0 and the odd lane row 1 of both, four adjacent columns = one 16-byte store per channel
+  const bool odd = lr & 1;
+  const int64_t at0 = (((int64_t)n * K + k0) * H + oh) * W + ow + (odd ? W - 2 : 0);
   float bc[16];
-  wc_v2f ad[16][2];
+  nhmc_v4f ad[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     bc[r] = 0.0f;
-    ad[r][0] = ad[r][1] = wc_v2f{0.0f, 0.0f};
+    ad[r] = nhmc_v4f{0.0f, 0.0f, 0.0f, 0.0f};
   }
   if (has_bias) {
 #pragma unroll
@@ -217,10 +289,11 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
   if (has_add) {
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-        ad[r][i] = *reinterpret_cast<const wc_v2f*>(a.add + at0 + (int64_t)((r & 3) + 8 * (r >> 2)) * HW + i * W);
+      ad[r] = *reinterpret_cast<const nhmc_v4f*>(a.add + at0 + (int64_t)((r & 3) + 8 * (r >> 2)) * HW);
   }
+  auto neighbour = [](float v) {                    // lane ^ 1's value: quad_perm [1, 0, 3, 2]
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
+  };
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -230,18 +303,31 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
       t[0][b] = (acc[4 * b + 0][r] + acc[4 * b + 1][r]) + acc[4 * b + 2][r];
       t[1][b] = (acc[4 * b + 1][r] - acc[4 * b + 2][r]) - acc[4 * b + 3][r];
     }
+    wc_v2f o[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      wc_v2f o;
-      o.x = (t[i][0] + t[i][1]) + t[i][2];
-      o.y = (t[i][1] - t[i][2]) - t[i][3];
-      o.x = has_bias ? o.x + bc[r] : o.x;
-      o.y = has_bias ? o.y + bc[r] : o.y;
-      o.x = has_add ? o.x + ad[r][i].x : o.x;
-      o.y = has_add ? o.y + ad[r][i].y : o.y;
-      __builtin_nontemporal_store(o, reinterpret_cast<wc_v2f*>(a.y + at0 + (int64_t)((r & 3) + 8 * (r >> 2)) * HW + i * W));
+      o[i].x = (t[i][0] + t[i][1]) + t[i][2];
+      o[i].y = (t[i][1] - t[i][2]) - t[i][3];
+      o[i].x = has_bias ? o[i].x + bc[r] : o[i].x;
+      o[i].y = has_bias ? o[i].y + bc[r] : o[i].y;
     }
+    const wc_v2f keep = odd ? o[1] : o[0], send = odd ? o[0] : o[1];
+    const wc_v2f got = {neighbour(send.x), neighbour(send.y)};
+    nhmc_v4f v;
+    v.x = odd ? got.x : keep.x; v.y = odd ? got.y : keep.y; v.z = odd ? keep.x : got.x; v.w = odd ? keep.y : got.y;
+    if (has_add) v += ad[r];
+    __builtin_nontemporal_store(v, reinterpret_cast<nhmc_v4f*>(a.y + at0 + (int64_t)((r & 3) + 8 * (r >> 2)) * HW));
   }
+  WC_T64(4);
+#ifdef NHMC_WINO_STAMPS
+  if (nhmc_wino_stamps && lane == 0) {
+    unsigned long long* out = nhmc_wino_stamps + ((size_t)blockIdx.x * 4 + wave) * 24;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) out[i] = t64[i];
+#pragma unroll
+    for (int i = 0; i < 13; ++i) out[7 + i] = t32[i];
+  }
+#endif
 }
 
 // U[ci][ko][f = 4 b + a] = (G g G^T)[a][b], G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1].
@@ -334,33 +420,33 @@ extern "C" int nhmc_conv3x3_wino_narrow_covers(int n, int c, int k, int h, int w
 // F.conv2d's time at 64 chains on MI355X in the same process (the figure behind each row is the larger of the median and
 // the best-of-rounds ratio): a tie is never routed.  Other batch sizes follow the same rows; only n = 64 was measured.
 // The first table holds the 3x3 convolutions of unet.FFHQ_CONFIG (unet.conv3x3_shapes()) with widths that are multiples of
-// 64, all measured in one run: profiles/r07_wino_conv_routing.txt.  The second holds shapes that FFHQ_CONFIG never runs;
+// 64, all measured in one run: profiles/r09_wino_conv_routing.txt.  The second holds shapes that FFHQ_CONFIG never runs;
 // they are kept because they are real measurements (profiles/r05_wino_conv_roofline.txt) and serve other channel multipliers.
 extern "C" int nhmc_conv3x3_wino_prefers(int backward, int n, int c, int k, int h, int w) {
   if (!wc_covers(n, c, k, h, w) || h != w) return 0;
   static const WcRow network[] = {
-      {0, 128, 128, 256},   // 128->128 forward: 0.676
-      {1, 128, 128, 256},   // 128->128 backward-data: 0.651
-      {0, 256, 128, 256},   // 256->128 forward: 0.678
-      {1, 128, 256, 256},   // 256->128 backward-data: 0.653
-      {0, 128, 128, 128},   // 128->128 forward: 0.666
-      {1, 128, 128, 128},   // 128->128 backward-data: 0.665
-      {0, 256, 128, 128},   // 256->128 forward: 0.681
-      {1, 128, 256, 128},   // 256->128 backward-data: 0.655
-      {0, 256, 256, 128},   // 256->256 forward: 0.695
-      {1, 256, 256, 128},   // 256->256 backward-data: 0.680
-      {0, 384, 128, 128},   // 384->128 forward: 0.669
-      {1, 128, 384, 128},   // 384->128 backward-data: 0.655
-      {0, 128, 128, 64},   // 128->128 forward: 0.693
-      {1, 128, 128, 64},   // 128->128 backward-data: 0.666
-      {0, 128, 256, 64},   // 128->256 forward: 0.688
-      {1, 256, 128, 64},   // 128->256 backward-data: 0.668
-      {0, 256, 256, 64},   // 256->256 forward: 0.689
-      {1, 256, 256, 64},   // 256->256 backward-data: 0.657
-      {0, 384, 256, 64},   // 384->256 forward: 0.699
-      {1, 256, 384, 64},   // 384->256 backward-data: 0.688
-      {0, 512, 256, 64},   // 512->256 forward: 0.703
-      {1, 256, 512, 64},   // 512->256 backward-data: 0.696
+      {0, 128, 128, 256},   // 128->128 forward: 0.577
+      {1, 128, 128, 256},   // 128->128 backward-data: 0.556
+      {0, 256, 128, 256},   // 256->128 forward: 0.566
+      {1, 128, 256, 256},   // 256->128 backward-data: 0.562
+      {0, 128, 128, 128},   // 128->128 forward: 0.579
+      {1, 128, 128, 128},   // 128->128 backward-data: 0.576
+      {0, 256, 128, 128},   // 256->128 forward: 0.575
+      {1, 128, 256, 128},   // 256->128 backward-data: 0.564
+      {0, 256, 256, 128},   // 256->256 forward: 0.590
+      {1, 256, 256, 128},   // 256->256 backward-data: 0.578
+      {0, 384, 128, 128},   // 384->128 forward: 0.569
+      {1, 128, 384, 128},   // 384->128 backward-data: 0.560
+      {0, 128, 128, 64},   // 128->128 forward: 0.596
+      {1, 128, 128, 64},   // 128->128 backward-data: 0.575
+      {0, 128, 256, 64},   // 128->256 forward: 0.597
+      {1, 256, 128, 64},   // 128->256 backward-data: 0.575
+      {0, 256, 256, 64},   // 256->256 forward: 0.604
+      {1, 256, 256, 64},   // 256->256 backward-data: 0.568
+      {0, 384, 256, 64},   // 384->256 forward: 0.596
+      {1, 256, 384, 64},   // 384->256 backward-data: 0.593
+      {0, 512, 256, 64},   // 512->256 forward: 0.598
+      {1, 256, 512, 64},   // 512->256 backward-data: 0.601
   };
   static const WcRow elsewhere[] = {           // not in FFHQ_CONFIG
       {0, 384, 128, 256},   // 384->128 forward: 0.696
@@ -380,14 +466,14 @@ extern "C" int nhmc_conv3x3_wino_prefers(int backward, int n, int c, int k, int 
       {0, 1024, 512, 64},   // 1024->512 forward: 0.734
       {1, 512, 1024, 64},   // 1024->512 backward-data: 0.742
   };
-  // latent networks, measured at 16 chains (tools/conv_bench.py --latent, profiles/r08_wino_conv_latent.txt): the shapes of
+  // latent networks, measured at 16 chains (tools/conv_bench.py --latent, profiles/r09_wino_conv_latent.txt): the shapes of
   // ldm.conv3x3_shapes with K % 64 == 0 that no row above holds.  The score network runs without gradient: forward only
   static const WcRow latent[] = {
-      {0, 448, 448, 64},    // U-Net 448->448 forward: 0.646
-      {0, 256, 256, 256},   // decoder 256->256 forward: 0.692
-      {1, 256, 256, 256},   // decoder 256->256 backward-data: 0.679
-      {0, 512, 512, 128},   // decoder 512->512 forward: 0.715
-      {1, 512, 512, 128},   // decoder 512->512 backward-data: 0.710
+      {0, 448, 448, 64},    // U-Net 448->448 forward: 0.565
+      {0, 256, 256, 256},   // decoder 256->256 forward: 0.588
+      {1, 256, 256, 256},   // decoder 256->256 backward-data: 0.576
+      {0, 512, 512, 128},   // decoder 512->512 forward: 0.610
+      {1, 512, 512, 128},   // decoder 512->512 backward-data: 0.603
   };
   return wc_listed(network, backward, c, k, h) || wc_listed(elsewhere, backward, c, k, h) || wc_listed(latent, backward, c, k, h);
 }
@@ -396,54 +482,54 @@ extern "C" int nhmc_conv3x3_wino_prefers(int backward, int n, int c, int k, int 
 extern "C" int nhmc_conv3x3_wino_narrow_prefers(int backward, int n, int c, int k, int h, int w) {
   if (!wc_narrow_covers(n, c, k, h, w) || h != w) return 0;
   static const WcRow network[] = {
-      {0, 256, 256, 32},   // 256->256 forward: 0.706
-      {1, 256, 256, 32},   // 256->256 backward-data: 0.656
-      {0, 512, 256, 32},   // 512->256 forward: 0.668
-      {1, 256, 512, 32},   // 512->256 backward-data: 0.646
-      {0, 512, 512, 32},   // 512->512 forward: 0.710
-      {1, 512, 512, 32},   // 512->512 backward-data: 0.704
-      {0, 768, 256, 32},   // 768->256 forward: 0.655
-      {1, 256, 768, 32},   // 768->256 backward-data: 0.687
-      {0, 256, 256, 16},   // 256->256 forward: 0.716
-      {1, 256, 256, 16},   // 256->256 backward-data: 0.660
-      {0, 256, 512, 16},   // 256->512 forward: 0.701
-      {1, 512, 256, 16},   // 256->512 backward-data: 0.703
-      {0, 512, 512, 16},   // 512->512 forward: 0.712
-      {1, 512, 512, 16},   // 512->512 backward-data: 0.702
-      {0, 768, 512, 16},   // 768->512 forward: 0.703
-      {1, 512, 768, 16},   // 768->512 backward-data: 0.701
-      {0, 1024, 512, 16},   // 1024->512 forward: 0.715
-      {1, 512, 1024, 16},   // 1024->512 backward-data: 0.776
+      {0, 256, 256, 32},   // 256->256 forward: 0.578
+      {1, 256, 256, 32},   // 256->256 backward-data: 0.574
+      {0, 512, 256, 32},   // 512->256 forward: 0.580
+      {1, 256, 512, 32},   // 512->256 backward-data: 0.576
+      {0, 512, 512, 32},   // 512->512 forward: 0.615
+      {1, 512, 512, 32},   // 512->512 backward-data: 0.613
+      {0, 768, 256, 32},   // 768->256 forward: 0.579
+      {1, 256, 768, 32},   // 768->256 backward-data: 0.600
+      {0, 256, 256, 16},   // 256->256 forward: 0.610
+      {1, 256, 256, 16},   // 256->256 backward-data: 0.565
+      {0, 256, 512, 16},   // 256->512 forward: 0.597
+      {1, 512, 256, 16},   // 256->512 backward-data: 0.599
+      {0, 512, 512, 16},   // 512->512 forward: 0.606
+      {1, 512, 512, 16},   // 512->512 backward-data: 0.586
+      {0, 768, 512, 16},   // 768->512 forward: 0.595
+      {1, 512, 768, 16},   // 768->512 backward-data: 0.604
+      {0, 1024, 512, 16},   // 1024->512 forward: 0.603
+      {1, 512, 1024, 16},   // 1024->512 backward-data: 0.597
   };
-  // latent networks, measured at 16 chains (profiles/r08_wino_conv_latent.txt): the LDM U-Net's K = 448 / 896 layers, forward
+  // latent networks, measured at 16 chains (profiles/r09_wino_conv_latent.txt): the LDM U-Net's K = 448 / 896 layers, forward
   static const WcRow latent[] = {
-      {0, 224, 448, 32},    // 224->448 forward: 0.752
-      {0, 448, 448, 32},    // 448->448 forward: 0.743
-      {0, 672, 448, 32},    // 672->448 forward: 0.743
-      {0, 896, 448, 32},    // 896->448 forward: 0.728
-      {0, 1120, 448, 32},   // 1120->448 forward: 0.736
-      {0, 896, 896, 16},    // 896->896 forward: 0.675
+      {0, 224, 448, 32},    // 224->448 forward: 0.655
+      {0, 448, 448, 32},    // 448->448 forward: 0.642
+      {0, 672, 448, 32},    // 672->448 forward: 0.645
+      {0, 896, 448, 32},    // 896->448 forward: 0.640
+      {0, 1120, 448, 32},   // 1120->448 forward: 0.638
+      {0, 896, 896, 16},    // 896->896 forward: 0.570
   };
   return wc_listed(network, backward, c, k, h) || wc_listed(latent, backward, c, k, h);
 }
 
 // K % 64 == 32 only; same rule, measured at 16 chains (the latent sampler's chain count) by tools/conv_bench.py --latent:
-// profiles/r08_wino_conv_latent.txt.  The rows are the LDM U-Net's K = 224 / 672 layers, forward only (it runs without
+// profiles/r09_wino_conv_latent.txt.  The rows are the LDM U-Net's K = 224 / 672 layers, forward only (it runs without
 // gradient).  At 16 x 16 a tail launch has 16 x 11 = 176 workgroups on 256 CUs, one in eleven of them half empty.
 extern "C" int nhmc_conv3x3_wino_k32_covers(int n, int c, int k, int h, int w) { return wc_k32_covers(n, c, k, h, w); }
 
 extern "C" int nhmc_conv3x3_wino_k32_prefers(int backward, int n, int c, int k, int h, int w) {
   if (!wc_k32_covers(n, c, k, h, w) || h != w || k % WC_KBLK == 0) return 0;
   static const WcRow latent[] = {
-      {0, 224, 224, 64},    // 224->224 forward: 0.753
-      {0, 448, 224, 64},    // 448->224 forward: 0.742
-      {0, 672, 224, 64},    // 672->224 forward: 0.740
-      {0, 672, 672, 32},    // 672->672 forward: 0.697
-      {0, 448, 672, 16},    // 448->672 forward: 0.873
-      {0, 672, 672, 16},    // 672->672 forward: 0.864
-      {0, 1120, 672, 16},   // 1120->672 forward: 0.854
-      {0, 1344, 672, 16},   // 1344->672 forward: 0.859
-      {0, 1568, 672, 16},   // 1568->672 forward: 0.848
+      {0, 224, 224, 64},    // 224->224 forward: 0.710
+      {0, 448, 224, 64},    // 448->224 forward: 0.699
+      {0, 672, 224, 64},    // 672->224 forward: 0.691
+      {0, 672, 672, 32},    // 672->672 forward: 0.662
+      {0, 448, 672, 16},    // 448->672 forward: 0.810
+      {0, 672, 672, 16},    // 672->672 forward: 0.808
+      {0, 1120, 672, 16},   // 1120->672 forward: 0.799
+      {0, 1344, 672, 16},   // 1344->672 forward: 0.798
+      {0, 1568, 672, 16},   // 1568->672 forward: 0.795
   };
   return wc_listed(latent, backward, c, k, h);
 }
