@@ -20,8 +20,9 @@
 // LDS: two buffers of U[8][64][16] + V[8][64][16] = 128 KB: a row (c, k or tile) is the 16 frequencies = 64 bytes, so a
 // lane fetches the eight A or B values of one MFMA group with two ds_read_b128.  Rows of 64 bytes alone would put the 16
 // lanes of a b128 group on 4 of the 16 slots of a bank row; the 16-byte granule g of row R is stored at granule
-// g ^ ((R >> 2) & 3), which spreads every group over all 16.  While chunk i is multiplied, chunk i + 1 is loaded into
-// registers, transformed and written to the other buffer.
+// g ^ wc_swz(R), which spreads every group of the read over all 16 and every 8-lane group of the stores (32 banks: the four
+// rows of one parity) over all 8 (tests/test_wino_swizzle_cpu.py enumerates both).  While chunk i is multiplied, chunk
+// i + 1 is loaded into registers, transformed and written to the other buffer.
 // K that is a multiple of 32 but not of 64 (template parameter TAIL, entry nhmc_conv3x3_wino_k32): ceil(K / 64) K blocks, the
 // last one half empty.  U keeps nhmc_wino_weights' layout [C][K][16] with K as it is; the tail block's loads of the upper
 // 32 rows are predicated off and zeros go to LDS instead, so nothing outside U is read.  A channel's MFMA chain is the same
@@ -39,12 +40,18 @@ constexpr int WC_CHUNK = 8;                      // input channels per LDS stage
 constexpr int WC_OPER = 16 * WC_CHUNK * 64;      // floats of one operand (U or V) of one stage
 constexpr int WC_LDS_BYTES = 4 * WC_OPER * 4;    // 2 stages x (U + V)
 
+// granule swizzle of operand row R, linear in the row's bits: bit 1 -> 01, bit 2 -> 10, bit 3 -> 11.  A bijection on the rows
+// {0, 12, 20, 24} + r and {4, 8, 16, 28} + r that share a quarter of the 64 banks in a ds_read_b128 lane group, and on the
+// four rows of one parity among 8 contiguous ones, which share a half of the 32 banks in a ds_write_b128 lane group
+__device__ __forceinline__ constexpr int wc_swz(int R) { return ((R >> 1) & 3) ^ (((R >> 3) & 1) ? 3 : 0); }
+
 // Phase stamps, in the diagnostic build of tools/wino_stamps.hip only (NHMC_WINO_STAMPS; libnhmc.so holds none): every wave
 // keeps the shader clock of its phase boundaries in scalar registers and lane 0 writes them behind the epilogue, 24 values
 // per wave, into a buffer of their own.  WC_T64: 0 kernel start, 1 behind the prologue barrier, 2 loop start, 3 loop end,
 // 4 kernel end; 5, 6 the constant-rate clock at loop start and end.  WC_T32 (low words, of chunk nhmc_wino_stamp_chunk
 // only): 0 .. 6 the head of unit u, 7 / 8 around the wait for the patch, 9 / 10 around the chunk's barrier, 11 the head
-// of unit 7 (10 -> 11 held all 32 loads of a chunk while they were issued in one piece), 12 the chunk's end
+// of unit 7 (10 -> 11 held all loads of a chunk while they were issued in one piece), 12 the chunk's end, 13 .. 16 the
+// heads of MFMAs 1, 3, 5, 7 of unit 4: behind the reads, the arithmetic, the V stores, the U stores of a staging unit
 #ifdef NHMC_WINO_STAMPS
 __device__ unsigned long long* nhmc_wino_stamps;
 __device__ int nhmc_wino_stamp_chunk;
@@ -74,7 +81,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
   const int C = a.C, K = a.K, H = a.H, W = a.W, HW = H * W;
 #ifdef NHMC_WINO_STAMPS
   unsigned long long t64[7] = {};
-  unsigned t32[13] = {};
+  unsigned t32[17] = {};
   const int stamp_ch = nhmc_wino_stamp_chunk < C / WC_CHUNK ? nhmc_wino_stamp_chunk : C / WC_CHUNK - 1;
 #endif
   WC_T64(0);
@@ -97,18 +104,31 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
 
   // ---- loader roles: thread (lc, ltx) transforms channel lc of the chunk for the two tiles of tile column ltx % TC of
   // row pair ltx / TC
-  const int lc = tid >> 5, ltx = tid & 31;
-  unsigned voff[6][4];                                   // bytes from the chunk's first channel: the load's 32-bit offset
+  // The 6 x 4 patch of the thread has its origin at column w0 + 2 t - 1, t = ltx % TC.  Its two middle columns, 2 t and
+  // 2 t + 1 of the block, are one 8-byte load per row: w0 + 2 t is even and W a multiple of 16, so the load is aligned and
+  // never leaves the row.  The outer columns are the neighbouring lanes' (the 32 lanes of one lc are contiguous in a wave):
+  // column 2 t - 1 is the .y of lane - 1 and column 2 t + 2 the .x of lane + 1, moved by DPP once the patch has arrived.
+  // Lanes t = 0 and t = TC - 1 have no such neighbour.  In the narrow geometries the block is the whole width and the
+  // missing column is the zero padding (okmask).  In the wide one it is the padding in the first / last column block and
+  // column w0 - 1 / w0 + 64 of the image otherwise: one 4-byte load per row, EDGE, whose address is that column in the two
+  // edge lanes and the lane's own column 2 t (in range, the line the 8-byte load fetches) in all the others
+  constexpr bool EDGE = TC == 32;
+  constexpr int NP = EDGE ? 12 : 6;                      // patch loads per thread and chunk
+  const int lc = tid >> 5, ltx = tid & 31, lt = ltx % TC;
+  unsigned voff[6], eoff[6];                             // bytes from the chunk's first channel: the load's 32-bit offset
   unsigned okmask = 0;
+  const int ecol = lt == 0 ? w0 - 1 : w0 + 2 * TC;       // meaningful in the edge lanes only
+  const bool eok = EDGE && (lt == 0 || lt == TC - 1) && (unsigned)ecol < (unsigned)W;
 #pragma unroll
   for (int r = 0; r < 6; ++r) {
     const int row = h0 + 4 * (ltx / TC) - 1 + r;
     const bool rok = (unsigned)row < (unsigned)H;
+    voff[r] = rok ? 4u * (unsigned)(lc * HW + row * W + w0 + 2 * lt) : 0u;
+    eoff[r] = rok ? 4u * (unsigned)(lc * HW + row * W + (eok ? ecol : w0 + 2 * lt)) : 0u;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const int col = w0 + 2 * (ltx % TC) - 1 + s;
+      const int col = w0 + 2 * lt - 1 + s;
       const bool ok = rok && (unsigned)col < (unsigned)W;
-      voff[r][s] = ok ? 4u * (unsigned)(lc * HW + row * W + col) : 0u;
       okmask |= ok ? 1u << (r * 4 + s) : 0u;
     }
   }
@@ -116,27 +136,31 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
   // U stage: the chunk's 8 x 64 rows of this K block are 8 contiguous pieces of 4 KB; thread takes float4 tid of piece i
   const char* un = reinterpret_cast<const char*>(a.U + (int64_t)kb * WC_KBLK * 16);
   const unsigned uoff = 16u * tid;
-  const int uw = (tid & ~3) * 4 + (((tid & 3) ^ ((tid >> 4) & 3)) << 2);          // row tid >> 2, swizzled granule
-  const int vw = (lc * 64 + ltx) * 16, vswz = (ltx >> 2) & 3;
+  const int uw = (tid & ~3) * 4 + (((tid & 3) ^ wc_swz(tid >> 2)) << 2);            // row tid >> 2, swizzled granule
+  const int vw = (lc * 64 + ltx) * 16, vswz = wc_swz(ltx);                          // rows lc * 64 + 32 ty + ltx
 
-  // A chunk's 32 loads per thread, numbered in the order they are issued and consumed: 0 .. 23 the patch (row i / 4, column
-  // i % 4; all of it is needed at unit 3), 24 .. 31 the U pieces (piece 2 b, 2 b + 1 at unit 3 + b).  Scalar base + 32-bit
-  // lane offset, no address arithmetic per load.  The offset passes through an empty asm next to its load: hoisted out of the
-  // loop, its zero extension became a register pair per load (48 registers) and a 64-bit add in front of every load
-  float xr[6][4];
+  // A chunk's NP + 8 loads per thread, numbered in the order they are issued and consumed: 0 .. NP - 1 the patch (row by row;
+  // with EDGE the row's 8-byte load, then its edge load; all of it is needed at unit 3), then the 8 U pieces (piece 2 b,
+  // 2 b + 1 at unit 3 + b).  Scalar base + 32-bit lane offset, no address arithmetic per load.  The offset passes through an
+  // empty asm next to its load: hoisted out of the loop, its zero extension became a register pair per load and a 64-bit
+  // add in front of every load
+  wc_v2f xm[6];                                          // columns 1, 2 of the patch
+  float xl[6], xq[6], xe[6];                             // columns 0 and 3 (behind exchange_patch), the edge loads
   nhmc_v4f ur[8];
   auto load_one = [&](int ch, int i) {
-    if (i < 24) {
+    if (i < NP) {
       const char* xs = reinterpret_cast<const char*>(xn + (int64_t)ch * WC_CHUNK * HW);
-      unsigned off = voff[i >> 2][i & 3];
+      const int r = EDGE ? i >> 1 : i;
+      unsigned off = EDGE && (i & 1) ? eoff[r] : voff[r];
       asm volatile("" : "+v"(off));
-      xr[i >> 2][i & 3] = *reinterpret_cast<const float*>(xs + off);
+      if (EDGE && (i & 1)) xe[r] = *reinterpret_cast<const float*>(xs + off);
+      else xm[r] = *reinterpret_cast<const wc_v2f*>(xs + off);
     } else {
-      const char* us = un + (int64_t)ch * WC_CHUNK * K * 64 + (int64_t)(i - 24) * K * 64;
+      const char* us = un + (int64_t)ch * WC_CHUNK * K * 64 + (int64_t)(i - NP) * K * 64;
       unsigned off = uoff;
       asm volatile("" : "+v"(off));
-      if (!TAIL || u_row_ok) ur[i - 24] = *reinterpret_cast<const nhmc_v4f*>(us + off);
-      else ur[i - 24] = nhmc_v4f{0.0f, 0.0f, 0.0f, 0.0f};
+      if (!TAIL || u_row_ok) ur[i - NP] = *reinterpret_cast<const nhmc_v4f*>(us + off);
+      else ur[i - NP] = nhmc_v4f{0.0f, 0.0f, 0.0f, 0.0f};
     }
   };
   auto issue_loads = [&](int ch, int first, int last) {
@@ -147,28 +171,59 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
   // first-level differences of all four columns move to the head of the chunk, and the chunk starts with a wait on the loads
   auto pin_patch = [&]() {
 #pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(xr[r][s]));
+    for (int r = 0; r < 6; ++r) {
+      asm volatile("" : "+v"(xm[r]));
+      if (EDGE) asm volatile("" : "+v"(xe[r]));
+    }
   };
-  auto d = [&](int r, int s) { return (okmask >> (r * 4 + s)) & 1u ? xr[r][s] : 0.0f; };
-  // column b of V = B^T d B for both tiles of the thread (one granule each), and a quarter of the U stage -> LDS stage `st`
-  auto stage_part = [&](int st, int b) {
-    float* Us = lds + st * 2 * WC_OPER;
-    float* Vs = Us + WC_OPER;
-    float e[6];
+  // the outer columns from the neighbouring lanes: wave_shr:1 gives lane l the value of lane l - 1, wave_shl:1 that of lane
+  // l + 1 (values are moved, not computed).  What a lane at t = 0 / t = TC - 1 receives is another tile row's or channel's
+  // and is never used: with EDGE the edge load takes its place, and where that column is outside the image, here as in the
+  // narrow geometries, okmask selects the padding's 0.0f
+  auto exchange_patch = [&]() {
 #pragma unroll
-    for (int r = 0; r < 6; ++r)
+    for (int r = 0; r < 6; ++r) {
+      xl[r] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(xm[r].y), 0x138, 0xF, 0xF, false));
+      xq[r] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(xm[r].x), 0x130, 0xF, 0xF, false));
+      if (EDGE) {
+        xl[r] = lt == 0 ? xe[r] : xl[r];
+        xq[r] = lt == TC - 1 ? xe[r] : xq[r];
+      }
+    }
+  };
+  auto d = [&](int r, int s) {
+    const float v = s == 0 ? xl[r] : s == 1 ? xm[r].x : s == 2 ? xm[r].y : xq[r];
+    return (okmask >> (r * 4 + s)) & 1u ? v : 0.0f;
+  };
+  // column b of V = B^T d B for both tiles of the thread (one granule each), and a quarter of the U stage -> LDS stage `st`
+  // in pieces, so that the staging units can place each between two MFMAs: the row differences e[r] of column b, the
+  // granule of tile ty from them with its store, and the store of one U piece
+  float e[6];
+  auto stage_rows = [&](int b, int first, int last) {
+#pragma unroll
+    for (int r = first; r < last; ++r)
       e[r] = b == 0 ? d(r, 0) - d(r, 2) : b == 1 ? d(r, 1) + d(r, 2) : b == 2 ? d(r, 2) - d(r, 1) : d(r, 1) - d(r, 3);
+  };
+  nhmc_v4f vt[2];                                        // one granule per tile: both are formed before the first is stored,
+  auto stage_cols = [&]() {                              // so the second is not written into registers a store still reads
 #pragma unroll
     for (int ty = 0; ty < 2; ++ty) {
       const int r0 = 2 * ty;
-      nhmc_v4f v;
-      v.x = e[r0] - e[r0 + 2]; v.y = e[r0 + 1] + e[r0 + 2]; v.z = e[r0 + 2] - e[r0 + 1]; v.w = e[r0 + 1] - e[r0 + 3];
-      *reinterpret_cast<nhmc_v4f*>(Vs + vw + ty * 32 * 16 + ((b ^ vswz) << 2)) = v;
+      vt[ty].x = e[r0] - e[r0 + 2]; vt[ty].y = e[r0 + 1] + e[r0 + 2]; vt[ty].z = e[r0 + 2] - e[r0 + 1]; vt[ty].w = e[r0 + 1] - e[r0 + 3];
     }
-#pragma unroll
-    for (int i = 2 * b; i < 2 * b + 2; ++i) *reinterpret_cast<nhmc_v4f*>(Us + uw + 1024 * i) = ur[i];
+  };
+  auto stage_v = [&](int st, int b, int ty) {
+    float* Vs = lds + st * 2 * WC_OPER + WC_OPER;
+    *reinterpret_cast<nhmc_v4f*>(Vs + vw + ty * 32 * 16 + ((b ^ vswz) << 2)) = vt[ty];
+  };
+  auto stage_u = [&](int st, int i) { *reinterpret_cast<nhmc_v4f*>(lds + st * 2 * WC_OPER + uw + 1024 * i) = ur[i]; };
+  auto stage_part = [&](int st, int b) {
+    stage_rows(b, 0, 6);
+    stage_cols();
+    stage_v(st, b, 0);
+    stage_v(st, b, 1);
+    stage_u(st, 2 * b);
+    stage_u(st, 2 * b + 1);
   };
 
   const int chunks = C / WC_CHUNK;
@@ -179,32 +234,26 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
     for (int r = 0; r < 16; ++r) acc[f][r] = 0.0f;
 
   // one chunk: 8 units of 8 MFMAs (k-step u / 2, frequencies 8 (u & 1) .. + 7 = granules 2 (u & 1), + 1 of the lane's A and B
-  // rows); the operands of unit u + 1 are read from LDS before the MFMAs of unit u issue.  The following chunk is staged
-  // behind units 3 .. 6; the workgroup meets between units 6 and 7, when unit 7's operands are in registers, so that the
+  // rows); the operands of unit u + 1 are read from LDS before the MFMAs of unit u issue (units 0 .. 2, 7) or behind its
+  // first two (units 3 .. 6).  The following chunk is staged between the MFMAs of units 3 .. 6; the workgroup meets between units 6 and 7, when unit 7's operands are in registers, so that the
   // first operands of the following chunk are read behind the MFMAs of unit 7 and no MFMA waits on the read before it
-  const int swz = (lr >> 2) & 3;
+  const int swz = wc_swz(lr);
   const int arow = (lh * 64 + kh * 32 + lr) * 16, brow = WC_OPER + (lh * 64 + th * 32 + lr) * 16;
   float av[2][8], bv[2][8];
-  auto fetch = [&](int st, int u, float (&fa)[8], float (&fb)[8]) {
+  auto fetch_half = [&](int st, int u, int g, float (&fa)[8], float (&fb)[8]) {       // MFMAs 4 g .. 4 g + 3 of unit u
     const float* S = lds + st * 2 * WC_OPER + (u >> 1) * 2 * 64 * 16;
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      const int go = ((2 * (u & 1) + g) ^ swz) << 2;
-      const nhmc_v4f va = *reinterpret_cast<const nhmc_v4f*>(S + arow + go);
-      const nhmc_v4f vb = *reinterpret_cast<const nhmc_v4f*>(S + brow + go);
-      fa[4 * g + 0] = va.x; fa[4 * g + 1] = va.y; fa[4 * g + 2] = va.z; fa[4 * g + 3] = va.w;
-      fb[4 * g + 0] = vb.x; fb[4 * g + 1] = vb.y; fb[4 * g + 2] = vb.z; fb[4 * g + 3] = vb.w;
-    }
+    const int go = ((2 * (u & 1) + g) ^ swz) << 2;
+    const nhmc_v4f va = *reinterpret_cast<const nhmc_v4f*>(S + arow + go);
+    const nhmc_v4f vb = *reinterpret_cast<const nhmc_v4f*>(S + brow + go);
+    fa[4 * g + 0] = va.x; fa[4 * g + 1] = va.y; fa[4 * g + 2] = va.z; fa[4 * g + 3] = va.w;
+    fb[4 * g + 0] = vb.x; fb[4 * g + 1] = vb.y; fb[4 * g + 2] = vb.z; fb[4 * g + 3] = vb.w;
   };
-  auto unit = [&](int u) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int f = 8 * (u & 1) + j;
-      if (!TAIL || !idle) acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u & 1][j], bv[u & 1][j], acc[f], 0, 0, 0);
-    }
+  auto fetch = [&](int st, int u, float (&fa)[8], float (&fb)[8]) {
+    fetch_half(st, u, 0, fa, fb);
+    fetch_half(st, u, 1, fa, fb);
   };
   // The loads of chunk `cl` are spread over the gaps between the MFMAs of the four units that follow the barrier, at most two
-  // per gap, instead of all 32 behind the barrier (where the four waves of the CU, released together, queued 128 of them on
+  // per gap, instead of all of them behind the barrier (where the four waves of the CU, released together, queued them on
   // the one address path and no MFMA issued until the last was accepted): unit 7 the patch's rows 0 - 2, unit 0 of the next
   // body its rows 3 - 5 and U pieces 0, 1, unit 1 pieces 2 - 5, unit 2 pieces 6, 7.  Every gap is fenced, so the placement
   // is the scheduler's too
@@ -213,22 +262,52 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
     for (int j = 0; j < 8; ++j) {
       const int f = 8 * (u & 1) + j;
       if (!TAIL || !idle) acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u & 1][j], bv[u & 1][j], acc[f], 0, 0, 0);
-      if (u == 7) issue_loads(cl, (3 * j) / 2, (3 * j + 3) / 2);                     // 1, 2, 1, 2, ... : 12 loads
-      if (u == 0 && j < 6) issue_loads(cl, 12 + 2 * j, 14 + 2 * j);
-      if (u == 0 && j >= 6) issue_loads(cl, 18 + j, 19 + j);                         // pieces 0, 1
-      if (u == 1 && (j & 1) == 0) issue_loads(cl, 26 + j / 2, 27 + j / 2);           // pieces 2 .. 5
-      if (u == 2 && (j == 0 || j == 2)) issue_loads(cl, 30 + j / 2, 31 + j / 2);     // pieces 6, 7
+      if (u == 7) issue_loads(cl, (NP / 2 * j) / 8, (NP / 2 * (j + 1)) / 8);         // rows 0 - 2: 6 or 3 loads over 8 gaps
+      if (u == 0 && j < 6) issue_loads(cl, NP / 2 + (NP / 2 * j) / 6, NP / 2 + (NP / 2 * (j + 1)) / 6);   // rows 3 - 5
+      if (u == 0 && j >= 6) issue_loads(cl, NP - 6 + j, NP - 5 + j);                 // pieces 0, 1
+      if (u == 1 && (j & 1) == 0) issue_loads(cl, NP + 2 + j / 2, NP + 3 + j / 2);   // pieces 2 .. 5
+      if (u == 2 && (j == 0 || j == 2)) issue_loads(cl, NP + 6 + j / 2, NP + 7 + j / 2);   // pieces 6, 7
       __builtin_amdgcn_sched_barrier(0);
     }
   };
 
-  issue_loads(0, 0, 32);
+  // Units 3 .. 6 stage column u - 3 of V and U pieces 2 (u - 3), + 1 of the following chunk into stage st ^ 1 and read the
+  // operands of unit u + 1, every gap fenced as above.  Left to the scheduler, the four stores, the four reads and the
+  // arithmetic all went into the unit's first four gaps, and the four waves, released by one barrier, met on the LDS
+  // store-data path (13 cycles per ds_write_b128, shared by two SIMDs).  Here a gap holds at most one store, with the
+  // arithmetic that feeds it in front, and the reads sit in the two gaps that hold none: gap 0 (behind the exchange of the
+  // patch, in unit 3) and gap 1, the row differences in gaps 1 and 2, the V stores in gaps 3 and 4, the U stores in 5 and 6
+  auto unit_staging = [&](int u, int st, int ch) {
+    const int b = u - 3;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int f = 8 * (u & 1) + j;
+      if (u == 4 && (j & 1)) WC_T32(13 + j / 2);
+      if (!TAIL || !idle) acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u & 1][j], bv[u & 1][j], acc[f], 0, 0, 0);
+      if (j == 0 && u == 3) {
+        WC_T32(7);
+        pin_patch();
+        exchange_patch();
+        WC_T32(8);
+      }
+      if (j < 2) fetch_half(st, u + 1, j, av[(u + 1) & 1], bv[(u + 1) & 1]);
+      if (j == 1) stage_rows(b, 0, 3);
+      if (j == 2) stage_rows(b, 3, 6);
+      if (j == 3) stage_cols();
+      if (j == 3 || j == 4) stage_v(st ^ 1, b, j - 3);
+      if (j == 5 || j == 6) stage_u(st ^ 1, 2 * b + j - 5);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  issue_loads(0, 0, NP + 8);
+  exchange_patch();
 #pragma unroll
   for (int b = 0; b < 4; ++b) stage_part(0, b);
   __syncthreads();
   WC_T64(1);
   int cl = 1 < chunks ? 1 : 0;                      // the chunk being loaded
-  issue_loads(cl, 0, 12);
+  issue_loads(cl, 0, NP / 2);
   fetch(0, 0, av[0], bv[0]);
   // ONE instance of the chunk body (a second one behind the loop made the register allocator shuffle the 256 accumulators
   // through scratch): the last chunk stages itself once more into the idle buffer and reads unit 0 of it, which nobody
@@ -240,16 +319,13 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
 #pragma unroll
     for (int u = 0; u < 7; ++u) {
       WC_T32(u);
-      fetch(st, u + 1, av[(u + 1) & 1], bv[(u + 1) & 1]);
-      __builtin_amdgcn_sched_barrier(0);
-      if (u < 3) unit_loading(u, cl);
-      else unit(u);
-      if (u == 3) {
-        WC_T32(7);
-        pin_patch();
-        WC_T32(8);
+      if (u < 3) {
+        fetch(st, u + 1, av[(u + 1) & 1], bv[(u + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+        unit_loading(u, cl);
+      } else {
+        unit_staging(u, st, ch);
       }
-      if (u >= 3) stage_part(st ^ 1, u - 3);
     }
     WC_T32(9);
     __syncthreads();                                // stage st ^ 1 is complete, and every wave is done reading stage st
@@ -325,7 +401,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
 #pragma unroll
     for (int i = 0; i < 7; ++i) out[i] = t64[i];
 #pragma unroll
-    for (int i = 0; i < 13; ++i) out[7 + i] = t32[i];
+    for (int i = 0; i < 17; ++i) out[7 + i] = t32[i];
   }
 #endif
 }
@@ -420,33 +496,33 @@ extern "C" int nhmc_conv3x3_wino_narrow_covers(int n, int c, int k, int h, int w
 // F.conv2d's time at 64 chains on MI355X in the same process (the figure behind each row is the larger of the median and
 // the best-of-rounds ratio): a tie is never routed.  Other batch sizes follow the same rows; only n = 64 was measured.
 // The first table holds the 3x3 convolutions of unet.FFHQ_CONFIG (unet.conv3x3_shapes()) with widths that are multiples of
-// 64, all measured in one run: profiles/r09_wino_conv_routing.txt.  The second holds shapes that FFHQ_CONFIG never runs;
+// 64, all measured in one run: profiles/r10_wino_conv_routing.txt.  The second holds shapes that FFHQ_CONFIG never runs;
 // they are kept because they are real measurements (profiles/r05_wino_conv_roofline.txt) and serve other channel multipliers.
 extern "C" int nhmc_conv3x3_wino_prefers(int backward, int n, int c, int k, int h, int w) {
   if (!wc_covers(n, c, k, h, w) || h != w) return 0;
   static const WcRow network[] = {
-      {0, 128, 128, 256},   // 128->128 forward: 0.577
-      {1, 128, 128, 256},   // 128->128 backward-data: 0.556
-      {0, 256, 128, 256},   // 256->128 forward: 0.566
-      {1, 128, 256, 256},   // 256->128 backward-data: 0.562
-      {0, 128, 128, 128},   // 128->128 forward: 0.579
-      {1, 128, 128, 128},   // 128->128 backward-data: 0.576
-      {0, 256, 128, 128},   // 256->128 forward: 0.575
-      {1, 128, 256, 128},   // 256->128 backward-data: 0.564
-      {0, 256, 256, 128},   // 256->256 forward: 0.590
-      {1, 256, 256, 128},   // 256->256 backward-data: 0.578
-      {0, 384, 128, 128},   // 384->128 forward: 0.569
-      {1, 128, 384, 128},   // 384->128 backward-data: 0.560
-      {0, 128, 128, 64},   // 128->128 forward: 0.596
-      {1, 128, 128, 64},   // 128->128 backward-data: 0.575
-      {0, 128, 256, 64},   // 128->256 forward: 0.597
-      {1, 256, 128, 64},   // 128->256 backward-data: 0.575
-      {0, 256, 256, 64},   // 256->256 forward: 0.604
-      {1, 256, 256, 64},   // 256->256 backward-data: 0.568
-      {0, 384, 256, 64},   // 384->256 forward: 0.596
-      {1, 256, 384, 64},   // 384->256 backward-data: 0.593
-      {0, 512, 256, 64},   // 512->256 forward: 0.598
-      {1, 256, 512, 64},   // 512->256 backward-data: 0.601
+      {0, 128, 128, 256},   // 128->128 forward: 0.513
+      {1, 128, 128, 256},   // 128->128 backward-data: 0.499
+      {0, 256, 128, 256},   // 256->128 forward: 0.503
+      {1, 128, 256, 256},   // 256->128 backward-data: 0.500
+      {0, 128, 128, 128},   // 128->128 forward: 0.524
+      {1, 128, 128, 128},   // 128->128 backward-data: 0.517
+      {0, 256, 128, 128},   // 256->128 forward: 0.512
+      {1, 128, 256, 128},   // 256->128 backward-data: 0.504
+      {0, 256, 256, 128},   // 256->256 forward: 0.527
+      {1, 256, 256, 128},   // 256->256 backward-data: 0.516
+      {0, 384, 128, 128},   // 384->128 forward: 0.506
+      {1, 128, 384, 128},   // 384->128 backward-data: 0.504
+      {0, 128, 128, 64},   // 128->128 forward: 0.535
+      {1, 128, 128, 64},   // 128->128 backward-data: 0.509
+      {0, 128, 256, 64},   // 128->256 forward: 0.526
+      {1, 256, 128, 64},   // 128->256 backward-data: 0.507
+      {0, 256, 256, 64},   // 256->256 forward: 0.533
+      {1, 256, 256, 64},   // 256->256 backward-data: 0.519
+      {0, 384, 256, 64},   // 384->256 forward: 0.533
+      {1, 256, 384, 64},   // 384->256 backward-data: 0.527
+      {0, 512, 256, 64},   // 512->256 forward: 0.532
+      {1, 256, 512, 64},   // 512->256 backward-data: 0.533
   };
   static const WcRow elsewhere[] = {           // not in FFHQ_CONFIG
       {0, 384, 128, 256},   // 384->128 forward: 0.696
@@ -466,14 +542,14 @@ extern "C" int nhmc_conv3x3_wino_prefers(int backward, int n, int c, int k, int 
       {0, 1024, 512, 64},   // 1024->512 forward: 0.734
       {1, 512, 1024, 64},   // 1024->512 backward-data: 0.742
   };
-  // latent networks, measured at 16 chains (tools/conv_bench.py --latent, profiles/r09_wino_conv_latent.txt): the shapes of
+  // latent networks, measured at 16 chains (tools/conv_bench.py --latent, profiles/r10_wino_conv_latent.txt): the shapes of
   // ldm.conv3x3_shapes with K % 64 == 0 that no row above holds.  The score network runs without gradient: forward only
   static const WcRow latent[] = {
-      {0, 448, 448, 64},    // U-Net 448->448 forward: 0.565
-      {0, 256, 256, 256},   // decoder 256->256 forward: 0.588
-      {1, 256, 256, 256},   // decoder 256->256 backward-data: 0.576
-      {0, 512, 512, 128},   // decoder 512->512 forward: 0.610
-      {1, 512, 512, 128},   // decoder 512->512 backward-data: 0.603
+      {0, 448, 448, 64},    // U-Net 448->448 forward: 0.505
+      {0, 256, 256, 256},   // decoder 256->256 forward: 0.526
+      {1, 256, 256, 256},   // decoder 256->256 backward-data: 0.512
+      {0, 512, 512, 128},   // decoder 512->512 forward: 0.544
+      {1, 512, 512, 128},   // decoder 512->512 backward-data: 0.537
   };
   return wc_listed(network, backward, c, k, h) || wc_listed(elsewhere, backward, c, k, h) || wc_listed(latent, backward, c, k, h);
 }
@@ -482,54 +558,54 @@ extern "C" int nhmc_conv3x3_wino_prefers(int backward, int n, int c, int k, int 
 extern "C" int nhmc_conv3x3_wino_narrow_prefers(int backward, int n, int c, int k, int h, int w) {
   if (!wc_narrow_covers(n, c, k, h, w) || h != w) return 0;
   static const WcRow network[] = {
-      {0, 256, 256, 32},   // 256->256 forward: 0.578
-      {1, 256, 256, 32},   // 256->256 backward-data: 0.574
-      {0, 512, 256, 32},   // 512->256 forward: 0.580
-      {1, 256, 512, 32},   // 512->256 backward-data: 0.576
-      {0, 512, 512, 32},   // 512->512 forward: 0.615
-      {1, 512, 512, 32},   // 512->512 backward-data: 0.613
-      {0, 768, 256, 32},   // 768->256 forward: 0.579
-      {1, 256, 768, 32},   // 768->256 backward-data: 0.600
-      {0, 256, 256, 16},   // 256->256 forward: 0.610
-      {1, 256, 256, 16},   // 256->256 backward-data: 0.565
-      {0, 256, 512, 16},   // 256->512 forward: 0.597
-      {1, 512, 256, 16},   // 256->512 backward-data: 0.599
-      {0, 512, 512, 16},   // 512->512 forward: 0.606
-      {1, 512, 512, 16},   // 512->512 backward-data: 0.586
-      {0, 768, 512, 16},   // 768->512 forward: 0.595
-      {1, 512, 768, 16},   // 768->512 backward-data: 0.604
-      {0, 1024, 512, 16},   // 1024->512 forward: 0.603
-      {1, 512, 1024, 16},   // 1024->512 backward-data: 0.597
+      {0, 256, 256, 32},   // 256->256 forward: 0.491
+      {1, 256, 256, 32},   // 256->256 backward-data: 0.490
+      {0, 512, 256, 32},   // 512->256 forward: 0.488
+      {1, 256, 512, 32},   // 512->256 backward-data: 0.485
+      {0, 512, 512, 32},   // 512->512 forward: 0.527
+      {1, 512, 512, 32},   // 512->512 backward-data: 0.515
+      {0, 768, 256, 32},   // 768->256 forward: 0.487
+      {1, 256, 768, 32},   // 768->256 backward-data: 0.510
+      {0, 256, 256, 16},   // 256->256 forward: 0.484
+      {1, 256, 256, 16},   // 256->256 backward-data: 0.463
+      {0, 256, 512, 16},   // 256->512 forward: 0.488
+      {1, 512, 256, 16},   // 256->512 backward-data: 0.470
+      {0, 512, 512, 16},   // 512->512 forward: 0.484
+      {1, 512, 512, 16},   // 512->512 backward-data: 0.475
+      {0, 768, 512, 16},   // 768->512 forward: 0.484
+      {1, 512, 768, 16},   // 768->512 backward-data: 0.506
+      {0, 1024, 512, 16},   // 1024->512 forward: 0.482
+      {1, 512, 1024, 16},   // 1024->512 backward-data: 0.518
   };
-  // latent networks, measured at 16 chains (profiles/r09_wino_conv_latent.txt): the LDM U-Net's K = 448 / 896 layers, forward
+  // latent networks, measured at 16 chains (profiles/r10_wino_conv_latent.txt): the LDM U-Net's K = 448 / 896 layers, forward
   static const WcRow latent[] = {
-      {0, 224, 448, 32},    // 224->448 forward: 0.655
-      {0, 448, 448, 32},    // 448->448 forward: 0.642
-      {0, 672, 448, 32},    // 672->448 forward: 0.645
-      {0, 896, 448, 32},    // 896->448 forward: 0.640
-      {0, 1120, 448, 32},   // 1120->448 forward: 0.638
-      {0, 896, 896, 16},    // 896->896 forward: 0.570
+      {0, 224, 448, 32},    // 224->448 forward: 0.561
+      {0, 448, 448, 32},    // 448->448 forward: 0.544
+      {0, 672, 448, 32},    // 672->448 forward: 0.544
+      {0, 896, 448, 32},    // 896->448 forward: 0.544
+      {0, 1120, 448, 32},   // 1120->448 forward: 0.550
+      {0, 896, 896, 16},    // 896->896 forward: 0.470
   };
   return wc_listed(network, backward, c, k, h) || wc_listed(latent, backward, c, k, h);
 }
 
 // K % 64 == 32 only; same rule, measured at 16 chains (the latent sampler's chain count) by tools/conv_bench.py --latent:
-// profiles/r09_wino_conv_latent.txt.  The rows are the LDM U-Net's K = 224 / 672 layers, forward only (it runs without
+// profiles/r10_wino_conv_latent.txt.  The rows are the LDM U-Net's K = 224 / 672 layers, forward only (it runs without
 // gradient).  At 16 x 16 a tail launch has 16 x 11 = 176 workgroups on 256 CUs, one in eleven of them half empty.
 extern "C" int nhmc_conv3x3_wino_k32_covers(int n, int c, int k, int h, int w) { return wc_k32_covers(n, c, k, h, w); }
 
 extern "C" int nhmc_conv3x3_wino_k32_prefers(int backward, int n, int c, int k, int h, int w) {
   if (!wc_k32_covers(n, c, k, h, w) || h != w || k % WC_KBLK == 0) return 0;
   static const WcRow latent[] = {
-      {0, 224, 224, 64},    // 224->224 forward: 0.710
-      {0, 448, 224, 64},    // 448->224 forward: 0.699
-      {0, 672, 224, 64},    // 672->224 forward: 0.691
-      {0, 672, 672, 32},    // 672->672 forward: 0.662
-      {0, 448, 672, 16},    // 448->672 forward: 0.810
-      {0, 672, 672, 16},    // 672->672 forward: 0.808
-      {0, 1120, 672, 16},   // 1120->672 forward: 0.799
-      {0, 1344, 672, 16},   // 1344->672 forward: 0.798
-      {0, 1568, 672, 16},   // 1568->672 forward: 0.795
+      {0, 224, 224, 64},    // 224->224 forward: 0.669
+      {0, 448, 224, 64},    // 448->224 forward: 0.671
+      {0, 672, 224, 64},    // 672->224 forward: 0.669
+      {0, 672, 672, 32},    // 672->672 forward: 0.609
+      {0, 448, 672, 16},    // 448->672 forward: 0.724
+      {0, 672, 672, 16},    // 672->672 forward: 0.728
+      {0, 1120, 672, 16},   // 1120->672 forward: 0.718
+      {0, 1344, 672, 16},   // 1344->672 forward: 0.722
+      {0, 1568, 672, 16},   // 1568->672 forward: 0.727
   };
   return wc_listed(latent, backward, c, k, h);
 }

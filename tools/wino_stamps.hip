@@ -5,7 +5,8 @@
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off tools/wino_stamps.hip -o tools/wino_stamps
 //   tools/wino_stamps [n c k h w]        (default: 64 128 128 256 256, then 64 512 256 64 64)
 // Random data; >= 2 s of back-to-back unstamped launches first; then one stamped launch each for the first, the middle and
-// the last chunk of every workgroup.  Prints the median over all waves, in shader cycles, per phase.
+// the last chunk of every workgroup.  Prints the median over all waves, in shader cycles, per phase, and unit 4, one of the
+// four units that stage the following chunk, split at its MFMAs 1, 3, 5 and 7 (reads, arithmetic, V stores, U stores).
 #define NHMC_WINO_STAMPS 1
 #include "../noise-space-hmc_amd/csrc/wino_conv.hip"
 
@@ -92,6 +93,9 @@ static int run_shape(int n, int c, int k, int h, int w) {
     for (int u = 0; u < 6; ++u) std::printf(" %.0f", d32(u, u + 1));
     std::printf(" %.0f (to the barrier) | of unit 3, patch wait %.0f | barrier %.0f | behind it, to unit 7 %.0f | unit 7 %.0f | chunk %.0f\n",
                 d32(6, 9), d32(7, 8), d32(9, 10), d32(10, 11), d32(11, 12), d32(0, 12));
+    // a staging unit by its gaps (two MFMAs = 128 cycles each): head of unit 4 -> its MFMA 1 (64) -> 3 -> 5 -> 7
+    std::printf("          unit 4 (staging): to MFMA 1, the operand reads %.0f | to MFMA 3, the row differences %.0f | to MFMA 5, the V stores "
+                "%.0f | to MFMA 7, the U stores and their waits %.0f\n", d32(4, 13), d32(13, 14), d32(14, 15), d32(15, 16));
   }
   CK(hipFree(X)); CK(hipFree(Y)); CK(hipFree(Wt)); CK(hipFree(U)); CK(hipFree(ST));
   return 0;
