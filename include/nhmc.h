@@ -686,6 +686,41 @@ int nhmc_chain_diag(const float* samples, float* rhat, float* ess, double* summa
                     int n_replicas, int n_samples, int64_t n_elem, double rhat_threshold, nhmc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Calibration of the posterior samples against the original image, on the device.
+ *
+ *   samples : fp32 [n_groups * n_replicas][n_samples][n_elem], the block the sampler returns; chain g * n_replicas + r is
+ *             replica r of image (group) g.  x_orig : fp32 [n_groups][n_elem].  Raw values in [-1, 1], finite.
+ *   z       : fp32 [n_groups][n_elem];  counts : int32 [n_groups][n_elem] = below + 65536 * equal.
+ *   hist    : int64 [n_groups][n + 1], zeroed by the entry on the stream;  summary : fp64 [n_groups][8].
+ *   ws      : double, nhmc_calibration_ws_bytes(n_groups, n_elem) bytes: 8 partials for each of the
+ *             nhmc_calibration_tiles(n_elem) tiles (256 elements each) of every group.
+ *   Validation, before any launch: null pointer / non-positive size -> ARG; samples, x_orig, z or counts not 16-byte
+ *   aligned or n_elem % 4 != 0 -> ALIGN; n < 2, n > 1024 or n_groups > 65535 -> SHAPE, with n = n_replicas * n_samples.
+ *
+ * Definition, per element of group g.  The n = n_replicas * n_samples draws of the element are pooled: d_1 ... d_n, d_1
+ * being the first sample of replica 0 (draw i is row g * n + i - 1 of the block); t is the original's value.
+ *   below = #{i : d_i < t},  equal = #{i : d_i == t}            fp32 comparisons, hence exact
+ *   mu = d_1 + sum(d_i - d_1) / n                                fp64; the shift by a draw keeps the one-pass form benign
+ *   v  = max(0, (sum (d_i - d_1)^2 - (sum(d_i - d_1))^2 / n) / (n - 1)),  s = sqrt(v)
+ *        All draws equal gives s = 0 exactly: the element is *flat*.
+ *   z  = (t - mu) / s  in fp64, rounded once to fp32; for s = 0 it is +-inf when t != mu and NaN when t == mu.
+ * Summary per group, fp64 sums over its n_elem elements:
+ *     [0] sum_err2 = sum (t - mu)^2      [1] sum_var = sum v             [2] sum_abs_err = sum |t - mu|
+ *     [3] sum_std  = sum s               [4] sum_abs_err_std = sum |t - mu| s
+ *     [5] sum_z2   = sum over s > 0 of z^2 (z before rounding)
+ *     [6] n_tied   = #{equal > 0}        [7] n_flat = #{s == 0}
+ * Rank histogram: hist[b], b = 0 ... n, counts the elements with equal == 0 and below == b.  A tied element (a clipped
+ *   pixel, say) has no rank: it is left out of the histogram and counted in n_tied.
+ * Reductions: the sums go through per-tile fp64 partials in ws and a fixed-order second pass; the histogram is summed per
+ *   block in LDS and added to hist with integer atomics, which no order of arrival changes.  Equal inputs give equal bits.
+ * Every sample value is read once, and t once: n * 4 + 4 bytes per element read, 8 written.
+ * ---------------------------------------------------------------------------------- */
+int nhmc_calibration_tiles(int64_t n_elem);
+size_t nhmc_calibration_ws_bytes(int n_groups, int64_t n_elem);
+int nhmc_calibration(const float* samples, const float* x_orig, float* z, int32_t* counts, int64_t* hist, double* summary,
+                     double* ws, int n_groups, int n_replicas, int n_samples, int64_t n_elem, nhmc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * a1  Momentum / accept noise: Philox4x32-10 keyed by seed, counted by
  *     (element quad, chain_id0 + chain, draw, tag) -- independent of how chains are sharded.
  *     Replaces torch.randn_like (main_sampling.py:692) and torch.rand(1) (:720).

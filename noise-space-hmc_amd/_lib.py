@@ -117,6 +117,9 @@ SIGNATURES = {
     'nhmc_chain_diag_tiles': (I, [I64]),
     'nhmc_chain_diag_ws_bytes': (SZ, [I, I64]),
     'nhmc_chain_diag': (I, [P, P, P, P, P, I, I, I, I64, D, P]),
+    'nhmc_calibration_tiles': (I, [I64]),
+    'nhmc_calibration_ws_bytes': (SZ, [I, I64]),
+    'nhmc_calibration': (I, [P, P, P, P, P, P, P, I, I, I, I64, P]),
     'nhmc_randn_philox': (I, [P, U64, U32, U32, F, I, I64, P]),
     'nhmc_copy_probe': (I, [P, P, I64, P]),
     'nhmc_uniform_philox': (I, [P, U64, U32, U32, I, P]),

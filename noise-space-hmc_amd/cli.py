@@ -23,6 +23,11 @@ i * K + r being replica r of the batch's image i): all replicas see the same mea
 single chain starts, replicas r >= 1 start from their own N(0,1) draw keyed by (seed, s, r), and the Philox stream of
 replica r of image s is s * K + r.  The report pools an image's K * S samples and adds the split R-hat / ESS line
 (nhmc.metrics.convergence).  With K = 1, the default, nothing changes.
+
+`--calibration [LEVEL]` (LEVEL = 0.9 when bare) adds, per image, where the original lies in the cloud of its pooled samples
+(nhmc.metrics.calibration): the coverage of the central interval nearest to LEVEL against its nominal value, spread / skill,
+the RMS z-score, the correlation of |error| with the sample std and the PSNR of the posterior mean -- CALIBRATION_COLUMNS
+in the JSON rows and, with `--save_images`, `calibration_map_{s}.png`.  Without the flag nothing changes.
 """
 import argparse
 import glob
@@ -82,6 +87,9 @@ def get_parser(latent=False):
     p.add_argument('--rhat_threshold', type=float, default=1.1,
                    help="R-hat above which a pixel counts as not converged (Gelman's classic 1.1; with the 10 draws per "
                         'split chain of a 20-sample run the stricter 1.01 flags sampling noise)')
+    p.add_argument('--calibration', type=float, nargs='?', const=0.9, default=None, metavar='LEVEL',
+                   help='report the calibration of the samples against the original: coverage of the central interval '
+                        'nearest to LEVEL (0.9 when the flag is bare), spread/skill, z-score RMS, |error|~std correlation')
     return p
 
 
@@ -250,13 +258,15 @@ def _setup(opt, latent):
 
 COLUMNS = ('image', 'psnr_mean', 'psnr_std', 'ssim_mean', 'ssim_std', 'std_map_min', 'std_map_max', 'n_samples')
 REPLICA_COLUMNS = ('replicas',) + metrics.CONVERGENCE_KEYS          # appended to COLUMNS with --replicas K > 1
-INT_COLUMNS = ('image', 'n_samples', 'replicas', 'n_constant')
+CALIBRATION_COLUMNS = metrics.CALIBRATION_KEYS                      # appended last with --calibration
+INT_COLUMNS = ('image', 'n_samples', 'replicas', 'n_constant', 'n_tied', 'n_flat')
 
 
-def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, rhat_threshold=1.1):
-    """Gathers the per-image rows (COLUMNS, with K > 1 replicas + REPLICA_COLUMNS) over the ranks in global image order,
-    prints the report on rank 0 and returns the [n, 3] table (image, PSNR mean, PSNR std over its samples)."""
-    columns = COLUMNS + (REPLICA_COLUMNS if replicas > 1 else ())
+def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, rhat_threshold=1.1, calibration=None):
+    """Gathers the per-image rows (COLUMNS, with K > 1 replicas + REPLICA_COLUMNS, with --calibration + CALIBRATION_COLUMNS)
+    over the ranks in global image order, prints the report on rank 0 and returns the [n, 3] table (image, PSNR mean, PSNR
+    std over its samples)."""
+    columns = COLUMNS + (REPLICA_COLUMNS if replicas > 1 else ()) + (CALIBRATION_COLUMNS if calibration is not None else ())
     local = torch.tensor(rows, dtype=torch.float64, device=device).reshape(-1, len(columns))
     full = sharding.gather_chains(local, n_images, rank, world).cpu()
     table = full[:, :3].float()
@@ -274,10 +284,19 @@ def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, r
                 print(f'image {int(idx)}: R-hat max {c["rhat_max"]:.3f} mean {c["rhat_mean"]:.4f} '
                       f'(> {rhat_threshold:g}: {100.0 * c["rhat_frac_above"]:.2f}%)  ESS min {c["ess_min"]:.1f} '
                       f'mean {c["ess_mean"]:.1f} of {int(c["n_samples"])} draws, constant elements {int(c["n_constant"])}')
+            if calibration is not None and c['n_flat'] == c['n_flat']:      # NaN: fewer than two pooled samples
+                print(f'image {int(idx)}: calibration: coverage {c["coverage"]:.4f} at nominal {c["coverage_nominal"]:.4f}, '
+                      f'spread/skill {c["spread_skill"]:.3f}, z rms {c["z_rms"]:.3f}, |err|~std r {c["err_std_corr"]:.3f}, '
+                      f'PSNR of the posterior mean {c["psnr_of_mean"]:.3f}, tied {int(c["n_tied"])} flat {int(c["n_flat"])}')
         print(f'Total Average PSNR: {float(table[:, 1].nanmean()):.3f}  images: {table.shape[0]}')
         # main_sampling.py:560: the average over the images, and in parentheses the mean over the images of each
         # image's std over its samples
         print('Total Average SSIM: {:.5f} ({:.5f})'.format(float(full[:, 3].nanmean()), float(full[:, 4].nanmean())))
+        if calibration is not None:
+            avg = {k: float(full[:, columns.index(k)].nanmean()) for k in CALIBRATION_COLUMNS}
+            print(f'Total Average calibration: coverage {avg["coverage"]:.4f} at nominal {avg["coverage_nominal"]:.4f}, '
+                  f'spread/skill {avg["spread_skill"]:.3f}, z rms {avg["z_rms"]:.3f}, |err|~std r {avg["err_std_corr"]:.3f}, '
+                  f'PSNR of the posterior mean {avg["psnr_of_mean"]:.3f}')
         if metrics_out:
             import json
             as_json = lambda k, v: (int(v) if k in INT_COLUMNS and v == v else (v if v == v else None))
@@ -290,15 +309,19 @@ def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, r
 
 def _metric_rows(batch, summary):
     """One COLUMNS row per image of `batch` from a `metrics.summarize` result (entry i of it for image i); a pooled
-    summary (replicas > 1) appends REPLICA_COLUMNS."""
+    summary (replicas > 1) appends REPLICA_COLUMNS, one with the calibration figures CALIBRATION_COLUMNS."""
     pooled = summary.get('replicas', 1) > 1
     return [[float(s)] + [float(summary[c][i]) for c in COLUMNS[1:-1]] + [float(summary['n_samples'])] +
-            ([float(summary['replicas'])] + [float(summary[c][i]) for c in metrics.CONVERGENCE_KEYS] if pooled else [])
+            ([float(summary['replicas'])] + [float(summary[c][i]) for c in metrics.CONVERGENCE_KEYS] if pooled else []) +
+            ([float(summary[c][i]) for c in CALIBRATION_COLUMNS] if 'coverage' in summary else [])
             for i, s in enumerate(batch)]
 
 
 def _save_report_images(summary, k, s, one_sample, folder):
-    """`{s}_mean.png` and, with two samples or more, `std_dev_map_{s}.png` (main_sampling.py:494-507)."""
+    """`{s}_mean.png` and, with two samples or more, `std_dev_map_{s}.png` (main_sampling.py:494-507); `rhat_map_{s}.png`
+    and `calibration_map_{s}.png` where the summary holds those maps."""
+    if summary.get('z') is not None:
+        metrics.save_calibration_map(summary['z'][k], os.path.join(folder, f'calibration_map_{s}.png'))
     if summary['mean'] is None:
         sampler._save_png(one_sample, os.path.join(folder, f'{s}_mean.png'))
         return
@@ -355,12 +378,13 @@ def main(argv=None):
         opt.chain_id0 = chain_id_base(batch, K)
         out = run_with_oom_backoff(opt, lambda: sampler.hmc(x, n, b, seq, seq_next, algo, opt, y_0, op, x_chain))
         samples = out[None] if n == 1 else out                              # [n, 20, C, H, W]
-        summary = metrics.summarize(samples.contiguous(), x_orig, replicas=K, rhat_threshold=opt.rhat_threshold)
+        summary = metrics.summarize(samples.contiguous(), x_orig, replicas=K, rhat_threshold=opt.rhat_threshold,
+                                    calibration=opt.calibration)
         rows += _metric_rows(batch, summary)
         if opt.save_images and samples.shape[1]:
             for k, s in enumerate(batch):
                 _save_report_images(summary, k, s, samples[k * K, 0], opt.image_folder)
-    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out, K, opt.rhat_threshold)
+    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out, K, opt.rhat_threshold, opt.calibration)
 
 
 def main_latent(argv=None):
@@ -400,11 +424,11 @@ def main_latent(argv=None):
             imgs = model.decode_first_stage(lat) if s_c else x_orig.new_empty((0,) + tuple(x_orig.shape[1:]))
             imgs = imgs.reshape((K, s_c) + tuple(imgs.shape[1:])).contiguous()
             summary = metrics.summarize(imgs if K > 1 else imgs[0], x_orig[k:k + 1], replicas=K,
-                                        rhat_threshold=opt.rhat_threshold)
+                                        rhat_threshold=opt.rhat_threshold, calibration=opt.calibration)
             rows += _metric_rows([s], summary)
             if opt.save_images and s_c:
                 _save_report_images(summary, 0, s, imgs[0, 0], opt.image_folder)
-    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out, K, opt.rhat_threshold)
+    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out, K, opt.rhat_threshold, opt.calibration)
 
 
 if __name__ == '__main__':

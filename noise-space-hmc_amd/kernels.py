@@ -1207,6 +1207,29 @@ def chain_diag(samples, n_replicas, rhat_threshold=1.1):
     return rhat, ess, summary
 
 
+def calibration(samples, x_orig, n_replicas=1):
+    """Rank and z-score of the original among an image's pooled draws (nhmc.h "Calibration of the posterior samples").
+    samples [G * n_replicas, S, C, H, W], chain g * n_replicas + r being replica r of image g, and x_orig [G, C, H, W]
+    -> (z [G, C, H, W] float32, counts [G, C, H, W] int32 = below + 65536 * equal, hist [G, n + 1] int64 with
+    n = n_replicas * S, summary [G, 8] float64)."""
+    lib = _lib.load()
+    B, S, Cc, H, W = _sample_block(samples)
+    K = int(n_replicas)
+    if K < 1 or B % K:
+        raise _lib.NhmcError(f'calibration: {B} chains are not a multiple of {n_replicas} replicas')
+    G, N, dev = B // K, Cc * H * W, samples.device
+    if x_orig.dim() != 4 or x_orig.shape[0] != G or x_orig.shape[1:] != samples.shape[2:]:
+        raise _lib.NhmcError(f'x_orig {tuple(x_orig.shape)} does not match {G} images of samples {tuple(samples.shape)}')
+    z = torch.empty((G, Cc, H, W), dtype=torch.float32, device=dev)
+    counts = torch.empty((G, Cc, H, W), dtype=torch.int32, device=dev)
+    hist = torch.empty((G, K * S + 1), dtype=torch.int64, device=dev)
+    summary = torch.empty((G, 8), dtype=torch.float64, device=dev)
+    ws = torch.empty(lib.nhmc_calibration_ws_bytes(G, N) // 8, dtype=torch.float64, device=dev)
+    _lib.check(lib.nhmc_calibration(_p(samples, torch.float32, 'samples'), _p(x_orig, torch.float32, 'x_orig'), _p(z),
+                                    _p(counts), _p(hist), _p(summary), _p(ws), G, K, S, N, _stream()), 'nhmc_calibration')
+    return z, counts, hist, summary
+
+
 # ---- a1 -------------------------------------------------------------------------------------
 def randn_philox(shape, seed, chain_id0, draw, scale=1.0, device='cuda', out=None):
     lib = _lib.load()

@@ -8,6 +8,9 @@ on the device.
     save_std_map(map01, path)        the `std_dev_map_{idx}.png` picture (:499-507)
     convergence(samples, replicas)   split R-hat and ESS per element over an image's replica chains, with summaries
     save_rhat_map(rhat, path)        the `rhat_map_{idx}.png` picture
+    calibration(samples, x_orig)     rank and z-score of the original among an image's pooled draws: coverage of the
+                                     central interval, spread / skill, |error| ~ std correlation, PSNR of the mean
+    save_calibration_map(z, path)    the `calibration_map_{idx}.png` picture
 
 With K replica chains per image (not in the reference, which runs one chain) the block is [G * K, S, C, H, W], chain
 g * K + r being replica r of image g, and `summarize(..., replicas=K)` pools an image's K * S samples.
@@ -84,7 +87,83 @@ def convergence(samples, replicas, rhat_threshold=1.1):
     return dict(rhat=rhat, ess=ess, **{k: host[:, i].copy() for i, k in enumerate(CONVERGENCE_KEYS)})
 
 
-def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1):
+CALIBRATION_KEYS = ('psnr_of_mean', 'spread_skill', 'z_rms', 'err_std_corr', 'coverage', 'coverage_nominal', 'n_tied',
+                    'n_flat')
+CALIBRATION_SUMS = ('sum_err2', 'sum_var', 'sum_abs_err', 'sum_std', 'sum_abs_err_std', 'sum_z2', 'n_tied', 'n_flat')
+
+
+def coverage_rank(n, level):
+    """k of the central interval [d_(k), d_(n+1-k)] between order statistics of n draws that comes nearest to `level`:
+    min(n // 2, max(1, floor((1 - level) / 2 * (n + 1) + 0.5)))."""
+    return min(n // 2, max(1, int(np.floor((1.0 - level) / 2.0 * (n + 1) + 0.5))))
+
+
+def coverage_from_hist(hist, level=0.9):
+    """hist [..., n + 1], the rank histogram of the untied elements -> (coverage, coverage_nominal): the share of them
+    whose original lies in [d_(k), d_(n+1-k)], i.e. has k <= below <= n - k, and the level (n + 1 - 2k) / (n + 1) such an
+    interval has for an exchangeable ensemble.  No untied element: coverage NaN."""
+    hist = np.asarray(hist)
+    n = hist.shape[-1] - 1
+    k = coverage_rank(n, level)
+    total = hist.sum(axis=-1).astype(np.float64)
+    inside = hist[..., k:n - k + 1].sum(axis=-1).astype(np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        coverage = inside / total
+    return coverage, np.full(coverage.shape, (n + 1 - 2 * k) / (n + 1.0))
+
+
+def calibration_from_sums(sums, hist, n_elem, level=0.9):
+    """The reported figures from the kernel's sums, in float64 on the host.  sums [G, 8] in the order CALIBRATION_SUMS
+    (include/nhmc.h), hist [G, n + 1], n_elem = C * H * W -> dict of CALIBRATION_KEYS, float64 [G]:
+        psnr_of_mean      10 log10(4 E / sum_err2): the inverse data transform halves a difference
+        spread_skill      sqrt((n + 1) / n * sum_var / sum_err2): 1 for an exchangeable ensemble, below 1 when over-confident
+        z_rms             sqrt(sum_z2 / (E - n_flat))
+        err_std_corr      Pearson's r between |t - mu| and s over the E elements
+        coverage, coverage_nominal   `coverage_from_hist`
+        n_tied, n_flat    the two counts
+    A ratio over nothing is NaN (or inf), never an error."""
+    sums = np.asarray(sums, dtype=np.float64)
+    err2, var, aerr, std, aerr_std, z2, tied, flat = (sums[..., i] for i in range(8))
+    n = np.asarray(hist).shape[-1] - 1
+    E = float(n_elem)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        cov = aerr_std / E - (aerr / E) * (std / E)
+        var_a, var_s = err2 / E - (aerr / E) ** 2, var / E - (std / E) ** 2
+        coverage, nominal = coverage_from_hist(hist, level)
+        return dict(psnr_of_mean=10.0 * np.log10(4.0 * E / err2),
+                    spread_skill=np.sqrt((n + 1.0) / n * var / err2),
+                    z_rms=np.sqrt(z2 / (E - flat)),
+                    err_std_corr=cov / np.sqrt(var_a * var_s),
+                    coverage=coverage, coverage_nominal=nominal, n_tied=tied.copy(), n_flat=flat.copy())
+
+
+def _split_counts(counts):
+    return counts & 0xFFFF, counts >> 16                                     # below + 65536 * equal, both <= 1024
+
+
+def calibration(samples, x_orig, replicas=1, level=0.9):
+    """Where the original lies in the sample cloud (the definition is in include/nhmc.h).  samples [G * K, S, C, H, W] with
+    2 <= K * S <= 1024, x_orig [G, C, H, W] -> dict: the device maps `z` (float32 [G, C, H, W]: (original - mean) / std
+    of the image's K * S pooled draws; +-inf or NaN where they are all equal), `below`, `equal` (int32: draws below / equal
+    to the original), `hist` (numpy int64 [G, K * S + 1], the rank histogram of the untied elements) and CALIBRATION_KEYS
+    as float64 numpy [G] at the central interval nearest to `level`, with one device->host read."""
+    samples, x_orig, _ = _block(samples, x_orig)
+    z, counts, hist, sums = K.calibration(samples, x_orig, replicas)
+    host = torch.cat([sums, hist.double()], dim=1).cpu().numpy()             # the one read; counts <= E are exact in fp64
+    return _calibration_result(z, counts, host, z[0].numel(), level)
+
+
+def _calibration_result(z, counts, host, n_elem, level):
+    hist = np.rint(host[:, 8:]).astype(np.int64)
+    below, equal = _split_counts(counts)
+    return dict(z=z, below=below, equal=equal, hist=hist, **calibration_from_sums(host[:, :8], hist, n_elem, level))
+
+
+def _no_calibration(G):
+    return dict(z=None, below=None, equal=None, hist=None, **{k: np.full(G, np.nan) for k in CALIBRATION_KEYS})
+
+
+def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1, calibration=None):
     """Everything the report prints or saves for B chains with S samples each, with one device->host read.
 
     -> dict of float64 numpy arrays [B]: psnr_mean, psnr_std, ssim_mean, ssim_std (np.mean / np.std(ddof=1) over the
@@ -96,23 +175,33 @@ def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1):
     replicas = K > 1: samples is [G * K, S, C, H, W] (chain g * K + r is replica r of image g) and x_orig [G, C, H, W].
     Everything above is then per image over its K * S pooled samples (`n_samples` = K * S; the block is contiguous, so
     pooling is a view), and the dict gains `replicas`, CONVERGENCE_KEYS as float64 numpy [G] and the device maps `rhat`,
-    `ess` [G, C, H, W].  With S < 4 split R-hat is undefined: the summaries are NaN and the two maps None."""
+    `ess` [G, C, H, W].  With S < 4 split R-hat is undefined: the summaries are NaN and the two maps None.
+
+    calibration = level (0.9, say; None, the default, changes nothing): the dict gains what `calibration` returns for the
+    pooled K * S samples -- `z`, `below`, `equal`, `hist` and CALIBRATION_KEYS -- in the same single read.  With fewer
+    than two pooled samples the four are None and the figures NaN."""
     replicas = int(replicas)
-    if replicas == 1:
+    if replicas == 1 and calibration is None:
         return _summarize(samples, x_orig)
     samples, x_orig, _ = _block(samples, x_orig)
     B, S = samples.shape[:2]
     if replicas < 1 or B % replicas:
         raise _lib.NhmcError(f'summarize: {B} chains are not a multiple of {replicas} replicas')
     G = B // replicas
-    diag = K.chain_diag(samples, replicas, rhat_threshold) if S >= 4 else None
+    diag = K.chain_diag(samples, replicas, rhat_threshold) if replicas > 1 and S >= 4 else None
+    cal = K.calibration(samples, x_orig, replicas) if calibration is not None and replicas * S >= 2 else None
+    extra = ([] if diag is None else [diag[2]]) + ([] if cal is None else [cal[3], cal[2].double()])
     out = _summarize(samples.reshape((G, replicas * S) + tuple(samples.shape[2:])), x_orig,
-                     extra=None if diag is None else diag[2])
-    conv = out.pop('extra', None)
-    out['replicas'] = replicas
-    out['rhat'], out['ess'] = (None, None) if diag is None else diag[:2]
-    for i, k in enumerate(CONVERGENCE_KEYS):
-        out[k] = np.full(G, np.nan) if conv is None else conv[:, i].copy()
+                     extra=torch.cat(extra, dim=1) if extra else None)
+    host = out.pop('extra', None)
+    if replicas > 1:
+        out['replicas'] = replicas
+        out['rhat'], out['ess'] = (None, None) if diag is None else diag[:2]
+        for i, k in enumerate(CONVERGENCE_KEYS):
+            out[k] = np.full(G, np.nan) if diag is None else host[:, i].copy()
+    if calibration is not None:
+        out.update(_no_calibration(G) if cal is None else _calibration_result(
+            cal[0], cal[1], host[:, 0 if diag is None else len(CONVERGENCE_KEYS):], cal[0][0].numel(), calibration))
     return out
 
 
@@ -183,3 +272,18 @@ def save_rhat_map(rhat, path):
     map01 = np.clip((np.nan_to_num(r, nan=1.0, posinf=np.inf) - 1.0) / 0.5, 0.0, 1.0)
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
     Image.fromarray(hot_colours(map01)).save(path)
+
+
+def save_calibration_map(z, path):
+    """The z-score map of one image, [C, H, W] (or [H, W]), as an 8-bit PNG in the `hot` colours: the maximum over the
+    channels of |z|, mapped clip(|z| / 3, 0, 1) -- black where the original sits at the mean of the draws, white from three
+    standard deviations.  NaN (all draws equal to the original) maps to 0, inf (all draws equal, the original elsewhere)
+    to 1."""
+    from PIL import Image
+    if isinstance(z, torch.Tensor):
+        z = z.detach().cpu().numpy()
+    a = np.nan_to_num(np.abs(np.asarray(z, dtype=np.float64)), nan=0.0, posinf=np.inf)
+    if a.ndim == 3:
+        a = a.max(axis=0)
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    Image.fromarray(hot_colours(np.clip(a / 3.0, 0.0, 1.0))).save(path)
