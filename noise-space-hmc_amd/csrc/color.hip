@@ -71,7 +71,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_color(const float4* __restrict__
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
               float gr = wt.w[c] * (wt.s * (wt.u * (-(2.0f * r[k]))));
-              if (apply_clip) gr = gr * nhmc_in1(e[k]);
+              if (apply_clip) gr = nhmc_masked(gr, nhmc_in1(e[k]));
               oe[k] = gr;
             }
             nhmc_stnt(&out[xbase + (int64_t)c * hw4 + q], o);

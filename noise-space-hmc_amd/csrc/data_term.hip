@@ -50,7 +50,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_data_inpaint(
         const float r = yb[se[c]] - v;
         acc += (double)(r * r);
         gr = -(2.0f * r);
-        if (apply_clip) gr = gr * nhmc_in1(xe[c]);
+        if (apply_clip) gr = nhmc_masked(gr, nhmc_in1(xe[c]));
       }
       oe[c] = gr;
     }
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_sr(
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           float gr = (-(2.0f * resid[BPS == 1 ? 0 : c / R])) * inv;
-          if (apply_clip) gr = gr * nhmc_in1(e[c]);
+          if (apply_clip) gr = nhmc_masked(gr, nhmc_in1(e[c]));
           oe[c] = gr;
         }
         nhmc_stnt(&g_out[row0 + (int64_t)rr * w4], o);
@@ -329,7 +329,7 @@ __device__ __forceinline__ float hdr_fwd(float v) { return nhmc_clip1(2.0f * v);
 __device__ __forceinline__ float hdr_grad(float v, float yv, double& acc) {
   const float r = yv - hdr_fwd(v);
   acc += (double)(r * r);
-  return ((-(2.0f * r)) * nhmc_in1(2.0f * v)) * 2.0f;
+  return nhmc_masked(-(2.0f * r), nhmc_in1(2.0f * v)) * 2.0f;
 }
 
 __global__ __launch_bounds__(NHMC_BLOCK) void k_hdr_H(const float4* __restrict__ x, float4* __restrict__ y, int64_t n4) {
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_data_hdr(
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       float gr = hdr_grad(apply_clip ? nhmc_clip1(xe[c]) : xe[c], ye[c], acc);
-      if (apply_clip) gr = gr * nhmc_in1(xe[c]);
+      if (apply_clip) gr = nhmc_masked(gr, nhmc_in1(xe[c]));
       oe[c] = gr;
     }
     nhmc_stnt(&g_xt[base + q], o);

@@ -108,7 +108,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd(
     for (int c = 0; c < 4; ++c) {
       const float u = nhmc_mix_u(k, xe[c], ee[c]);
       float gin = ge[c];
-      if (final_clip) gin = gin * nhmc_in1(nhmc_mix_pre(k, u, ee[c]));
+      if (final_clip) gin = nhmc_masked(gin, nhmc_in1(nhmc_mix_pre(k, u, ee[c])));
       // fused step: the gradient reaching x0 is gin*c3 (map_back); split surface: it is handed in
       nhmc_mix_vjp_body(k, gin, SPLIT ? se[c] : gin * k.c3, nhmc_in1(u), gx[c], gee[c]);
     }
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_mix_bwd_hdr(
       const float arg = 2.0f * nhmc_clip1(pre);                 // x / 0.5: exact in fp32
       const float r = ye[c] - nhmc_clip1(arg);
       acc += (double)(r * r);
-      const float gin = ((-(2.0f * r)) * nhmc_in1(arg)) * 2.0f; // clamp backward, then grad / 0.5
+      const float gin = nhmc_masked(-(2.0f * r), nhmc_in1(arg)) * 2.0f; // clamp backward, then grad / 0.5
       nhmc_mix_vjp_masked(k, gin, nhmc_in1(pre), nhmc_in1(u), gx[c], gee[c]);
     }
     nhmc_stnt(&g_xt[base + q], ox);

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_fwht_rows(const float* __restric
 #pragma unroll
         for (int e = 0; e < V; ++e) {
           float g = -(2.0f * (v[e] * scale));
-          if (apply_clip) g = g * nhmc_in1(xe[e]);
+          if (apply_clip) g = nhmc_masked(g, nhmc_in1(xe[e]));
           we[e] = g;
         }
       } else {                                                      // EPI_VJP
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_fwht_cols(const float* __restric
       vj.g_e[eoff] = ge;
     } else {
       v = -(2.0f * v);
-      if (apply_clip) v = v * nhmc_in1(xt[off]);
+      if (apply_clip) v = nhmc_masked(v, nhmc_in1(xt[off]));
       out[off] = v;
     }
   }
@@ -353,7 +353,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_fwht_cols256(const float* __rest
       if (apply_clip) {
         const nhmc_v4f xv = *reinterpret_cast<const nhmc_v4f*>(&xt[off]);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) gq[e] = gq[e] * nhmc_in1(xv[e]);
+        for (int e = 0; e < 4; ++e) gq[e] = nhmc_masked(gq[e], nhmc_in1(xv[e]));
       }
       *reinterpret_cast<nhmc_v4f*>(&out[off]) = gq;
     }

@@ -15,7 +15,7 @@ constexpr int SSIM_TH = 16, SSIM_TW = 32;        // window positions per block: 
 constexpr int SSIM_RH = SSIM_TH + SSIM_WIN - 1;  // staged rows: the tile plus the 6 pixels its windows reach below it
 constexpr int SSIM_RW = SSIM_TW + SSIM_WIN - 1;
 
-__device__ __forceinline__ float unit_range(float v) { return fminf(fmaxf((v + 1.0f) / 2.0f, 0.0f), 1.0f); }
+__device__ __forceinline__ float unit_range(float v) { return nhmc_unit_range(v); }   // NaN stays NaN (nhmc_common.h)
 
 // Block-level min / max of one value pair per thread (256 threads); result valid in thread 0.
 __device__ __forceinline__ void block_minmax(float& lo, float& hi, float* lds /* [8] */) {

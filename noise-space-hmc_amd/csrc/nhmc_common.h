@@ -85,8 +85,16 @@ __device__ __forceinline__ void nhmc_stnt(float4* p, const float4& v) {
   __builtin_nontemporal_store(w, reinterpret_cast<nhmc_v4f*>(p));
 }
 
-__device__ __forceinline__ float nhmc_clip1(float v) { return fminf(fmaxf(v, -1.0f), 1.0f); }
+// Clamps as torch.clamp: two compares and two selects, so a NaN passes through (fminf / fmaxf -- v_max_f32, v_med3_f32 --
+// return a bound for a NaN operand, which would turn a diverged chain's decode into a finite pixel).  Every other input,
+// -0.0 included, gets the bits of the min/max form.
+__device__ __forceinline__ float nhmc_clamp(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ float nhmc_clip1(float v) { return nhmc_clamp(v, -1.0f, 1.0f); }
+__device__ __forceinline__ float nhmc_unit_range(float v) { return nhmc_clamp((v + 1.0f) / 2.0f, 0.0f, 1.0f); }   // inverse_data_transform
 __device__ __forceinline__ float nhmc_in1(float v) { return (v >= -1.0f && v <= 1.0f) ? 1.0f : 0.0f; }
+// torch's clamp backward SELECTS: the gradient where the mask (nhmc_in1) is set, zero elsewhere, even when the gradient
+// is inf or NaN -- g * mask would give inf * 0 = NaN there.  For finite g the two forms are equal.
+__device__ __forceinline__ float nhmc_masked(float g, float mask) { return mask != 0.0f ? g : 0.0f; }
 
 // Square roots: plain sqrtf.  hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt makes sqrtf and the fp32 division
 // IEEE correctly rounded on gfx950 (no fast-math flag is set in build.py); tests/test_hygiene_gpu.py sweeps all 1001
@@ -119,9 +127,9 @@ __device__ __forceinline__ void nhmc_mix_decode(const NhmcMix& k, float x, float
 // The VJP's body, in autograd's rounding order: `gin` is the gradient w.r.t. the step's output (after the final clip's
 // mask), `g0` the gradient reaching x0 -- gin*c3 through map_back, except in k_mix_bwd's split form, which is handed it --
 // and `mu` = 1[-1 <= u <= 1] the x0 clip's mask.  Every product and the division are rounded separately
-// (-ffp-contract=off): g_xt = (g0*mu)/c2, g_e = c4*gin + (-g_xt)*c1.
+// (-ffp-contract=off), the masks select (nhmc_masked): g_xt = (mu ? g0 : 0)/c2, g_e = c4*gin + (-g_xt)*c1.
 __device__ __forceinline__ void nhmc_mix_vjp_body(const NhmcMix& k, float gin, float g0, float mu, float& g_xt, float& g_e) {
-  const float gu = (g0 * mu) / k.c2;
+  const float gu = nhmc_masked(g0, mu) / k.c2;
   g_xt = gu;
   g_e = k.c4 * gin + (-gu) * k.c1;
 }
@@ -129,7 +137,7 @@ __device__ __forceinline__ void nhmc_mix_vjp_body(const NhmcMix& k, float gin, f
 // Entry for kernels that keep u / pre, or only their mask bits mp = 1[-1 <= pre <= 1] and mu, between two passes.
 // `gin`: the data term's gradient w.r.t. the clipped decode.
 __device__ __forceinline__ void nhmc_mix_vjp_masked(const NhmcMix& k, float gin, float mp, float mu, float& g_xt, float& g_e) {
-  gin = gin * mp;                                            // final clip mask
+  gin = nhmc_masked(gin, mp);                                // final clip mask
   nhmc_mix_vjp_body(k, gin, gin * k.c3, mu, g_xt, g_e);
 }
 

@@ -174,8 +174,8 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_psnr_partial(const float4* __res
     const float* be = reinterpret_cast<const float*>(&b);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float ua = fminf(fmaxf((ae[c] + 1.0f) / 2.0f, 0.0f), 1.0f);   // inverse_data_transform
-      const float ub = fminf(fmaxf((be[c] + 1.0f) / 2.0f, 0.0f), 1.0f);
+      const float ua = nhmc_unit_range(ae[c]);   // inverse_data_transform; a NaN sample gives a NaN PSNR
+      const float ub = nhmc_unit_range(be[c]);
       const float d = ua - ub;
       acc += d * d;
     }

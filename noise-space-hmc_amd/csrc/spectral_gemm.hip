@@ -180,7 +180,8 @@ __global__ __launch_bounds__(64 * NW * NW, (NW == 2 && EPI != EPI_NONE) ? 4 : 1)
         q = -(2.0f * q);
         if (aux_img) {
           const nhmc_v4f xv = *reinterpret_cast<const nhmc_v4f*>(&aux_img[off]);
-          q.x = q.x * nhmc_in1(xv.x); q.y = q.y * nhmc_in1(xv.y); q.z = q.z * nhmc_in1(xv.z); q.w = q.w * nhmc_in1(xv.w);
+          q.x = nhmc_masked(q.x, nhmc_in1(xv.x)); q.y = nhmc_masked(q.y, nhmc_in1(xv.y));
+          q.z = nhmc_masked(q.z, nhmc_in1(xv.z)); q.w = nhmc_masked(q.w, nhmc_in1(xv.w));
         }
       }
       if (EPI == EPI_VJP) {
@@ -482,7 +483,8 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void k_pair256(
       o = -(2.0f * o);
       if (have_aux) {
         const nhmc_v4f xv = pre_aux[v];
-        o.x = o.x * nhmc_in1(xv.x); o.y = o.y * nhmc_in1(xv.y); o.z = o.z * nhmc_in1(xv.z); o.w = o.w * nhmc_in1(xv.w);
+        o.x = nhmc_masked(o.x, nhmc_in1(xv.x)); o.y = nhmc_masked(o.y, nhmc_in1(xv.y));
+        o.z = nhmc_masked(o.z, nhmc_in1(xv.z)); o.w = nhmc_masked(o.w, nhmc_in1(xv.w));
       }
     }
     if (EPI == EPI_VJP) {
@@ -974,8 +976,8 @@ __global__ __launch_bounds__(64 * NW * NW) void k_cgemm(
           for (int j = 0; j < 4; ++j) {
             const float r = yv[j] - a[j];
             lsum += (double)(r * r);
-            p[j] = a[j] > 0.0f ? r * (p[j] / a[j]) : 0.0f;        // d|Y| = Y / |Y|, sgn(0) = 0
-            q[j] = a[j] > 0.0f ? r * (q[j] / a[j]) : 0.0f;
+            p[j] = a[j] == 0.0f ? 0.0f : r * (p[j] / a[j]);       // d|Y| = Y / |Y|, sgn(0) = 0; a NaN |Y| stays NaN, as
+            q[j] = a[j] == 0.0f ? 0.0f : r * (q[j] / a[j]);       // torch.sgn's (`a > 0` would turn it into a zero gradient)
           }
           *reinterpret_cast<nhmc_v4f*>(&out_img[off]) = p;
           *reinterpret_cast<nhmc_v4f*>(&out_img[plane + off]) = q;
