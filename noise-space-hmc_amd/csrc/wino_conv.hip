@@ -27,7 +27,16 @@
 // last one half empty.  U keeps nhmc_wino_weights' layout [C][K][16] with K as it is; the tail block's loads of the upper
 // 32 rows are predicated off and zeros go to LDS instead, so nothing outside U is read.  A channel's MFMA chain is the same
 // A row against the same B rows in the same order whatever K is, so its bits do not depend on K.
+// Two workgroup geometries: k_conv3x3_wino, the four waves described above, for every instantiation; and k_conv3x3_wino8,
+// eight waves, two per SIMD, for the wide geometry without a tail block (TC = 32, K % 64 == 0), the default there.  Its wave
+// (fh, kh, th) holds the 8 frequencies 8 fh .. + 7 of wave (kh, th)'s outputs, 128 accumulators, so that the two halves of a
+// (kh, th) share a SIMD; before the output transform the pair exchanges accumulator halves through LDS, lane by lane, and
+// each wave transforms 8 of the lane's 16 channel rows.  Same LDS layout, same MFMA chains, same transform expressions: the
+// same bits.  NHMC_WINO_WAVES = 4 | 8, read per call, chooses (wc_waves); the comment above k_conv3x3_wino8 has the details.
 #include "nhmc_common.h"
+
+#include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -406,6 +415,313 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
 #endif
 }
 
+// ---- the eight-wave geometry of the wide kernel (TC = 32, K % 64 == 0): 512 threads, two waves per SIMD ----------------------
+// Wave (fh, kh, th), fh = wave >> 2, holds the same 32 channels x 32 tiles as wave (kh, th) above, for the 8 frequencies
+// 8 fh .. 8 fh + 7 only: acc[8], 128 registers, so that waves w and w + 4, the two frequency halves of one (kh, th), are
+// resident on one SIMD and each issues into the waits, the transform arithmetic and the load issue of the other.  A chunk is
+// 4 units of 8 MFMAs per wave: unit v is k-step v at the wave's frequency half (granules 2 fh, 2 fh + 1 of the operand
+// rows).  The LDS layout, the swizzle, the MFMA and every per-frequency chain over the channels are those of the four-wave
+// kernel, so every M_f has its bits.
+// Loader: thread (lc, lt, ty = tid >> 8) transforms channel lc of the chunk for the ONE tile of tile column lt in tile row
+// ty: rows 2 ty .. 2 ty + 3 of the column's 6 x 4 patch (rows 2 and 3 are loaded by both threads of a column), one V granule
+// per column b with the expressions of the four-wave loader, and U pieces 2 i + ty, i = 0 .. 3.
+// Epilogue: Y = A^T M A needs all 16 frequencies of a channel row in one lane.  The two waves of a pair hold the same
+// (channel rows, tile) in the same lane, so they exchange halves through LDS lane by lane: wave fh = 0 keeps accumulator
+// registers r = 0 .. 7 (channel rows (r & 3) + 8 (r >> 2) of the lane) and sends r = 8 .. 15, wave fh = 1 the reverse.  A wave
+// writes the float4 (frequency j of its half, registers 4 q .. + 3 of the half it sends) at float4 index
+// (16 wave + 2 j + q) * 64 + lane and reads its partner's at (16 (wave ^ 4) + 2 j + q) * 64 + lane: 8 x 16 x 64 float4 are
+// the 128 KB of the operand stages, every ds_write_b128 / ds_read_b128 lane group is contiguous
+// (tests/test_wino_exchange_cpu.py).  Each wave then runs the four-wave transform expression on its 8 channel rows.
+constexpr int WC8_XSLOTS = 16;                   // float4 per lane and wave in the exchange: 8 frequencies x 2 register quads
+
+__global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
+  constexpr int TC = 32, BLK_ROWS = 128 / TC, BLK_COLS = 2 * TC;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
+  const int kh = wave & 1, th = (wave >> 1) & 1;
+  const int fh = __builtin_amdgcn_readfirstlane(wave >> 2);
+  const int C = a.C, K = a.K, H = a.H, W = a.W, HW = H * W;
+#ifdef NHMC_WINO_STAMPS
+  unsigned long long t64[7] = {};
+  unsigned t32[17] = {};
+  const int stamp_ch = nhmc_wino_stamp_chunk < C / WC_CHUNK ? nhmc_wino_stamp_chunk : C / WC_CHUNK - 1;
+#endif
+  WC_T64(0);
+
+  const int total = gridDim.x;
+  int logical = blockIdx.x;
+  if ((total & 7) == 0) logical = (logical & 7) * (total >> 3) + (logical >> 3);
+  const int kblocks = K / WC_KBLK;
+  const int kb = logical % kblocks, sp = logical / kblocks;
+  const int cb = sp % a.col_blocks, rb = (sp / a.col_blocks) % a.row_blocks, n = sp / (a.col_blocks * a.row_blocks);
+  const int h0 = rb * BLK_ROWS, w0 = cb * BLK_COLS;
+
+  // ---- loader roles.  The patch's columns and the lane exchange are the four-wave loader's; q = 0 .. 3 is row 2 ty + q of
+  // the column's patch, image row h0 - 1 + 2 ty + q
+  const int ty = tid >> 8, t8 = tid & 255, lc = t8 >> 5, lt = tid & 31;
+  unsigned voff[4], eoff[4];
+  unsigned okmask = 0;
+  const int ecol = lt == 0 ? w0 - 1 : w0 + 2 * TC;
+  const bool eok = (lt == 0 || lt == TC - 1) && (unsigned)ecol < (unsigned)W;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int row = h0 + 2 * ty - 1 + q;
+    const bool rok = (unsigned)row < (unsigned)H;
+    voff[q] = rok ? 4u * (unsigned)(lc * HW + row * W + w0 + 2 * lt) : 0u;
+    eoff[q] = rok ? 4u * (unsigned)(lc * HW + row * W + (eok ? ecol : w0 + 2 * lt)) : 0u;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int col = w0 + 2 * lt - 1 + s;
+      const bool ok = rok && (unsigned)col < (unsigned)W;
+      okmask |= ok ? 1u << (q * 4 + s) : 0u;
+    }
+  }
+  const float* xn = a.x + (int64_t)n * C * HW;
+  const char* un = reinterpret_cast<const char*>(a.U + (int64_t)kb * WC_KBLK * 16);
+  const unsigned uoff = 16u * t8 + (unsigned)ty * (unsigned)K * 64u;                // float4 t8 of piece 2 i + ty
+  const int uw = (t8 & ~3) * 4 + (((t8 & 3) ^ wc_swz(t8 >> 2)) << 2) + 1024 * ty;
+  const int vw = (lc * 64 + 32 * ty + lt) * 16, vswz = wc_swz(lt);                  // row lc * 64 + 32 ty + lt
+
+  // A chunk's 12 loads per thread: 0 .. 7 the patch (row q = i >> 1: its 8-byte load, then its edge load), 8 .. 11 U pieces
+  wc_v2f xm[4];
+  float xl[4], xq[4], xe[4];
+  nhmc_v4f ur[4];
+  auto load_one = [&](int ch, int i) {
+    if (i < 8) {
+      const char* xs = reinterpret_cast<const char*>(xn + (int64_t)ch * WC_CHUNK * HW);
+      const int q = i >> 1;
+      unsigned off = (i & 1) ? eoff[q] : voff[q];
+      asm volatile("" : "+v"(off));
+      if (i & 1) xe[q] = *reinterpret_cast<const float*>(xs + off);
+      else xm[q] = *reinterpret_cast<const wc_v2f*>(xs + off);
+    } else {
+      const char* us = un + (int64_t)ch * WC_CHUNK * K * 64 + (int64_t)(2 * (i - 8)) * K * 64;
+      unsigned off = uoff;
+      asm volatile("" : "+v"(off));
+      ur[i - 8] = *reinterpret_cast<const nhmc_v4f*>(us + off);
+    }
+  };
+  auto issue_loads = [&](int ch, int first, int last) {
+#pragma unroll
+    for (int i = first; i < last; ++i) load_one(ch, i);
+  };
+  auto pin_patch = [&]() {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      asm volatile("" : "+v"(xm[q]));
+      asm volatile("" : "+v"(xe[q]));
+    }
+  };
+  auto exchange_patch = [&]() {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      xl[q] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(xm[q].y), 0x138, 0xF, 0xF, false));
+      xq[q] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(xm[q].x), 0x130, 0xF, 0xF, false));
+      xl[q] = lt == 0 ? xe[q] : xl[q];
+      xq[q] = lt == TC - 1 ? xe[q] : xq[q];
+    }
+  };
+  auto d = [&](int q, int s) {
+    const float v = s == 0 ? xl[q] : s == 1 ? xm[q].x : s == 2 ? xm[q].y : xq[q];
+    return (okmask >> (q * 4 + s)) & 1u ? v : 0.0f;
+  };
+  float e[4];
+  auto stage_rows = [&](int b) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      e[q] = b == 0 ? d(q, 0) - d(q, 2) : b == 1 ? d(q, 1) + d(q, 2) : b == 2 ? d(q, 2) - d(q, 1) : d(q, 1) - d(q, 3);
+  };
+  nhmc_v4f vt;
+  auto stage_cols = [&]() { vt.x = e[0] - e[2]; vt.y = e[1] + e[2]; vt.z = e[2] - e[1]; vt.w = e[1] - e[3]; };
+  auto stage_v = [&](int st, int b) {
+    *reinterpret_cast<nhmc_v4f*>(lds + st * 2 * WC_OPER + WC_OPER + vw + ((b ^ vswz) << 2)) = vt;
+  };
+  auto stage_u = [&](int st, int i) { *reinterpret_cast<nhmc_v4f*>(lds + st * 2 * WC_OPER + uw + 2048 * i) = ur[i]; };
+
+  const int chunks = C / WC_CHUNK;
+  f32x16 acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+
+  const int swz = wc_swz(lr);
+  const int arow = (lh * 64 + kh * 32 + lr) * 16, brow = WC_OPER + (lh * 64 + th * 32 + lr) * 16;
+  const int go[2] = {((2 * fh) ^ swz) << 2, ((2 * fh + 1) ^ swz) << 2};              // the wave's two granules of a row
+  float av[2][8], bv[2][8];
+  auto fetch_half = [&](int st, int v, int g, float (&fa)[8], float (&fb)[8]) {      // MFMAs 4 g .. 4 g + 3 of unit v
+    const float* S = lds + st * 2 * WC_OPER + v * 2 * 64 * 16;
+    const nhmc_v4f va = *reinterpret_cast<const nhmc_v4f*>(S + arow + go[g]);
+    const nhmc_v4f vb = *reinterpret_cast<const nhmc_v4f*>(S + brow + go[g]);
+    fa[4 * g + 0] = va.x; fa[4 * g + 1] = va.y; fa[4 * g + 2] = va.z; fa[4 * g + 3] = va.w;
+    fb[4 * g + 0] = vb.x; fb[4 * g + 1] = vb.y; fb[4 * g + 2] = vb.z; fb[4 * g + 3] = vb.w;
+  };
+  // One unit: 8 MFMAs, every gap fenced.  Gaps 0 and 1 read the operands of the following unit (unit 3: unit 0 of stage
+  // `st`, which the caller has flipped behind the barrier) and hold no store.  Units 1 and 2 stage columns 2 (v - 1), + 1 of
+  // V and U pieces v - 1, v + 1 of the following chunk into stage st ^ 1, at most one store per gap with the arithmetic that
+  // feeds it in front: the exchange of the patch in gap 0 of unit 1, row differences in gaps 1 and 4, the V stores in gaps 3
+  // and 5, the U stores in gaps 6 and 7.  The patch of chunk `cl`, two chunks ahead, is loaded as soon as the staging has
+  // read the last one: rows 0 - 2 in gaps 5 - 7 of unit 2, in front of the barrier (which waits for LDS only, so they stay in
+  // flight across it), row 3 in gaps 0 and 1 of unit 3; its 4 U pieces follow in gaps 1, 3, 5, 7 of unit 0.  Issued behind
+  // the barrier, one per gap of unit 3, the patch cost 2 % of the kernel (with the priority below; without it, nothing)
+  int ch = 0;                                       // the chunk being multiplied
+  auto unit = [&](int v, int st, int cl) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[v & 1][j], bv[v & 1][j], acc[j], 0, 0, 0);
+      if (j == 0 && v == 1) {
+        WC_T32(7);
+        pin_patch();
+        exchange_patch();
+        WC_T32(8);
+      }
+      if (j < 2) fetch_half(st, (v + 1) & 3, j, av[(v + 1) & 1], bv[(v + 1) & 1]);
+      if (v == 2 && j >= 5) issue_loads(cl, 2 * (j - 5), 2 * (j - 5) + 2);
+      if (v == 3 && j < 2) issue_loads(cl, 6 + j, 7 + j);
+      if (v == 0 && (j & 1)) issue_loads(cl, 8 + j / 2, 9 + j / 2);
+      if (v == 1 || v == 2) {
+        const int b = 2 * (v - 1);
+        if (j == 1) stage_rows(b);
+        if (j == 2) stage_cols();
+        if (j == 3) stage_v(st ^ 1, b);
+        if (j == 4) { stage_rows(b + 1); stage_cols(); }
+        if (j == 5) stage_v(st ^ 1, b + 1);
+        if (j == 6) stage_u(st ^ 1, v - 1);
+        if (j == 7) stage_u(st ^ 1, v + 1);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  issue_loads(0, 0, 12);
+  exchange_patch();
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    stage_rows(b);
+    stage_cols();
+    stage_v(0, b);
+    stage_u(0, b);
+  }
+  __syncthreads();
+  WC_T64(1);
+  int cl = 1 < chunks ? 1 : 0;
+  issue_loads(cl, 0, 8);
+  fetch_half(0, 0, 0, av[0], bv[0]);
+  fetch_half(0, 0, 1, av[0], bv[0]);
+  // ONE instance of the chunk body, as in the four-wave kernel: the last chunk stages itself once more into the idle buffer.
+  // One barrier per chunk, between units 2 and 3, when unit 3's operands are in registers: the first operands of the
+  // following chunk are read behind the first MFMAs of unit 3.
+  // The two waves of a SIMD run the same stream in lockstep.  Waves 4 - 7, dispatched second, lose every arbitration of the
+  // SIMD's issue to their partners; one static s_setprio 1 for them in front of the loop, with the early patch loads above,
+  // is worth 2 % of the kernel (neither alone is outside the run-to-run spread; profiles/r12_wino_waves_ab.txt)
+  int st = 0;
+  if (fh) __builtin_amdgcn_s_setprio(1);
+  WC_T64(2);
+  WC_R64(5);
+  do {
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+      WC_T32(v);
+      if (v == 2) cl = ch + 2 < chunks ? ch + 2 : chunks - 1;
+      unit(v, st, cl);
+    }
+    WC_T32(9);
+    __syncthreads();                                // stage st ^ 1 is complete, and every wave is done reading stage st
+    WC_T32(10);
+    st ^= 1;
+    WC_T32(3);
+    unit(3, st, cl);
+    WC_T32(12);
+  } while (++ch < chunks);
+  WC_T64(3);
+  WC_R64(6);
+
+  // ---- the exchange, then Y = A^T M A for the wave's 8 channel rows per lane: rows (r & 3) + 8 (r >> 2), r = 8 fh + rr
+  const int oh = h0 + 2 * th, ow = w0 + 2 * lr;
+  const bool has_bias = a.bias != nullptr, has_add = a.add != nullptr;
+  const int k0 = kb * WC_KBLK + kh * 32 + 4 * lh + 16 * fh;
+  const bool odd = lr & 1;
+  const int64_t at0 = (((int64_t)n * K + k0) * H + oh) * W + ow + (odd ? W - 2 : 0);
+  float bc[8];
+  nhmc_v4f ad[8];
+#pragma unroll
+  for (int rr = 0; rr < 8; ++rr) {
+    bc[rr] = 0.0f;
+    ad[rr] = nhmc_v4f{0.0f, 0.0f, 0.0f, 0.0f};
+  }
+  if (has_bias) {
+#pragma unroll
+    for (int rr = 0; rr < 8; ++rr) bc[rr] = a.bias[k0 + (rr & 3) + 8 * (rr >> 2)];
+  }
+  if (has_add) {
+#pragma unroll
+    for (int rr = 0; rr < 8; ++rr)
+      ad[rr] = *reinterpret_cast<const nhmc_v4f*>(a.add + at0 + (int64_t)((rr & 3) + 8 * (rr >> 2)) * HW);
+  }
+  nhmc_v4f* xch = reinterpret_cast<nhmc_v4f*>(lds);
+  const int xw = wave * WC8_XSLOTS * 64 + lane, xr = (wave ^ 4) * WC8_XSLOTS * 64 + lane;
+  __syncthreads();                                  // every wave has left the loop: the operand stages are free
+  auto send = [&](auto half) {                      // the 8 registers of each frequency that the partner transforms
+    constexpr int RS = decltype(half)::value ? 0 : 8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+        xch[xw + (2 * j + q) * 64] = nhmc_v4f{acc[j][RS + 4 * q], acc[j][RS + 4 * q + 1], acc[j][RS + 4 * q + 2], acc[j][RS + 4 * q + 3]};
+  };
+  if (fh == 0) send(std::integral_constant<int, 0>{});
+  else send(std::integral_constant<int, 1>{});
+  __syncthreads();
+  nhmc_v4f got[8][2];                               // the partner's frequencies, registers 8 fh + 4 q .. + 3
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) got[j][q] = xch[xr + (2 * j + q) * 64];
+  auto neighbour = [](float v) {                    // lane ^ 1's value: quad_perm [1, 0, 3, 2]
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
+  };
+  auto finish = [&](auto half) {
+    constexpr int F = decltype(half)::value, RK = 8 * F;
+    auto M = [&](int f, int rr) { return (f >> 3) == F ? acc[f & 7][RK + rr] : got[f & 7][rr >> 2][rr & 3]; };
+#pragma unroll
+    for (int rr = 0; rr < 8; ++rr) {
+      float t[2][4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        t[0][b] = (M(4 * b + 0, rr) + M(4 * b + 1, rr)) + M(4 * b + 2, rr);
+        t[1][b] = (M(4 * b + 1, rr) - M(4 * b + 2, rr)) - M(4 * b + 3, rr);
+      }
+      wc_v2f o[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        o[i].x = (t[i][0] + t[i][1]) + t[i][2];
+        o[i].y = (t[i][1] - t[i][2]) - t[i][3];
+        o[i].x = has_bias ? o[i].x + bc[rr] : o[i].x;
+        o[i].y = has_bias ? o[i].y + bc[rr] : o[i].y;
+      }
+      const wc_v2f keep = odd ? o[1] : o[0], give = odd ? o[0] : o[1];
+      const wc_v2f recv = {neighbour(give.x), neighbour(give.y)};
+      nhmc_v4f v;
+      v.x = odd ? recv.x : keep.x; v.y = odd ? recv.y : keep.y; v.z = odd ? keep.x : recv.x; v.w = odd ? keep.y : recv.y;
+      if (has_add) v += ad[rr];
+      __builtin_nontemporal_store(v, reinterpret_cast<nhmc_v4f*>(a.y + at0 + (int64_t)((rr & 3) + 8 * (rr >> 2)) * HW));
+    }
+  };
+  __builtin_amdgcn_sched_barrier(0);
+  if (fh == 0) finish(std::integral_constant<int, 0>{});
+  else finish(std::integral_constant<int, 1>{});
+  WC_T64(4);
+#ifdef NHMC_WINO_STAMPS
+  if (nhmc_wino_stamps && lane == 0) {
+    unsigned long long* out = nhmc_wino_stamps + ((size_t)blockIdx.x * 8 + wave) * 24;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) out[i] = t64[i];
+#pragma unroll
+    for (int i = 0; i < 17; ++i) out[7 + i] = t32[i];
+  }
+#endif
+}
+
 // U[ci][ko][f = 4 b + a] = (G g G^T)[a][b], G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1].
 // forward: (ci, ko) = (c, k), g = w[k][c];  backward-data: (ci, ko) = (k, c), g[r][s] = w[k][c][2 - r][2 - s].
 __global__ __launch_bounds__(NHMC_BLOCK) void k_wino_weights(const float* __restrict__ w, float* __restrict__ U, int C, int K,
@@ -468,9 +784,44 @@ int wc_listed(const WcRow (&table)[N], int backward, int c, int k, int h) {
   return 0;
 }
 
+// Waves per workgroup, read per call (as NHMC_WINO is in Python): NHMC_WINO_WAVES = 4 or 8, unset = WC_DEFAULT_WAVES.  The
+// eight-wave kernel exists for the wide geometry without a tail block; every other instantiation runs on four waves whatever
+// the variable says.  -1: the variable holds something else.  Eight waves are the default because they were faster than four
+// at 128->128 @ 256^2, 256->256 @ 128^2 and 512->256 @ 64^2, forward and backward-data, by 3.8 - 4.8 % against a
+// run-to-run spread of at most 1.1 % (profiles/r12_wino_waves_ab.txt).
+constexpr int WC_DEFAULT_WAVES = 8;
+
+int wc_waves() {
+  const char* v = std::getenv("NHMC_WINO_WAVES");
+  if (!v || !*v) return WC_DEFAULT_WAVES;
+  if (v[0] == '4' && !v[1]) return 4;
+  if (v[0] == '8' && !v[1]) return 8;
+  return -1;
+}
+
+int wc_launch8(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c, int k, int h, int w,
+               nhmc_stream_t stream) {
+  static bool attr_set[64] = {};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wino8), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            WC_LDS_BYTES) != hipSuccess)
+      return NHMC_ERR_LAUNCH;
+    if (dev >= 0 && dev < 64) attr_set[dev] = true;
+  }
+  const WinoArgs a{x, u, bias, add, y, c, k, h, w, h / WC_ROWS, w / WC_COLS};
+  const int64_t blocks = (int64_t)n * a.row_blocks * a.col_blocks * (k / WC_KBLK);
+  NHMC_LAUNCH(k_conv3x3_wino8, dim3((unsigned)blocks), dim3(512), WC_LDS_BYTES, nhmc_s(stream), a);
+  return nhmc_launch_status();
+}
+
 template <int TC, bool TAIL = false>
 int wc_launch(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c, int k, int h, int w,
               nhmc_stream_t stream) {
+  const int waves = wc_waves();
+  if (waves < 0) return NHMC_ERR_ARG;
+  if (TC == 32 && !TAIL && waves == 8) return wc_launch8(x, u, bias, add, y, n, c, k, h, w, stream);
   static bool attr_set[64] = {};                             // raise the dynamic-LDS limit once per device
   int dev = 0;
   (void)hipGetDevice(&dev);

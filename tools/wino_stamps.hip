@@ -4,6 +4,8 @@
 // in-kernel shader clock.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off tools/wino_stamps.hip -o tools/wino_stamps
 //   tools/wino_stamps [n c k h w]        (default: 64 128 128 256 256, then 64 512 256 64 64)
+//   NHMC_WINO_WAVES=4|8 chooses the geometry as in the library (k_conv3x3_wino or k_conv3x3_wino8, which keeps the same
+//   stamp slots: 8 x 24 values per workgroup)
 // Random data; >= 2 s of back-to-back unstamped launches first; then one stamped launch each for the first, the middle and
 // the last chunk of every workgroup.  Prints the median over all waves, in shader cycles, per phase, and unit 4, one of the
 // four units that stage the following chunk, split at its MFMAs 1, 3, 5 and 7 (reads, arithmetic, V stores, U stores).
@@ -35,7 +37,9 @@ static int run_shape(int n, int c, int k, int h, int w) {
   if (!wc_covers(n, c, k, h, w)) { std::printf("[%d,%d->%d,%dx%d] is not a shape of the wide geometry\n", n, c, k, h, w); return 1; }
   const size_t nx = (size_t)n * c * h * w, ny = (size_t)n * k * h * w, nw = (size_t)k * c * 9, nu = (size_t)k * c * 16;
   const int chunks = c / WC_CHUNK;
-  const size_t waves = (size_t)n * (h / WC_ROWS) * (w / WC_COLS) * (k / WC_KBLK) * 4;
+  const int geometry = wc_waves();                    // NHMC_WINO_WAVES, as the library reads it
+  if (geometry < 0) { std::printf("NHMC_WINO_WAVES must be 4 or 8\n"); return 1; }
+  const size_t waves = (size_t)n * (h / WC_ROWS) * (w / WC_COLS) * (k / WC_KBLK) * geometry;
   float *X, *Wt, *U, *Y;
   unsigned long long* ST;
   CK(hipMalloc(&X, nx * 4)); CK(hipMalloc(&Y, ny * 4)); CK(hipMalloc(&Wt, nw * 4)); CK(hipMalloc(&U, nu * 4));
@@ -88,6 +92,15 @@ static int run_shape(int n, int c, int k, int h, int w) {
       std::printf("   in-kernel shader clock (loop cycles / loop time on the 100 MHz clock): %.3f GHz\n", ghz);
       std::printf("   workgroup, median cycles: prologue %.0f | loop %.0f = %.0f per chunk (64 MFMAs = 4096) | epilogue %.0f | whole %.0f\n",
                   d64(0, 1) + d64(1, 2), d64(2, 3), d64(2, 3) / chunks, d64(3, 4), d64(0, 4));
+    }
+    if (geometry == 8) {
+      // eight waves: a wave's chunk is 4 units of 8 MFMAs; two waves share the pipe, so a unit is 1024 cycles of it.  Stamps 0,
+      // 1, 2: the heads of units 0 - 2; 9 / 10 around the barrier; 3 the head of unit 3; 12 the chunk's end; 7 / 8 around the
+      // wait for the patch and its exchange, in unit 1
+      std::printf("   %-6s chunk (%2d): units 0-2 %.0f %.0f %.0f (to the barrier) | of unit 1, patch wait and exchange %.0f | barrier %.0f | "
+                  "unit 3 %.0f | chunk %.0f\n", sel_name[s], sel[s], d32(0, 1), d32(1, 2), d32(2, 9), d32(7, 8), d32(9, 10), d32(3, 12),
+                  d32(0, 12));
+      continue;
     }
     std::printf("   %-6s chunk (%2d): units 0-6", sel_name[s], sel[s]);
     for (int u = 0; u < 6; ++u) std::printf(" %.0f", d32(u, u + 1));
