@@ -721,6 +721,46 @@ int nhmc_calibration(const float* samples, const float* x_orig, float* z, int32_
                      double* ws, int n_groups, int n_replicas, int n_samples, int64_t n_elem, nhmc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Credible interval and median of the posterior samples, on the device: the interval "Calibration" speaks of.
+ *
+ *   samples : fp32 [n_groups * n_replicas][n_samples][n_elem], laid out and pooled as for nhmc_calibration: draw i of
+ *             group g is row g * n + i - 1 of the block, n = n_replicas * n_samples.  Any value, NaN and +-inf included.
+ *   x_orig  : fp32 [n_groups][n_elem], or NULL.    lower, median, upper : fp32 [n_groups][n_elem].
+ *   summary : fp64 [n_groups][6].  ws : double, nhmc_credible_ws_bytes(n_groups, n_elem) bytes: 8 partials for each of the
+ *             nhmc_credible_tiles(n_elem) tiles (256 elements each) of every group.
+ *   Validation, before any launch: null pointer (x_orig excepted) / non-positive size -> ARG; samples, x_orig, lower, median
+ *   or upper not 16-byte aligned or n_elem % 4 != 0 -> ALIGN; n < 2, n > 1024, n_groups > 65535, k < 1 or k > n / 2 -> SHAPE.
+ *
+ * Definition, per element of group g.  Its n pooled draws are sorted in torch.sort's order -- ascending, every NaN above
+ * +inf -- into d_(1) <= ... <= d_(n).
+ *   lower  = d_(k),  upper = d_(n+1-k)
+ *   median = d_((n+1)/2) for odd n;  (d_(n/2) + d_(n/2+1)) * 0.5f for even n: one fp32 add and one fp32 multiply, which
+ *            is np.median of a float32 array.
+ *   Selection is exact: lower and upper are values among the draws, and so is median for odd n.  A NaN that is selected
+ *   comes back as a quiet NaN.  -0.0 and +0.0 compare equal and either sign may come back.
+ * Summary per group, over its n_elem elements, t being the original's value:
+ *     [0] sum_width       = sum ((double)upper - (double)lower)
+ *     [1] max_width       = the largest such width
+ *     [2] sum_err2_median = sum ((double)t - (double)median)^2
+ *     [3] n_inside        = #{lower <= t <= upper}     fp32 comparisons
+ *     [4] n_point         = #{upper == lower}
+ *     [5] n_nan           = #{upper is NaN}
+ *   x_orig == NULL: [2] and [3] are NaN.  NaN is never turned into a number: a NaN width (a NaN bound, or inf - inf) makes
+ *   [0] NaN and [1] NaN, so [1] is NaN whenever [5] > 0; [3] and [4] count only what compares true.  What one group holds
+ *   never changes a bit of another group's outputs or summary.
+ * Reductions: per-tile fp64 partials in ws and a fixed-order second pass by one wave per group; no float atomics, equal
+ *   inputs give equal bits.
+ * Two kernels, chosen from n, return the same bits: for n <= 64 a sorting network over registers that reads every sample
+ *   value once -- n * 4 + 4 bytes per element read, 12 written -- and for larger n a radix select that reads the draws 16
+ *   times.  NHMC_CREDIBLE_PATH=general in the environment, read per call, sends every n through the second (register or
+ *   unset: the choice above; anything else -> ARG).
+ * ---------------------------------------------------------------------------------- */
+int nhmc_credible_tiles(int64_t n_elem);
+size_t nhmc_credible_ws_bytes(int n_groups, int64_t n_elem);
+int nhmc_credible(const float* samples, const float* x_orig, float* lower, float* median, float* upper, double* summary,
+                  double* ws, int n_groups, int n_replicas, int n_samples, int64_t n_elem, int k, nhmc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * a1  Momentum / accept noise: Philox4x32-10 keyed by seed, counted by
  *     (element quad, chain_id0 + chain, draw, tag) -- independent of how chains are sharded.
  *     Replaces torch.randn_like (main_sampling.py:692) and torch.rand(1) (:720).

@@ -28,6 +28,11 @@ replica r of image s is s * K + r.  The report pools an image's K * S samples an
 (nhmc.metrics.calibration): the coverage of the central interval nearest to LEVEL against its nominal value, spread / skill,
 the RMS z-score, the correlation of |error| with the sample std and the PSNR of the posterior mean -- CALIBRATION_COLUMNS
 in the JSON rows and, with `--save_images`, `calibration_map_{s}.png`.  Without the flag nothing changes.
+
+`--credible [LEVEL]` (LEVEL = 0.9 when bare) adds, per image, the interval that coverage is computed for and the median
+(nhmc.metrics.credible): the order statistics d_(k) and d_(n+1-k) of the image's pooled draws per element and their median --
+CREDIBLE_COLUMNS in the JSON rows, after the calibration columns, and, with `--save_images`, `{s}_median.png`,
+`{s}_lower.png`, `{s}_upper.png` and `ci_width_map_{s}.png`.  Without the flag nothing changes.
 """
 import argparse
 import glob
@@ -90,6 +95,9 @@ def get_parser(latent=False):
     p.add_argument('--calibration', type=float, nargs='?', const=0.9, default=None, metavar='LEVEL',
                    help='report the calibration of the samples against the original: coverage of the central interval '
                         'nearest to LEVEL (0.9 when the flag is bare), spread/skill, z-score RMS, |error|~std correlation')
+    p.add_argument('--credible', type=float, nargs='?', const=0.9, default=None, metavar='LEVEL',
+                   help='report the central credible interval nearest to LEVEL (0.9 when the flag is bare) and the median of '
+                        "the samples per pixel: the interval's width, the share of the original inside it, PSNR of the median")
     return p
 
 
@@ -259,14 +267,17 @@ def _setup(opt, latent):
 COLUMNS = ('image', 'psnr_mean', 'psnr_std', 'ssim_mean', 'ssim_std', 'std_map_min', 'std_map_max', 'n_samples')
 REPLICA_COLUMNS = ('replicas',) + metrics.CONVERGENCE_KEYS          # appended to COLUMNS with --replicas K > 1
 CALIBRATION_COLUMNS = metrics.CALIBRATION_KEYS                      # appended last with --calibration
-INT_COLUMNS = ('image', 'n_samples', 'replicas', 'n_constant', 'n_tied', 'n_flat')
+CREDIBLE_COLUMNS = metrics.CREDIBLE_KEYS                            # appended after those with --credible
+INT_COLUMNS = ('image', 'n_samples', 'replicas', 'n_constant', 'n_tied', 'n_flat', 'ci_rank', 'n_point', 'n_nan')
 
 
-def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, rhat_threshold=1.1, calibration=None):
-    """Gathers the per-image rows (COLUMNS, with K > 1 replicas + REPLICA_COLUMNS, with --calibration + CALIBRATION_COLUMNS)
-    over the ranks in global image order, prints the report on rank 0 and returns the [n, 3] table (image, PSNR mean, PSNR
-    std over its samples)."""
-    columns = COLUMNS + (REPLICA_COLUMNS if replicas > 1 else ()) + (CALIBRATION_COLUMNS if calibration is not None else ())
+def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, rhat_threshold=1.1, calibration=None,
+            credible=None):
+    """Gathers the per-image rows (COLUMNS, with K > 1 replicas + REPLICA_COLUMNS, with --calibration + CALIBRATION_COLUMNS,
+    with --credible + CREDIBLE_COLUMNS) over the ranks in global image order, prints the report on rank 0 and returns the
+    [n, 3] table (image, PSNR mean, PSNR std over its samples)."""
+    columns = COLUMNS + (REPLICA_COLUMNS if replicas > 1 else ()) + (CALIBRATION_COLUMNS if calibration is not None else ()) + \
+        (CREDIBLE_COLUMNS if credible is not None else ())
     local = torch.tensor(rows, dtype=torch.float64, device=device).reshape(-1, len(columns))
     full = sharding.gather_chains(local, n_images, rank, world).cpu()
     table = full[:, :3].float()
@@ -288,6 +299,12 @@ def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, r
                 print(f'image {int(idx)}: calibration: coverage {c["coverage"]:.4f} at nominal {c["coverage_nominal"]:.4f}, '
                       f'spread/skill {c["spread_skill"]:.3f}, z rms {c["z_rms"]:.3f}, |err|~std r {c["err_std_corr"]:.3f}, '
                       f'PSNR of the posterior mean {c["psnr_of_mean"]:.3f}, tied {int(c["n_tied"])} flat {int(c["n_flat"])}')
+            if credible is not None and c['ci_rank'] == c['ci_rank']:       # NaN: fewer than two pooled samples
+                k_, n_ = int(c['ci_rank']), int(c['n_samples'])
+                print(f'image {int(idx)}: credible interval: order statistics {k_} and {n_ + 1 - k_} of {n_} draws '
+                      f'(level {c["ci_level"]:.4f}), width mean {c["ci_width_mean"]:.4f} max {c["ci_width_max"]:.4f}, '
+                      f'original inside {c["ci_inside"]:.4f}, PSNR of the median {c["psnr_of_median"]:.3f}, '
+                      f'point elements {int(c["n_point"])}')
         print(f'Total Average PSNR: {float(table[:, 1].nanmean()):.3f}  images: {table.shape[0]}')
         # main_sampling.py:560: the average over the images, and in parentheses the mean over the images of each
         # image's std over its samples
@@ -297,6 +314,11 @@ def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, r
             print(f'Total Average calibration: coverage {avg["coverage"]:.4f} at nominal {avg["coverage_nominal"]:.4f}, '
                   f'spread/skill {avg["spread_skill"]:.3f}, z rms {avg["z_rms"]:.3f}, |err|~std r {avg["err_std_corr"]:.3f}, '
                   f'PSNR of the posterior mean {avg["psnr_of_mean"]:.3f}')
+        if credible is not None:
+            avg = {k: float(full[:, columns.index(k)].nanmean()) for k in CREDIBLE_COLUMNS}
+            print(f'Total Average credible interval: level {avg["ci_level"]:.4f}, width mean {avg["ci_width_mean"]:.4f} '
+                  f'max {avg["ci_width_max"]:.4f}, original inside {avg["ci_inside"]:.4f}, '
+                  f'PSNR of the median {avg["psnr_of_median"]:.3f}')
         if metrics_out:
             import json
             as_json = lambda k, v: (int(v) if k in INT_COLUMNS and v == v else (v if v == v else None))
@@ -309,19 +331,26 @@ def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, r
 
 def _metric_rows(batch, summary):
     """One COLUMNS row per image of `batch` from a `metrics.summarize` result (entry i of it for image i); a pooled
-    summary (replicas > 1) appends REPLICA_COLUMNS, one with the calibration figures CALIBRATION_COLUMNS."""
+    summary (replicas > 1) appends REPLICA_COLUMNS, one with the calibration figures CALIBRATION_COLUMNS, one with the
+    credible interval's CREDIBLE_COLUMNS."""
     pooled = summary.get('replicas', 1) > 1
     return [[float(s)] + [float(summary[c][i]) for c in COLUMNS[1:-1]] + [float(summary['n_samples'])] +
             ([float(summary['replicas'])] + [float(summary[c][i]) for c in metrics.CONVERGENCE_KEYS] if pooled else []) +
-            ([float(summary[c][i]) for c in CALIBRATION_COLUMNS] if 'coverage' in summary else [])
+            ([float(summary[c][i]) for c in CALIBRATION_COLUMNS] if 'coverage' in summary else []) +
+            ([float(summary[c][i]) for c in CREDIBLE_COLUMNS] if 'ci_level' in summary else [])
             for i, s in enumerate(batch)]
 
 
 def _save_report_images(summary, k, s, one_sample, folder):
     """`{s}_mean.png` and, with two samples or more, `std_dev_map_{s}.png` (main_sampling.py:494-507); `rhat_map_{s}.png`
-    and `calibration_map_{s}.png` where the summary holds those maps."""
+    and `calibration_map_{s}.png` where the summary holds those maps; with the credible interval's maps `{s}_median.png`,
+    `{s}_lower.png`, `{s}_upper.png` and `ci_width_map_{s}.png`."""
     if summary.get('z') is not None:
         metrics.save_calibration_map(summary['z'][k], os.path.join(folder, f'calibration_map_{s}.png'))
+    if summary.get('median') is not None:
+        for name in ('median', 'lower', 'upper'):
+            sampler._save_png(summary[name][k], os.path.join(folder, f'{s}_{name}.png'))
+        metrics.save_ci_width_map(summary['lower'][k], summary['upper'][k], os.path.join(folder, f'ci_width_map_{s}.png'))
     if summary['mean'] is None:
         sampler._save_png(one_sample, os.path.join(folder, f'{s}_mean.png'))
         return
@@ -379,12 +408,13 @@ def main(argv=None):
         out = run_with_oom_backoff(opt, lambda: sampler.hmc(x, n, b, seq, seq_next, algo, opt, y_0, op, x_chain))
         samples = out[None] if n == 1 else out                              # [n, 20, C, H, W]
         summary = metrics.summarize(samples.contiguous(), x_orig, replicas=K, rhat_threshold=opt.rhat_threshold,
-                                    calibration=opt.calibration)
+                                    calibration=opt.calibration, credible=opt.credible)
         rows += _metric_rows(batch, summary)
         if opt.save_images and samples.shape[1]:
             for k, s in enumerate(batch):
                 _save_report_images(summary, k, s, samples[k * K, 0], opt.image_folder)
-    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out, K, opt.rhat_threshold, opt.calibration)
+    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out, K, opt.rhat_threshold, opt.calibration,
+                   opt.credible)
 
 
 def main_latent(argv=None):
@@ -424,11 +454,13 @@ def main_latent(argv=None):
             imgs = model.decode_first_stage(lat) if s_c else x_orig.new_empty((0,) + tuple(x_orig.shape[1:]))
             imgs = imgs.reshape((K, s_c) + tuple(imgs.shape[1:])).contiguous()
             summary = metrics.summarize(imgs if K > 1 else imgs[0], x_orig[k:k + 1], replicas=K,
-                                        rhat_threshold=opt.rhat_threshold, calibration=opt.calibration)
+                                        rhat_threshold=opt.rhat_threshold, calibration=opt.calibration,
+                                        credible=opt.credible)
             rows += _metric_rows([s], summary)
             if opt.save_images and s_c:
                 _save_report_images(summary, 0, s, imgs[0, 0], opt.image_folder)
-    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out, K, opt.rhat_threshold, opt.calibration)
+    return _report(rows, images.shape[0], rank, world, device, opt.metrics_out, K, opt.rhat_threshold, opt.calibration,
+                   opt.credible)
 
 
 if __name__ == '__main__':

@@ -1230,7 +1230,28 @@ def calibration(samples, x_orig, n_replicas=1):
     return z, counts, hist, summary
 
 
-# ---- a1 -------------------------------------------------------------------------------------
+def credible(samples, x_orig, n_replicas=1, k=1):
+    """Order statistics of an image's pooled draws (nhmc.h "Credible interval and median of the posterior samples").
+    samples [G * n_replicas, S, C, H, W], chain g * n_replicas + r being replica r of image g, x_orig [G, C, H, W] or None,
+    1 <= k <= n // 2 with n = n_replicas * S -> (lower, median, upper [G, C, H, W] float32: d_(k), the median and
+    d_(n+1-k) of the n draws in torch.sort's order, summary [G, 6] float64)."""
+    lib = _lib.load()
+    B, S, Cc, H, W = _sample_block(samples)
+    K = int(n_replicas)
+    if K < 1 or B % K:
+        raise _lib.NhmcError(f'credible: {B} chains are not a multiple of {n_replicas} replicas')
+    G, N, dev = B // K, Cc * H * W, samples.device
+    if x_orig is not None and (x_orig.dim() != 4 or x_orig.shape[0] != G or x_orig.shape[1:] != samples.shape[2:]):
+        raise _lib.NhmcError(f'x_orig {tuple(x_orig.shape)} does not match {G} images of samples {tuple(samples.shape)}')
+    lower, median, upper = (torch.empty((G, Cc, H, W), dtype=torch.float32, device=dev) for _ in range(3))
+    summary = torch.empty((G, 6), dtype=torch.float64, device=dev)
+    ws = torch.empty(lib.nhmc_credible_ws_bytes(G, N) // 8, dtype=torch.float64, device=dev)
+    _lib.check(lib.nhmc_credible(_p(samples, torch.float32, 'samples'), _p(x_orig, torch.float32, 'x_orig'), _p(lower),
+                                 _p(median), _p(upper), _p(summary), _p(ws), G, K, S, N, int(k), _stream()), 'nhmc_credible')
+    return lower, median, upper, summary
+
+
+# ---- a1-------------------------------------------------------------------------------------
 def randn_philox(shape, seed, chain_id0, draw, scale=1.0, device='cuda', out=None):
     lib = _lib.load()
     if out is None:

@@ -11,6 +11,9 @@ on the device.
     calibration(samples, x_orig)     rank and z-score of the original among an image's pooled draws: coverage of the
                                      central interval, spread / skill, |error| ~ std correlation, PSNR of the mean
     save_calibration_map(z, path)    the `calibration_map_{idx}.png` picture
+    credible(samples, x_orig)        the interval calibration speaks of, as maps: the order statistics d_(k) and d_(n+1-k)
+                                     of an image's pooled draws and their median, per element, with summaries
+    save_ci_width_map(lower, upper, path)   the `ci_width_map_{idx}.png` picture
 
 With K replica chains per image (not in the reference, which runs one chain) the block is [G * K, S, C, H, W], chain
 g * K + r being replica r of image g, and `summarize(..., replicas=K)` pools an image's K * S samples.
@@ -163,7 +166,49 @@ def _no_calibration(G):
     return dict(z=None, below=None, equal=None, hist=None, **{k: np.full(G, np.nan) for k in CALIBRATION_KEYS})
 
 
-def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1, calibration=None):
+CREDIBLE_KEYS = ('ci_rank', 'ci_level', 'ci_width_mean', 'ci_width_max', 'psnr_of_median', 'ci_inside', 'n_point', 'n_nan')
+CREDIBLE_SUMS = ('sum_width', 'max_width', 'sum_err2_median', 'n_inside', 'n_point', 'n_nan')
+
+
+def credible_from_sums(sums, n, k, n_elem):
+    """The reported figures from the kernel's summary, in float64 on the host.  sums [G, 6] in the order CREDIBLE_SUMS
+    (include/nhmc.h), n pooled draws, k the interval's rank, n_elem = C * H * W = E -> dict of CREDIBLE_KEYS, float64 [G]:
+        ci_rank           k: the interval is [d_(k), d_(n+1-k)]
+        ci_level          (n + 1 - 2k) / (n + 1), the same number as `coverage_nominal`
+        ci_width_mean     sum_width / (2 E), ci_width_max = max_width / 2: on the [0, 1] image scale, the inverse data
+                          transform halves a difference
+        psnr_of_median    10 log10(4 E / sum_err2_median), the convention of `psnr_of_mean`
+        ci_inside         n_inside / E: the share of the elements whose original lies in the interval, ties included
+        n_point, n_nan    the two counts: elements whose interval is a point, elements whose upper bound is NaN
+    A ratio over nothing is NaN (or inf), never an error."""
+    sums = np.asarray(sums, dtype=np.float64)
+    width, wmax, err2, inside, point, nan = (sums[..., i] for i in range(6))
+    E = float(n_elem)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return dict(ci_rank=np.full(width.shape, float(k)), ci_level=np.full(width.shape, (n + 1 - 2 * k) / (n + 1.0)),
+                    ci_width_mean=width / (2.0 * E), ci_width_max=wmax / 2.0,
+                    psnr_of_median=10.0 * np.log10(4.0 * E / err2), ci_inside=inside / E, n_point=point.copy(),
+                    n_nan=nan.copy())
+
+
+def credible(samples, x_orig=None, replicas=1, level=0.9):
+    """The central credible interval and the median of an image's pooled draws, per element (the definition is in
+    include/nhmc.h).  samples [G * K, S, C, H, W] with 2 <= K * S <= 1024, x_orig [G, C, H, W] or None -> dict: the device
+    maps `lower`, `median`, `upper` (float32 [G, C, H, W]: d_(k), the median and d_(n+1-k) of the n = K * S draws, with
+    k = coverage_rank(n, level): the interval whose coverage `calibration` reports at the same level) and CREDIBLE_KEYS as
+    float64 numpy [G], with one device->host read.  Without x_orig, psnr_of_median and ci_inside are NaN."""
+    samples, x_orig, _ = _block(samples, x_orig)
+    n = int(replicas) * samples.shape[1]
+    k = coverage_rank(n, level)
+    lower, median, upper, sums = K.credible(samples, x_orig, replicas, k)
+    return dict(lower=lower, median=median, upper=upper, **credible_from_sums(sums.cpu().numpy(), n, k, lower[0].numel()))
+
+
+def _no_credible(G):
+    return dict(lower=None, median=None, upper=None, **{k: np.full(G, np.nan) for k in CREDIBLE_KEYS})
+
+
+def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1, calibration=None, credible=None):
     """Everything the report prints or saves for B chains with S samples each, with one device->host read.
 
     -> dict of float64 numpy arrays [B]: psnr_mean, psnr_std, ssim_mean, ssim_std (np.mean / np.std(ddof=1) over the
@@ -179,9 +224,13 @@ def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1, calibration=None)
 
     calibration = level (0.9, say; None, the default, changes nothing): the dict gains what `calibration` returns for the
     pooled K * S samples -- `z`, `below`, `equal`, `hist` and CALIBRATION_KEYS -- in the same single read.  With fewer
-    than two pooled samples the four are None and the figures NaN."""
+    than two pooled samples the four are None and the figures NaN.
+
+    credible = level (None, the default, changes nothing): the dict gains, after everything else, what `credible` returns
+    for the pooled K * S samples -- `lower`, `median`, `upper` and CREDIBLE_KEYS -- in the same single read.  With fewer
+    than two pooled samples the three maps are None and the figures NaN."""
     replicas = int(replicas)
-    if replicas == 1 and calibration is None:
+    if replicas == 1 and calibration is None and credible is None:
         return _summarize(samples, x_orig)
     samples, x_orig, _ = _block(samples, x_orig)
     B, S = samples.shape[:2]
@@ -190,7 +239,11 @@ def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1, calibration=None)
     G = B // replicas
     diag = K.chain_diag(samples, replicas, rhat_threshold) if replicas > 1 and S >= 4 else None
     cal = K.calibration(samples, x_orig, replicas) if calibration is not None and replicas * S >= 2 else None
-    extra = ([] if diag is None else [diag[2]]) + ([] if cal is None else [cal[3], cal[2].double()])
+    n = replicas * S
+    rank = coverage_rank(n, credible) if credible is not None and n >= 2 else None
+    cred = None if rank is None else K.credible(samples, x_orig, replicas, rank)
+    extra = ([] if diag is None else [diag[2]]) + ([] if cal is None else [cal[3], cal[2].double()]) + \
+        ([] if cred is None else [cred[3]])
     out = _summarize(samples.reshape((G, replicas * S) + tuple(samples.shape[2:])), x_orig,
                      extra=torch.cat(extra, dim=1) if extra else None)
     host = out.pop('extra', None)
@@ -199,9 +252,15 @@ def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1, calibration=None)
         out['rhat'], out['ess'] = (None, None) if diag is None else diag[:2]
         for i, k in enumerate(CONVERGENCE_KEYS):
             out[k] = np.full(G, np.nan) if diag is None else host[:, i].copy()
+    at = 0 if diag is None else len(CONVERGENCE_KEYS)
     if calibration is not None:
         out.update(_no_calibration(G) if cal is None else _calibration_result(
-            cal[0], cal[1], host[:, 0 if diag is None else len(CONVERGENCE_KEYS):], cal[0][0].numel(), calibration))
+            cal[0], cal[1], host[:, at:at + len(CALIBRATION_SUMS) + n + 1], cal[0][0].numel(), calibration))
+    if credible is not None:
+        at += 0 if cal is None else len(CALIBRATION_SUMS) + n + 1
+        out.update(_no_credible(G) if cred is None else dict(
+            lower=cred[0], median=cred[1], upper=cred[2],
+            **credible_from_sums(host[:, at:at + len(CREDIBLE_SUMS)], n, rank, cred[0][0].numel())))
     return out
 
 
@@ -287,3 +346,18 @@ def save_calibration_map(z, path):
         a = a.max(axis=0)
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
     Image.fromarray(hot_colours(np.clip(a / 3.0, 0.0, 1.0))).save(path)
+
+
+def save_ci_width_map(lower, upper, path):
+    """The width of one image's credible interval, `upper - lower` [C, H, W] (or [H, W]), as an 8-bit PNG in the `hot`
+    colours: the mean over the channels, min-max normalised -- the std map's picture (`save_std_map`) of the interval, so
+    that the two can be laid side by side.  A map that is flat, or holds a NaN width, has no range and comes out black."""
+    from PIL import Image
+    width = (upper - lower).float()
+    if width.dim() == 3:
+        width = width.mean(dim=0)
+    width = width[None].contiguous()
+    minmax = torch.stack([width.min(), width.max()])[None].contiguous()
+    map01 = np.nan_to_num(K.std_map_normalise(width, minmax)[0].cpu().numpy(), nan=0.0, posinf=1.0, neginf=0.0)
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    Image.fromarray(hot_colours(map01)).save(path)
