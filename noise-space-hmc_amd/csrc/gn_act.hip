@@ -13,9 +13,17 @@
 //   u = ((x - mean_g) rstd_g gamma_c + beta_c) (1 + scale_bc) + shift_bc ;   y = act ? u sigmoid(u) : u
 //   reference modules: guided_diffusion/nn.py GroupNorm32 + SiLU, unet_ffhq.py:310-321 (scale-shift norm);
 //   ldm/modules/diffusionmodules/model.py:38-39 (Normalize, eps 1e-6) + nonlinearity.
-// Statistics: fp64 sums of x and x^2 per (sample, group), split over `splits` blocks and reduced in a fixed order by
-// the consumer (deterministic, no atomics); var = E[x^2] - mean^2 in fp64.  Only the input gradient is produced: the
-// networks are frozen (requires_grad False) and the FiLM terms come from the time embedding, which does not depend on x.
+// Statistics: with v = x + pre formed in fp64, the sums of v and v^2 per (sample, group) are fp64 from the first
+// operation on -- per float4, per thread, per block -- split over `splits` blocks and reduced in a fixed order by the
+// consumer (deterministic, no atomics); var = E[v^2] - mean^2 in fp64.  That difference cancels |mean|^2 / var leading
+// digits, so nothing of it may be formed in fp32: a square rounded to fp32 is off by mean^2 2^-24, which is the whole
+// variance of a slab with |mean| / std = 4096 and 10 - 17 % of the output of a flat one (mean 3, std 1e-4); with fp64
+// sums the statistics are exact to r^2 2^-53, r = |mean| / std.  The forward's output keeps that: it is evaluated in
+// fp64 per element and rounded to fp32 once (nhmc_gn_out of nhmc_common.h), within 1 ulp of the float64 definition;
+// the backward centres x + pre - mean from the fp64 mean (gn_centre) and goes on in fp32.  Neither's distance from the
+// float64 definition grows with r (tests/test_gn_conditioning_gpu.py).  The backward's sums (dxh, dxh xh: no
+// cancellation) are fp32 inside a float4 and fp64 across.  Only the input gradient is produced: the networks are
+// frozen (requires_grad False) and the FiLM terms come from the time embedding, which does not depend on x.
 #include "nhmc_common.h"
 
 namespace {
@@ -34,6 +42,17 @@ struct GnArgs {
 
 __device__ __forceinline__ float gn_sigmoid(float u) { return 1.0f / (1.0f + expf(-u)); }
 
+// Centring: x + pre - mean is formed as (x + hi) + lo with hi + lo = pre - mean split from fp64, once per float4 (one
+// channel).  Neither x + pre nor mean is rounded to fp32 on its own -- each of those roundings is |mean| / std 2^-24
+// of the slab's std -- and where |mean| >> std the first addition is exact (the operands agree within a factor 2).
+struct GnCentre { float hi, lo; };
+__device__ __forceinline__ GnCentre gn_centre(float pb, double mean) {
+  const double c = (double)pb - mean;
+  GnCentre r;
+  r.hi = (float)c; r.lo = (float)(c - (double)r.hi);
+  return r;
+}
+
 // partial sums of one (sample, group): ws[(bg * splits + split) * NV + v]
 template <bool BWD>
 __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_stats(const float4* __restrict__ x, const float4* __restrict__ dy,
@@ -43,12 +62,13 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_stats(const float4* __restric
   const int b = bg / a.G, g = bg % a.G, cpg = a.C / a.G;
   const int64_t n4 = (int64_t)cpg * a.hw / 4, base = (int64_t)bg * n4;
   const int64_t per = (n4 + a.splits - 1) / a.splits, lo = (int64_t)split * per, hi = min(n4, lo + per);
-  float mean = 0.f, rstd = 0.f;
+  double mean = 0.0;
+  float rstd = 0.f;
   if (BWD) {
     double s = 0.0, ss = 0.0;
     for (int k = 0; k < a.fwd_splits; ++k) { s += fwd_ws[((int64_t)bg * a.fwd_splits + k) * 2]; ss += fwd_ws[((int64_t)bg * a.fwd_splits + k) * 2 + 1]; }
     const double n = (double)cpg * (double)a.hw, m = s / n;
-    mean = (float)m;
+    mean = m;
     rstd = (float)(1.0 / sqrt(fmax(ss / n - m * m, 0.0) + (double)a.eps));
   }
   double s0 = 0.0, s1 = 0.0;
@@ -58,19 +78,22 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_stats(const float4* __restric
     const int ch = g * cpg + (int)((q * 4) / a.hw);
     const float pb = a.pre ? a.pre[(int64_t)b * a.pre_stride + ch] : 0.0f;
     if (!BWD) {
-      float t0 = 0.f, t1 = 0.f;
+      // every element widened before pre is added and before it is squared (one rounding per fma): what E[v^2] - mean^2
+      // cancels is the rounding of fp64 sums, not mean^2 2^-24 per square (a slab with |mean| >> std would lose its variance)
+      double t0 = 0.0, t1 = 0.0;
 #pragma unroll
-      for (int c = 0; c < 4; ++c) { const float v = xe[c] + pb; t0 += v; t1 += v * v; }
-      s0 += (double)t0; s1 += (double)t1;
+      for (int c = 0; c < 4; ++c) { const double v = (double)xe[c] + (double)pb; t0 += v; t1 = fma(v, v, t1); }
+      s0 += t0; s1 += t1;
     } else {
       const float4 dv = dy[base + q];
       const float* de = reinterpret_cast<const float*>(&dv);
       float ga = a.gamma[ch], be = a.beta[ch];
       if (a.film) { const float sc = 1.0f + a.film[(int64_t)b * a.film_stride + ch]; ga *= sc; be = be * sc + a.film[(int64_t)b * a.film_stride + a.C + ch]; }
+      const GnCentre ce = gn_centre(pb, mean);
       float t0 = 0.f, t1 = 0.f;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const float xh = ((xe[c] + pb) - mean) * rstd;
+        const float xh = ((xe[c] + ce.hi) + ce.lo) * rstd;
         float du = de[c];
         if (a.act) { const float u = xh * ga + be, sg = gn_sigmoid(u); du = du * (sg * (1.0f + u * (1.0f - sg))); }
         const float dxh = du * ga;
@@ -95,6 +118,7 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_apply(const float4* __restric
   const int b = bg / a.G, g = bg % a.G, cpg = a.C / a.G;
   const int64_t n4 = (int64_t)cpg * a.hw / 4, base = (int64_t)bg * n4;
   __shared__ float st[4];
+  __shared__ double st_mean, st_rstd;
   if (threadIdx.x == 0) {
     double s = 0.0, ss = 0.0, d0 = 0.0, d1 = 0.0;
     for (int k = 0; k < a.fwd_splits; ++k) { s += fwd_ws[((int64_t)bg * a.fwd_splits + k) * 2]; ss += fwd_ws[((int64_t)bg * a.fwd_splits + k) * 2 + 1]; }
@@ -102,13 +126,15 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_apply(const float4* __restric
       for (int k = 0; k < a.splits; ++k) { d0 += bwd_ws[((int64_t)bg * a.splits + k) * 2]; d1 += bwd_ws[((int64_t)bg * a.splits + k) * 2 + 1]; }
     }
     const double n = (double)cpg * (double)a.hw, m = s / n;
-    st[0] = (float)m;
-    st[1] = (float)(1.0 / sqrt(fmax(ss / n - m * m, 0.0) + (double)a.eps));
+    st_mean = m;
+    st_rstd = 1.0 / sqrt(fmax(ss / n - m * m, 0.0) + (double)a.eps);
+    st[1] = (float)st_rstd;
     st[2] = (float)(d0 / n);
     st[3] = (float)(d1 / n);
   }
   __syncthreads();
-  const float mean = st[0], rstd = st[1], m0 = st[2], m1 = st[3];
+  const double mean = st_mean;
+  const float rstd = st[1], m0 = st[2], m1 = st[3];
   const int64_t t0 = (int64_t)blockIdx.x * (NHMC_BLOCK * 2) + threadIdx.x;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -118,22 +144,22 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_apply(const float4* __restric
     const float* xe = reinterpret_cast<const float*>(&xv);
     const int ch = g * cpg + (int)((q * 4) / a.hw);
     const float pb = a.pre ? a.pre[(int64_t)b * a.pre_stride + ch] : 0.0f;
-    float ga = a.gamma[ch], be = a.beta[ch];
-    if (a.film) { const float sc = 1.0f + a.film[(int64_t)b * a.film_stride + ch]; ga *= sc; be = be * sc + a.film[(int64_t)b * a.film_stride + a.C + ch]; }
     float4 o;
     float* oe = reinterpret_cast<float*>(&o);
     if (!BWD) {
+      // the output in fp64 per element, rounded once (nhmc_gn_out, shared with gn_onepass.hip)
+      const NhmcGnOut k = nhmc_gn_out_terms(nhmc_gn_affine(a.gamma, a.beta, a.film, a.film_stride, a.C, b, ch), pb, mean, st_rstd);
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float u = (((xe[c] + pb) - mean) * rstd) * ga + be;
-        oe[c] = a.act ? u * gn_sigmoid(u) : u;
-      }
+      for (int c = 0; c < 4; ++c) oe[c] = nhmc_gn_out(k, xe[c], a.act);
     } else {
+      const GnCentre ce = gn_centre(pb, mean);
+      float ga = a.gamma[ch], be = a.beta[ch];
+      if (a.film) { const float sc = 1.0f + a.film[(int64_t)b * a.film_stride + ch]; ga *= sc; be = be * sc + a.film[(int64_t)b * a.film_stride + a.C + ch]; }
       const float4 dv = dy[base + q];
       const float* de = reinterpret_cast<const float*>(&dv);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const float xh = ((xe[c] + pb) - mean) * rstd;
+        const float xh = ((xe[c] + ce.hi) + ce.lo) * rstd;
         float du = de[c];
         if (a.act) { const float u = xh * ga + be, sg = gn_sigmoid(u); du = du * (sg * (1.0f + u * (1.0f - sg))); }
         oe[c] = rstd * ((du * ga - m0) - xh * m1);

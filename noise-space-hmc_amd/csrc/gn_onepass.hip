@@ -12,6 +12,11 @@
 //     backward  k_gn_onepass<true>  (R x, dy [, acc], W dx)                     2 (3) reads + 1 write
 // The formulas, the fp64 partial sums, their fixed summation order k = 0 .. splits - 1 and the workspace layout
 // ws[(bg * splits + split) * 2 ..] are those of gn_act.hip, so a forward workspace of either path feeds either backward.
+// As there, the forward's sums of v = x + pre and v^2 are fp64 from the element on (widened, added and squared per
+// float4, per thread, per workgroup in fp64): var = E[v^2] - mean^2 cancels and tolerates no square rounded to fp32;
+// the forward's output is evaluated in fp64 per element and rounded once (nhmc_gn_out of nhmc_common.h, the one
+// definition both files call); the backward centres x + pre - mean from the fp64 mean (op_centre) and goes on in fp32.
+// The backward's sums are fp32 inside a float4, fp64 across.
 //
 // The wait protocol (agent scope, placement independent; "the data is the flag").  The entry point fills the workspace
 // with the byte 0xFF by a small launch of its own (k_gn_ws_fill) on the same stream ahead of every launch; no partial sum can have
@@ -86,11 +91,12 @@ __device__ __forceinline__ void op_block_sum(double (&v)[2], double* lds) {
 }
 
 constexpr int OP_CHAN_LDS = 64;                  // channels per group whose terms are staged in LDS
-struct OpChan { float pb, ga, be; };
+struct OpChan { float pb, ga, be, hi, lo; };       // hi + lo = pb - mean (op_centre), where the mean is known
 // tab (nullable): the terms of the group's channels in LDS, 3 floats each, first channel ch0
 template <bool AFFINE>
 __device__ __forceinline__ OpChan op_chan(const OpArgs& a, int b, int ch, const float* tab = nullptr, int ch0 = 0) {
   OpChan c;
+  c.hi = c.lo = 0.0f;
   if (tab) { const float* t = tab + 3 * (ch - ch0); c.pb = t[0]; c.ga = t[1]; c.be = t[2]; return c; }
   c.pb = a.pre ? a.pre[(int64_t)b * a.pre_stride + ch] : 0.0f;
   c.ga = c.be = 0.0f;
@@ -101,44 +107,54 @@ __device__ __forceinline__ OpChan op_chan(const OpArgs& a, int b, int ch, const 
   return c;
 }
 
-// One element's contribution to the partial sums of its share, and one element of the output: the one place where each
-// is formed (the register path calls them four times per float4, the fallback element by element).
+// x + pre - mean is (x + hi) + lo, hi + lo split from fp64 once per float4: gn_centre of gn_act.hip
+__device__ __forceinline__ OpChan op_centre(OpChan c, double mean) {
+  const double d = (double)c.pb - mean;
+  c.hi = (float)d; c.lo = (float)(d - (double)c.hi);
+  return c;
+}
+
+// One element's contribution to the partial sums of its share, and one element of the backward's output: the one place
+// where each is formed (the register path calls them four times per float4, the fallback element by element).
+// OpAcc: what the four elements of a float4 are added up in before the sum joins the fp64 partial.  Forward: fp64, as
+// in gn_act.hip -- v = x + pre and v^2 never exist rounded to fp32, or E[v^2] - mean^2 would cancel against
+// mean^2 2^-24 per square.  Backward: fp32; its two sums do not cancel.
+template <bool BWD> struct OpAccT { using type = double; };
+template <> struct OpAccT<true> { using type = float; };
+template <bool BWD> using OpAcc = typename OpAccT<BWD>::type;
+
 template <bool BWD>
-__device__ __forceinline__ void op_stat1(const OpArgs& a, const OpChan& c, float x, float d, float mean, float rstd, float& t0,
-                                         float& t1) {
-  if (!BWD) {
-    const float v = x + c.pb;
-    t0 += v; t1 += v * v;
+__device__ __forceinline__ void op_stat1(const OpArgs& a, const OpChan& c, float x, float d, float rstd,
+                                         OpAcc<BWD>& t0, OpAcc<BWD>& t1) {
+  if constexpr (!BWD) {
+    const double v = (double)x + (double)c.pb;
+    t0 += v; t1 = fma(v, v, t1);
   } else {
-    const float xh = ((x + c.pb) - mean) * rstd;
+    const float xh = ((x + c.hi) + c.lo) * rstd;
     float du = d;
     if (a.act) { const float u = xh * c.ga + c.be, sg = op_sigmoid(u); du = du * (sg * (1.0f + u * (1.0f - sg))); }
     const float dxh = du * c.ga;
     t0 += dxh; t1 += dxh * xh;
   }
 }
-template <bool BWD>
-__device__ __forceinline__ float op_apply1(const OpArgs& a, const OpChan& c, float x, float d, float mean, float rstd, float m0,
-                                           float m1) {
-  if (!BWD) {
-    const float u = (((x + c.pb) - mean) * rstd) * c.ga + c.be;
-    return a.act ? u * op_sigmoid(u) : u;
-  }
-  const float xh = ((x + c.pb) - mean) * rstd;
+// (the backward's element; the forward's is nhmc_gn_out of nhmc_common.h, shared with gn_act.hip)
+__device__ __forceinline__ float op_apply1(const OpArgs& a, const OpChan& c, float x, float d, float rstd, float m0, float m1) {
+  const float xh = ((x + c.hi) + c.lo) * rstd;
   float du = d;
   if (a.act) { const float u = xh * c.ga + c.be, sg = op_sigmoid(u); du = du * (sg * (1.0f + u * (1.0f - sg))); }
   return rstd * ((du * c.ga - m0) - xh * m1);
 }
 
 template <bool BWD>
-__device__ __forceinline__ void op_stat(const OpArgs& a, int b, int ch, const float4& xv, const float4& dv, float mean, float rstd,
+__device__ __forceinline__ void op_stat(const OpArgs& a, int b, int ch, const float4& xv, const float4& dv, double mean, float rstd,
                                         double& s0, double& s1, const float* tab, int ch0) {
   const float* xe = reinterpret_cast<const float*>(&xv);
   const float* de = reinterpret_cast<const float*>(&dv);
-  const OpChan c = op_chan<BWD>(a, b, ch, tab, ch0);
-  float t0 = 0.f, t1 = 0.f;
+  OpChan c = op_chan<BWD>(a, b, ch, tab, ch0);
+  if (BWD) c = op_centre(c, mean);
+  OpAcc<BWD> t0 = 0, t1 = 0;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) op_stat1<BWD>(a, c, xe[e], de[e], mean, rstd, t0, t1);
+  for (int e = 0; e < 4; ++e) op_stat1<BWD>(a, c, xe[e], de[e], rstd, t0, t1);
   s0 += (double)t0; s1 += (double)t1;
 }
 
@@ -160,16 +176,24 @@ __device__ __forceinline__ T* op_side(const OpArgs& a, T* p1, T* p2, int b, int6
 // normalise (forward) / differentiate (backward) one float4 held in registers and write it
 template <bool BWD>
 __device__ __forceinline__ void op_apply(const OpArgs& a, int b, int64_t base, int q, const OpAt& at, const float4& xv,
-                                         const float4& dv, float mean, float rstd, float m0, float m1, float4* __restrict__ out1,
-                                         float4* __restrict__ out2, float4* __restrict__ xcat, const float4* __restrict__ acc,
-                                         const float* tab, int ch0) {
-  const OpChan c = op_chan<true>(a, b, at.ch, tab, ch0);
+                                         const float4& dv, double mean, float rstd, double rstd64, float m0, float m1,
+                                         float4* __restrict__ out1, float4* __restrict__ out2, float4* __restrict__ xcat,
+                                         const float4* __restrict__ acc, const float* tab, const NhmcGnAffine* tab64, int ch0) {
   const float* xe = reinterpret_cast<const float*>(&xv);
   const float* de = reinterpret_cast<const float*>(&dv);
   float4 o;
   float* oe = reinterpret_cast<float*>(&o);
+  if constexpr (!BWD) {
+    // the output in fp64 per element, rounded once: the arithmetic of gn_act.hip's forward, the same bits
+    const NhmcGnAffine f = tab64 ? tab64[at.ch - ch0] : nhmc_gn_affine(a.gamma, a.beta, a.film, a.film_stride, a.C, b, at.ch);
+    const NhmcGnOut k = nhmc_gn_out_terms(f, op_chan<false>(a, b, at.ch, tab, ch0).pb, mean, rstd64);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) oe[e] = op_apply1<BWD>(a, c, xe[e], de[e], mean, rstd, m0, m1);
+    for (int e = 0; e < 4; ++e) oe[e] = nhmc_gn_out(k, xe[e], a.act);
+  } else {
+    const OpChan c = op_centre(op_chan<true>(a, b, at.ch, tab, ch0), mean);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) oe[e] = op_apply1(a, c, xe[e], de[e], rstd, m0, m1);
+  }
   if (!BWD) {
     out1[base + q] = o;
     if (xcat) xcat[base + q] = xv;
@@ -182,13 +206,14 @@ __device__ __forceinline__ void op_apply(const OpArgs& a, int b, int64_t base, i
   }
 }
 
-// thread 0: the slab's totals -> st[0..1] = mean, rstd (forward) / st[2..3] = the two means of the backward
+// thread 0: the slab's totals -> st64[0..1] = mean, rstd (fp64), st[1] = rstd (forward) / st[2..3] = the two means of the backward
 template <bool BWD>
-__device__ __forceinline__ void op_totals(const OpArgs& a, double n, double t0, double t1, float* st) {
+__device__ __forceinline__ void op_totals(const OpArgs& a, double n, double t0, double t1, float* st, double* st64) {
   if (!BWD) {
     const double m = t0 / n;
-    st[0] = (float)m;
-    st[1] = (float)(1.0 / sqrt(fmax(t1 / n - m * m, 0.0) + (double)a.eps));
+    st64[0] = m;
+    st64[1] = 1.0 / sqrt(fmax(t1 / n - m * m, 0.0) + (double)a.eps);
+    st[1] = (float)st64[1];
   } else {
     st[2] = (float)(t0 / n);
     st[3] = (float)(t1 / n);
@@ -209,16 +234,21 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_onepass(const float4* __restr
   const double n = (double)(a.C / a.G) * (double)a.hw4 * 4.0;
   __shared__ double red[8];
   __shared__ float st[4];
+  __shared__ double st64[2];
   __shared__ int arrived;
   __shared__ double part[2 * OP_MAX_SPLITS];        // the partials of a slab, one lane loads one
   __shared__ float chan[3 * OP_CHAN_LDS];
+  __shared__ NhmcGnAffine chan64[BWD ? 1 : OP_CHAN_LDS];   // forward: the affine terms in fp64, for its output
   const int cpg = a.C / a.G, ch0 = g * cpg;
   const float* tab = cpg <= OP_CHAN_LDS ? chan : nullptr;
+  const NhmcGnAffine* tab64 = !BWD && tab ? chan64 : nullptr;
   if (tab && tid < cpg) {
     const OpChan c = op_chan<true>(a, b, ch0 + tid);
     chan[3 * tid] = c.pb; chan[3 * tid + 1] = c.ga; chan[3 * tid + 2] = c.be;
+    if (!BWD) chan64[tid] = nhmc_gn_affine(a.gamma, a.beta, a.film, a.film_stride, a.C, b, ch0 + tid);
   }
-  float mean = 0.f, rstd = 0.f;
+  double mean = 0.0;
+  float rstd = 0.f;
   if (BWD) {
     // the forward's partials: one lane each (a serial chain of dependent loads costs more than the share itself), then
     // thread 0 adds them in the order k = 0 .. fwd_splits - 1
@@ -228,10 +258,10 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_onepass(const float4* __restr
       double s = 0.0, ss = 0.0;
 #pragma unroll 2
       for (int k = 0; k < a.fwd_splits; ++k) { s += part[2 * k]; ss += part[2 * k + 1]; }
-      op_totals<false>(a, n, s, ss, st);
+      op_totals<false>(a, n, s, ss, st, st64);
     }
     __syncthreads();
-    mean = st[0]; rstd = st[1];
+    mean = st64[0]; rstd = st[1];
   }
 
   // ---- the share of this workgroup, once, into registers
@@ -298,12 +328,13 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_onepass(const float4* __restr
             const int q = k * OP_SHARE + i * NHMC_BLOCK + tid;
             if (q >= a.n4) continue;
             const OpAt at = op_at(a, g, q);
-            const OpChan c = op_chan<BWD>(a, b, at.ch, tab, ch0);
+            OpChan c = op_chan<BWD>(a, b, at.ch, tab, ch0);
+            if (BWD) c = op_centre(c, mean);
             const float* xs = reinterpret_cast<const float*>(op_side(a, x1, BWD ? nullptr : x2, b, base, q, at));
             const float* ds = reinterpret_cast<const float*>(dy + (base + q));
-            float u0 = 0.f, u1 = 0.f;
+            OpAcc<BWD> u0 = 0, u1 = 0;
 #pragma unroll 1
-            for (int e = 0; e < 4; ++e) op_stat1<BWD>(a, c, xs[e], BWD ? ds[e] : 0.0f, mean, rstd, u0, u1);
+            for (int e = 0; e < 4; ++e) op_stat1<BWD>(a, c, xs[e], BWD ? ds[e] : 0.0f, rstd, u0, u1);
             p[0] += (double)u0; p[1] += (double)u1;
           }
           op_block_sum(p, red);
@@ -313,13 +344,14 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_onepass(const float4* __restr
       }
     }
   }
-  if (tid == 0) op_totals<BWD>(a, n, t0, t1, st);
+  if (tid == 0) op_totals<BWD>(a, n, t0, t1, st, st64);
   if (!BWD && tid == 0 && split == 0) {            // the slab totals behind the partials: a one-split workspace
     double* tot = ws + ((int64_t)gridDim.y * a.splits + bg) * 2;
     tot[0] = t0; tot[1] = t1;
   }
   __syncthreads();
-  mean = st[0]; rstd = st[1];
+  mean = st64[0]; rstd = st[1];
+  const double rstd64 = st64[1];
   const float m0 = st[2], m1 = st[3];
 
   // ---- normalise / differentiate the share from registers
@@ -327,11 +359,12 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_onepass(const float4* __restr
   for (int i = 0; i < OP_K; ++i) {
     // the share fills 32 / 64 VGPRs: keep the scheduler from hoisting all eight `acc` loads on top of them, and from
     // carrying the plane index and channel terms of all eight float4 over from the statistics (q is opaque here, they
-    // are formed again): 71 instead of 87 VGPRs forward, 126 instead of 146 backward
+    // are formed again): 71 instead of 87 VGPRs forward (74 since the forward's sums and its output are fp64 per
+    // element), 126 instead of 146 backward
     if (i % 2 == 0) __builtin_amdgcn_sched_barrier(0);
     int q = split * OP_SHARE + i * NHMC_BLOCK + tid;
     asm volatile("" : "+v"(q));
-    if (q < a.n4) op_apply<BWD>(a, b, base, q, op_at(a, g, q), xv[i], dv[i], mean, rstd, m0, m1, out1, out2, xcat, acc, tab, ch0);
+    if (q < a.n4) op_apply<BWD>(a, b, base, q, op_at(a, g, q), xv[i], dv[i], mean, rstd, rstd64, m0, m1, out1, out2, xcat, acc, tab, tab64, ch0);
   }
 }
 

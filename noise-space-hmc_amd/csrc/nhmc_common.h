@@ -100,6 +100,42 @@ __device__ __forceinline__ float nhmc_masked(float g, float mask) { return mask 
 // IEEE correctly rounded on gfx950 (no fast-math flag is set in build.py); tests/test_hygiene_gpu.py sweeps all 1001
 // alpha-bar table entries through the kernels against numpy's correctly rounded root.
 
+// ---- the forward epilogue of the fused GroupNorm kernels (gn_act.hip, gn_onepass.hip): one definition, the same bits ----
+//   u = (x + pre - mean) rstd gamma (1 + scale) + beta (1 + scale) + shift ;   y = act ? u sigmoid(u) : u
+// evaluated in fp64 per element and rounded to fp32 once, so an output element is within 1 ulp of the float64
+// definition whatever the slab's mean / std is: a chain of fp32 roundings (centring, rstd, FiLM, exp, 1 + e, the
+// division, the product) is 3 ulp off on some elements, which a slab of 8 elements does not average out
+// (tests/test_gn_conditioning_gpu.py).  The kernels are bandwidth bound and gfx950 issues fp64 FMAs at half the fp32 rate.
+struct NhmcGnAffine { double ga, be; };           // gamma (1 + scale), beta (1 + scale) + shift of one (sample, channel)
+struct NhmcGnOut { double c, a, b; };             // u = (x + c) a + b
+__device__ __forceinline__ NhmcGnAffine nhmc_gn_affine(const float* gamma, const float* beta, const float* film,
+                                                       int64_t film_stride, int C, int b, int ch) {
+  NhmcGnAffine f{(double)gamma[ch], (double)beta[ch]};
+  if (film) {
+    const double sc = 1.0 + (double)film[(int64_t)b * film_stride + ch];
+    f.ga = f.ga * sc; f.be = fma(f.be, sc, (double)film[(int64_t)b * film_stride + C + ch]);
+  }
+  return f;
+}
+__device__ __forceinline__ NhmcGnOut nhmc_gn_out_terms(const NhmcGnAffine& f, float pb, double mean, double rstd) {
+  return NhmcGnOut{(double)pb - mean, rstd * f.ga, f.be};
+}
+// SiLU: exp(-u) is expf at u rounded to fp32 (<= 1 ulp, which 1 / (1 + e) damps to u s (1 - s) 2^-23 <= 0.23 2^-23 of
+// the output) times exp(fl(u) - u) = 1 + (fl(u) - u); the reciprocal is the fp32 approximation and one Newton step.
+// Below u = -80 the result is u 0 as in fp32, where exp(-u) overflows: -0 for a finite u (|u sigmoid(u)| < 2e-33 there),
+// NaN for -inf as torch's SiLU gives; the exponent is held at 80 so that no inf enters the Newton step.  A NaN stays
+// one; +inf gives +inf (tests/test_nonfinite_gpu.py::test_group_norm_silu_at_the_ends).
+__device__ __forceinline__ float nhmc_gn_out(const NhmcGnOut& k, float x, int act) {
+  const double u = fma((double)x + k.c, k.a, k.b);
+  if (!act) return (float)u;
+  const float uf = (float)u;
+  const double du = (uf - uf == 0.0f) ? (double)uf - u : 0.0;
+  const double e = (double)expf(fminf(-uf, 80.0f)) * (1.0 + du);
+  const double d = 1.0 + e;
+  const double s = (double)__builtin_amdgcn_rcpf((float)d);
+  return (float)(uf < -80.0f ? u * 0.0 : u * fma(s, fma(-d, s, 1.0), s));
+}
+
 // ---- the last DDIM step and its VJP: the one definition every fused "data term + last-step VJP" kernel calls ----------
 //   u   = (x - e*c1) / c2         x0 = clip(u)
 //   pre = c3*x0 + c4*e            xt_next = clip(pre)  (final_clip)

@@ -791,6 +791,41 @@ def test_group_norm(route, shape, nowait, name, kind, monkeypatch):
     assert not bool(torch.isfinite(want['dx'][1]).all())
 
 
+@pytest.mark.parametrize('route,shape,nowait', GN_ROUTES, ids=[r[0] for r in GN_ROUTES])
+def test_group_norm_silu_at_the_ends(route, shape, nowait, monkeypatch):
+    """The forward's SiLU where its argument leaves the range of exp, driven there by the FiLM shift of single channels
+    of sample 1 (the statistics do not see it): u = -1e4 and -1e30 give 0 as torch's fp32 SiLU does (exp(-u) overflows),
+    -inf gives NaN and +inf gives +inf as torch's do, +1e30 gives u; the other channels and samples keep their bits."""
+    groups, eps, C = 32, 1e-5, shape[1]
+    g_ = gen(29 + C)
+    gamma, beta = 1 + 0.2 * torch.randn(C, generator=g_), 0.1 * torch.randn(C, generator=g_)
+    fm, pb = 0.3 * torch.randn(B, 2 * C, generator=g_), 0.5 * torch.randn(B, C, generator=g_)
+    x = torch.randn(shape, generator=g_) * 1.7 + 0.3
+    ends = {5: -INF, 6: -1e4, 7: -1e30, 40: INF, 41: 1e30}               # channel of sample 1 -> its shift
+    fm_ends = fm.clone()
+    for ch, v in ends.items():
+        fm_ends[1, C + ch] = v
+    one = route != 'two_pass'
+    if one:
+        assert K.gn_onepass_splits(B, C, groups, shape[2] * shape[3]) > 1
+    else:
+        monkeypatch.setenv('NHMC_GN_ONEPASS', '0')
+    flags = K.GN_ONEPASS_NOWAIT if nowait else 0
+
+    def call(f):
+        return K.gn_act_fwd(dev(x), dev(gamma), dev(beta), groups, eps, True, dev(f), dev(pb), flags=flags, onepass=True if one else None)[0].cpu()
+    clean, got = call(fm), call(fm_ends)
+    want = gn_torch(x, gamma, beta, fm_ends, pb, groups, eps, True)
+    rest = torch.ones(B, C, dtype=torch.bool)
+    rest[1, list(ends)] = False
+    assert torch.equal(got[rest], clean[rest]) and bool(torch.isfinite(clean).all())
+    assert bool(torch.isnan(want[1, 5]).all()) and bool(torch.isnan(got[1, 5]).all())
+    for ch in (6, 7):
+        assert bool((want[1, ch] == 0).all()) and bool((got[1, ch] == 0).all()), (ch, got[1, ch].abs().max())
+    assert bool((want[1, 40] == INF).all()) and bool((got[1, 40] == INF).all())
+    assert float((got[1, 41] - want[1, 41]).abs().max()) <= 1e-6 * 1e30
+
+
 @pytest.mark.parametrize('kind', KINDS)
 @pytest.mark.parametrize('name', ['h', 'other'])
 def test_bias_add2(name, kind):
