@@ -761,6 +761,48 @@ int nhmc_credible(const float* samples, const float* x_orig, float* lower, float
                   double* ws, int n_groups, int n_replicas, int n_samples, int64_t n_elem, int k, nhmc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Principal components of the posterior samples, on the device: the Gram matrix of an image's pooled draws about the
+ * first one (the N x N covariance's eigenvectors follow from it on the host, nothing of size N x N is formed), and the
+ * projection that turns coefficients over the draws back into images.
+ *
+ *   samples : fp32 [n_groups * n_replicas][n_samples][n_elem], laid out and pooled as for nhmc_calibration: draw i of
+ *             group g is row g * n + i - 1 of the block, n = n_replicas * n_samples.
+ *   x_orig  : fp32 [n_groups][n_elem], or NULL.    gram : fp64 [n_groups][n][n].
+ *   ws      : double, nhmc_sample_gram_ws_bytes(n_groups, n, n_elem) bytes: one set of 16 x 16 partial tiles for each of
+ *             the nhmc_sample_gram_slabs(n_elem) slabs (1024 elements each) of every group.  The slab count is a function
+ *             of n_elem alone, never of the device.
+ *   Validation, before any launch: null pointer (x_orig excepted) / non-positive size -> ARG; samples, x_orig or gram not
+ *   16-byte aligned or n_elem % 4 != 0 -> ALIGN; n < 2, n > 256 or n_groups > 65535 -> SHAPE.
+ *
+ * Definition, per group, t being the original:
+ *   u_i = (double)d_{i+1} - (double)d_1   for i = 1 ... n - 1     the subtraction in fp64: the shift costs no fp32 rounding
+ *   u_n = (double)t - (double)d_1
+ *   gram[a][b] = sum over the n_elem elements of u_a u_b          a, b = 1 ... n (stored from 0); products and sums in fp64
+ *   The matrix is written exactly symmetric: [a][b] and [b][a] hold the same bits.  x_orig == NULL: row and column n - 1
+ *   are NaN.  A non-finite draw (NaN or +-inf) makes its own row and column NaN, a non-finite d_1 the whole matrix: it is
+ *   never turned into a number.  What one group holds never changes a bit of another group's matrix.
+ * Reductions: a workgroup owns one slab of one group, keeps its accumulators in registers over the whole slab and writes
+ *   one fp64 partial tile set to ws; a second kernel adds the slabs in ascending order.  No atomics: equal inputs give equal
+ *   bits.  The products run on the fp64 MFMA (16 x 16 x 4), so the order of the additions inside a slab is the hardware's.
+ * Every sample value and t leave HBM once: n * 4 + 4 bytes per element read.  On top of that the slabs' partial tiles
+ *   are written once and read once: nhmc_sample_gram_ws_bytes each way (189 MB at n = 160 and 8 groups of 3 x 256^2
+ *   elements, against the 1.0 GB block; 453 MB at n = 256).
+ *
+ * nhmc_sample_project:  coef : fp64 [n_groups][n_out][n], 1 <= n_out <= 8;  out : fp32 [n_groups][n_out][n_elem]
+ *   out[g][j][e] = fp32( sum_{i = 1 ... n} coef[g][j][i] ((double)d_i[e] - (double)d_1[e]) )
+ *   explicit fp64 fmas in ascending i from 0, rounded once to fp32.  Every sample value is read once.
+ *   Validation as above (samples, coef, out aligned); n_out outside 1 ... 8 -> SHAPE.  The kernel takes one element per
+ *   thread and needs neither the alignment nor n_elem % 4 == 0: both are asked for so that whatever nhmc_sample_gram
+ *   accepts this entry accepts, and nothing else.
+ * ---------------------------------------------------------------------------------- */
+int nhmc_sample_gram_slabs(int64_t n_elem);
+size_t nhmc_sample_gram_ws_bytes(int n_groups, int n, int64_t n_elem);
+int nhmc_sample_gram(const float* samples, const float* x_orig, double* gram, double* ws, int n_groups, int n_replicas,
+                     int n_samples, int64_t n_elem, nhmc_stream_t stream);
+int nhmc_sample_project(const float* samples, const double* coef, float* out, int n_groups, int n_replicas, int n_samples,
+                        int n_out, int64_t n_elem, nhmc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * a1  Momentum / accept noise: Philox4x32-10 keyed by seed, counted by
  *     (element quad, chain_id0 + chain, draw, tag) -- independent of how chains are sharded.
  *     Replaces torch.randn_like (main_sampling.py:692) and torch.rand(1) (:720).

@@ -123,6 +123,10 @@ SIGNATURES = {
     'nhmc_credible_tiles': (I, [I64]),
     'nhmc_credible_ws_bytes': (SZ, [I, I64]),
     'nhmc_credible': (I, [P, P, P, P, P, P, P, I, I, I, I64, I, P]),
+    'nhmc_sample_gram_slabs': (I, [I64]),
+    'nhmc_sample_gram_ws_bytes': (SZ, [I, I, I64]),
+    'nhmc_sample_gram': (I, [P, P, P, P, I, I, I, I64, P]),
+    'nhmc_sample_project': (I, [P, P, P, I, I, I, I, I64, P]),
     'nhmc_randn_philox': (I, [P, U64, U32, U32, F, I, I64, P]),
     'nhmc_copy_probe': (I, [P, P, I64, P]),
     'nhmc_uniform_philox': (I, [P, U64, U32, U32, I, P]),

@@ -33,6 +33,12 @@ in the JSON rows and, with `--save_images`, `calibration_map_{s}.png`.  Without 
 (nhmc.metrics.credible): the order statistics d_(k) and d_(n+1-k) of the image's pooled draws per element and their median --
 CREDIBLE_COLUMNS in the JSON rows, after the calibration columns, and, with `--save_images`, `{s}_median.png`,
 `{s}_lower.png`, `{s}_upper.png` and `ci_width_map_{s}.png`.  Without the flag nothing changes.
+
+`--pcs [COUNT]` (COUNT = 3 when bare, 1 ... 8) adds, per image, the principal components of its pooled samples
+(nhmc.metrics.pcs): how many there are, the share of the variance the first and the first COUNT carry, the effective rank,
+the share of the error that lies inside the samples' span and its RMS z-score along the components -- PCS_COLUMNS in the
+JSON rows, after all other columns, and, with `--save_images`, `{s}_pc{j}_plus.png` and `{s}_pc{j}_minus.png`: the posterior
+mean moved two standard deviations along component j.  Without the flag nothing changes.
 """
 import argparse
 import glob
@@ -98,6 +104,9 @@ def get_parser(latent=False):
     p.add_argument('--credible', type=float, nargs='?', const=0.9, default=None, metavar='LEVEL',
                    help='report the central credible interval nearest to LEVEL (0.9 when the flag is bare) and the median of '
                         "the samples per pixel: the interval's width, the share of the original inside it, PSNR of the median")
+    p.add_argument('--pcs', type=int, nargs='?', const=3, default=None, choices=range(1, 9), metavar='COUNT',
+                   help='report the first COUNT (3 when the flag is bare, 1 ... 8) principal components of the samples: their '
+                        'share of the variance, the effective rank, the share of the error inside their span and its z-score')
     return p
 
 
@@ -268,16 +277,18 @@ COLUMNS = ('image', 'psnr_mean', 'psnr_std', 'ssim_mean', 'ssim_std', 'std_map_m
 REPLICA_COLUMNS = ('replicas',) + metrics.CONVERGENCE_KEYS          # appended to COLUMNS with --replicas K > 1
 CALIBRATION_COLUMNS = metrics.CALIBRATION_KEYS                      # appended last with --calibration
 CREDIBLE_COLUMNS = metrics.CREDIBLE_KEYS                            # appended after those with --credible
-INT_COLUMNS = ('image', 'n_samples', 'replicas', 'n_constant', 'n_tied', 'n_flat', 'ci_rank', 'n_point', 'n_nan')
+PCS_COLUMNS = metrics.PCS_KEYS                                      # appended after all others with --pcs
+INT_COLUMNS = ('image', 'n_samples', 'replicas', 'n_constant', 'n_tied', 'n_flat', 'ci_rank', 'n_point', 'n_nan', 'pc_count',
+               'pc_rank')
 
 
 def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, rhat_threshold=1.1, calibration=None,
-            credible=None):
+            credible=None, pcs=None):
     """Gathers the per-image rows (COLUMNS, with K > 1 replicas + REPLICA_COLUMNS, with --calibration + CALIBRATION_COLUMNS,
-    with --credible + CREDIBLE_COLUMNS) over the ranks in global image order, prints the report on rank 0 and returns the
-    [n, 3] table (image, PSNR mean, PSNR std over its samples)."""
+    with --credible + CREDIBLE_COLUMNS, with --pcs + PCS_COLUMNS) over the ranks in global image order, prints the report on
+    rank 0 and returns the [n, 3] table (image, PSNR mean, PSNR std over its samples)."""
     columns = COLUMNS + (REPLICA_COLUMNS if replicas > 1 else ()) + (CALIBRATION_COLUMNS if calibration is not None else ()) + \
-        (CREDIBLE_COLUMNS if credible is not None else ())
+        (CREDIBLE_COLUMNS if credible is not None else ()) + (PCS_COLUMNS if pcs is not None else ())
     local = torch.tensor(rows, dtype=torch.float64, device=device).reshape(-1, len(columns))
     full = sharding.gather_chains(local, n_images, rank, world).cpu()
     table = full[:, :3].float()
@@ -305,6 +316,11 @@ def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, r
                       f'(level {c["ci_level"]:.4f}), width mean {c["ci_width_mean"]:.4f} max {c["ci_width_max"]:.4f}, '
                       f'original inside {c["ci_inside"]:.4f}, PSNR of the median {c["psnr_of_median"]:.3f}, '
                       f'point elements {int(c["n_point"])}')
+            if pcs is not None and c['pc_var_first'] == c['pc_var_first']:  # NaN: no component (n < 2, n > 256, no variance)
+                print(f'image {int(idx)}: principal components: {int(c["pc_count"])} of rank {int(c["pc_rank"])}, variance '
+                      f'share first {c["pc_var_first"]:.4f} top-{int(c["pc_count"])} {c["pc_var_top"]:.4f}, effective rank '
+                      f'{c["pc_eff_rank"]:.2f}, error inside the span {c["pc_err_in_span"]:.4f}, z rms along them '
+                      f'{c["pc_z_rms"]:.3f}')
         print(f'Total Average PSNR: {float(table[:, 1].nanmean()):.3f}  images: {table.shape[0]}')
         # main_sampling.py:560: the average over the images, and in parentheses the mean over the images of each
         # image's std over its samples
@@ -319,6 +335,11 @@ def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, r
             print(f'Total Average credible interval: level {avg["ci_level"]:.4f}, width mean {avg["ci_width_mean"]:.4f} '
                   f'max {avg["ci_width_max"]:.4f}, original inside {avg["ci_inside"]:.4f}, '
                   f'PSNR of the median {avg["psnr_of_median"]:.3f}')
+        if pcs is not None:
+            avg = {k: float(full[:, columns.index(k)].nanmean()) for k in PCS_COLUMNS}
+            print(f'Total Average principal components: variance share first {avg["pc_var_first"]:.4f} top-{pcs} '
+                  f'{avg["pc_var_top"]:.4f}, effective rank {avg["pc_eff_rank"]:.2f}, error inside the span '
+                  f'{avg["pc_err_in_span"]:.4f}, z rms along them {avg["pc_z_rms"]:.3f}')
         if metrics_out:
             import json
             as_json = lambda k, v: (int(v) if k in INT_COLUMNS and v == v else (v if v == v else None))
@@ -332,25 +353,32 @@ def _report(rows, n_images, rank, world, device, metrics_out=None, replicas=1, r
 def _metric_rows(batch, summary):
     """One COLUMNS row per image of `batch` from a `metrics.summarize` result (entry i of it for image i); a pooled
     summary (replicas > 1) appends REPLICA_COLUMNS, one with the calibration figures CALIBRATION_COLUMNS, one with the
-    credible interval's CREDIBLE_COLUMNS."""
+    credible interval's CREDIBLE_COLUMNS, one with the principal components' PCS_COLUMNS."""
     pooled = summary.get('replicas', 1) > 1
     return [[float(s)] + [float(summary[c][i]) for c in COLUMNS[1:-1]] + [float(summary['n_samples'])] +
             ([float(summary['replicas'])] + [float(summary[c][i]) for c in metrics.CONVERGENCE_KEYS] if pooled else []) +
             ([float(summary[c][i]) for c in CALIBRATION_COLUMNS] if 'coverage' in summary else []) +
-            ([float(summary[c][i]) for c in CREDIBLE_COLUMNS] if 'ci_level' in summary else [])
+            ([float(summary[c][i]) for c in CREDIBLE_COLUMNS] if 'ci_level' in summary else []) +
+            ([float(summary[c][i]) for c in PCS_COLUMNS] if 'pc_count' in summary else [])
             for i, s in enumerate(batch)]
 
 
 def _save_report_images(summary, k, s, one_sample, folder):
     """`{s}_mean.png` and, with two samples or more, `std_dev_map_{s}.png` (main_sampling.py:494-507); `rhat_map_{s}.png`
     and `calibration_map_{s}.png` where the summary holds those maps; with the credible interval's maps `{s}_median.png`,
-    `{s}_lower.png`, `{s}_upper.png` and `ci_width_map_{s}.png`."""
+    `{s}_lower.png`, `{s}_upper.png` and `ci_width_map_{s}.png`; with principal components `{s}_pc{j}_plus.png` and
+    `{s}_pc{j}_minus.png`, the mean moved by +-2 standard deviations along component j = 1 ... pc_count."""
     if summary.get('z') is not None:
         metrics.save_calibration_map(summary['z'][k], os.path.join(folder, f'calibration_map_{s}.png'))
     if summary.get('median') is not None:
         for name in ('median', 'lower', 'upper'):
             sampler._save_png(summary[name][k], os.path.join(folder, f'{s}_{name}.png'))
         metrics.save_ci_width_map(summary['lower'][k], summary['upper'][k], os.path.join(folder, f'ci_width_map_{s}.png'))
+    if summary.get('directions') is not None and summary['mean'] is not None and summary['pc_count'][k] == summary['pc_count'][k]:
+        for j in range(int(summary['pc_count'][k])):
+            step = 2.0 * summary['directions'][k, j]
+            sampler._save_png(summary['mean'][k] + step, os.path.join(folder, f'{s}_pc{j + 1}_plus.png'))
+            sampler._save_png(summary['mean'][k] - step, os.path.join(folder, f'{s}_pc{j + 1}_minus.png'))
     if summary['mean'] is None:
         sampler._save_png(one_sample, os.path.join(folder, f'{s}_mean.png'))
         return
@@ -408,13 +436,14 @@ def main(argv=None):
         out = run_with_oom_backoff(opt, lambda: sampler.hmc(x, n, b, seq, seq_next, algo, opt, y_0, op, x_chain))
         samples = out[None] if n == 1 else out                              # [n, 20, C, H, W]
         summary = metrics.summarize(samples.contiguous(), x_orig, replicas=K, rhat_threshold=opt.rhat_threshold,
-                                    calibration=opt.calibration, credible=opt.credible)
+                                    calibration=opt.calibration, credible=opt.credible,
+                                    pcs=opt.pcs)
         rows += _metric_rows(batch, summary)
         if opt.save_images and samples.shape[1]:
             for k, s in enumerate(batch):
                 _save_report_images(summary, k, s, samples[k * K, 0], opt.image_folder)
     return _report(rows, images.shape[0], rank, world, device, opt.metrics_out, K, opt.rhat_threshold, opt.calibration,
-                   opt.credible)
+                   opt.credible, opt.pcs)
 
 
 def main_latent(argv=None):
@@ -455,12 +484,12 @@ def main_latent(argv=None):
             imgs = imgs.reshape((K, s_c) + tuple(imgs.shape[1:])).contiguous()
             summary = metrics.summarize(imgs if K > 1 else imgs[0], x_orig[k:k + 1], replicas=K,
                                         rhat_threshold=opt.rhat_threshold, calibration=opt.calibration,
-                                        credible=opt.credible)
+                                        credible=opt.credible, pcs=opt.pcs)
             rows += _metric_rows([s], summary)
             if opt.save_images and s_c:
                 _save_report_images(summary, 0, s, imgs[0, 0], opt.image_folder)
     return _report(rows, images.shape[0], rank, world, device, opt.metrics_out, K, opt.rhat_threshold, opt.calibration,
-                   opt.credible)
+                   opt.credible, opt.pcs)
 
 
 if __name__ == '__main__':

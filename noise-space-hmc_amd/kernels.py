@@ -1251,6 +1251,50 @@ def credible(samples, x_orig, n_replicas=1, k=1):
     return lower, median, upper, summary
 
 
+def _pooled(samples, n_replicas, what):
+    """-> (G, S, N): the images, samples per chain and elements of a [G * n_replicas, S, C, H, W] block on the GPU."""
+    if not samples.is_cuda:
+        raise _lib.NhmcError(f'{what}: samples must live on the GPU (got {samples.device}); libnhmc has no CPU path')
+    B, S, Cc, H, W = _sample_block(samples)
+    K = int(n_replicas)
+    if K < 1 or B % K:
+        raise _lib.NhmcError(f'{what}: {B} chains are not a multiple of {n_replicas} replicas')
+    return B // K, S, Cc * H * W
+
+
+def sample_gram(samples, x_orig, n_replicas=1):
+    """Gram matrix of an image's pooled draws about the first one (nhmc.h "Principal components of the posterior samples").
+    samples [G * n_replicas, S, C, H, W], chain g * n_replicas + r being replica r of image g, x_orig [G, C, H, W] or None,
+    2 <= n = n_replicas * S <= 256 -> [G, n, n] float64: rows u_1 ... u_{n-1} = d_2 - d_1 ... d_n - d_1 and u_n = t - d_1
+    (NaN without x_orig), exactly symmetric."""
+    G, S, N = _pooled(samples, n_replicas, 'sample_gram')
+    lib = _lib.load()
+    K, dev = int(n_replicas), samples.device
+    if x_orig is not None and (x_orig.dim() != 4 or x_orig.shape[0] != G or x_orig.shape[1:] != samples.shape[2:]):
+        raise _lib.NhmcError(f'x_orig {tuple(x_orig.shape)} does not match {G} images of samples {tuple(samples.shape)}')
+    n = K * S
+    gram = torch.empty((G, n, n), dtype=torch.float64, device=dev)
+    ws = torch.empty(lib.nhmc_sample_gram_ws_bytes(G, n, N) // 8, dtype=torch.float64, device=dev)
+    _lib.check(lib.nhmc_sample_gram(_p(samples, torch.float32, 'samples'), _p(x_orig, torch.float32, 'x_orig'), _p(gram),
+                                    _p(ws), G, K, S, N, _stream()), 'nhmc_sample_gram')
+    return gram
+
+
+def sample_project(samples, coef, n_replicas=1):
+    """Images from coefficients over an image's pooled draws: out[g, j] = sum_i coef[g, j, i] (d_i - d_1) in fp64, rounded
+    once.  samples as for `sample_gram`, coef [G, J, n] float64 with 1 <= J <= 8 -> [G, J, C, H, W] float32."""
+    G, S, N = _pooled(samples, n_replicas, 'sample_project')
+    lib = _lib.load()
+    K, n = int(n_replicas), int(n_replicas) * S
+    if coef.dim() != 3 or coef.shape[0] != G or coef.shape[2] != n:
+        raise _lib.NhmcError(f'coef {tuple(coef.shape)} does not match {G} images of {n} pooled draws')
+    J = coef.shape[1]
+    out = torch.empty((G, J) + tuple(samples.shape[2:]), dtype=torch.float32, device=samples.device)
+    _lib.check(lib.nhmc_sample_project(_p(samples, torch.float32, 'samples'), _p(coef, torch.float64, 'coef'), _p(out),
+                                       G, K, S, J, N, _stream()), 'nhmc_sample_project')
+    return out
+
+
 # ---- a1-------------------------------------------------------------------------------------
 def randn_philox(shape, seed, chain_id0, draw, scale=1.0, device='cuda', out=None):
     lib = _lib.load()

@@ -14,6 +14,9 @@ on the device.
     credible(samples, x_orig)        the interval calibration speaks of, as maps: the order statistics d_(k) and d_(n+1-k)
                                      of an image's pooled draws and their median, per element, with summaries
     save_ci_width_map(lower, upper, path)   the `ci_width_map_{idx}.png` picture
+    pcs(samples, x_orig)             the principal components of an image's pooled draws: direction images, eigenvalues,
+                                     the variance they carry and how much of the error lies along them
+    pcs_from_gram(gram, count)       the host part of it: the eigen-solve of the kernel's n x n Gram matrix
 
 With K replica chains per image (not in the reference, which runs one chain) the block is [G * K, S, C, H, W], chain
 g * K + r being replica r of image g, and `summarize(..., replicas=K)` pools an image's K * S samples.
@@ -208,7 +211,101 @@ def _no_credible(G):
     return dict(lower=None, median=None, upper=None, **{k: np.full(G, np.nan) for k in CREDIBLE_KEYS})
 
 
-def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1, calibration=None, credible=None):
+PCS_KEYS = ('pc_count', 'pc_rank', 'pc_var_first', 'pc_var_top', 'pc_eff_rank', 'pc_err_in_span', 'pc_z_rms')
+PCS_MAX_N, PCS_MAX_COUNT = 256, 8
+PCS_RANK_TOL = 1e-12                          # an eigenvalue counts while it is above this share of the first
+
+
+def pcs_from_gram(gram, count=3):
+    """The principal components of the sample covariance from the kernel's Gram matrix, in float64 numpy on the host.
+    gram [G, n, n] (include/nhmc.h: rows u_1 ... u_{n-1} = d_{i+1} - d_1 and u_n = t - d_1, the last NaN without an
+    original) -> dict of PCS_KEYS as float64 [G], `eigenvalues` [G, n - 1] (descending) and `coef` [G, count, n], the
+    coefficients `kernels.sample_project` turns into sqrt(lambda_j) v_j: one posterior standard deviation along
+    component j, in image units.
+
+    With u_0 = 0 the centred Gram of the n draws is C = J Sd J, J = I - 11^T / n, Sd the Gram of u_0 ... u_{n-1}; its
+    eigenpairs (lambda (n - 1), V) give the covariance's: lambda_j and the unit direction v_j = sum_i a_ji (d_i - d_1) with
+    a_j = V[:, j] / sqrt((n - 1) lambda_j), whose sum is 0.  Sign: the coefficient of largest magnitude is positive, the
+    lowest index winning a tie.  With eps = t - mean and q_j = <eps, v_j>, both from the Gram's last row:
+        pc_rank          #{lambda_j > 1e-12 lambda_1}; 0 if lambda_1 <= 0 or the draws' Gram holds a non-finite value
+        pc_count         min(count, pc_rank): the directions served, the other rows of `coef` are zero
+        pc_var_first     lambda_1 / sum lambda,  pc_var_top = sum_{j <= pc_count} lambda_j / sum lambda
+        pc_eff_rank      (sum lambda)^2 / sum lambda^2
+        pc_err_in_span   sum_{j <= pc_rank} q_j^2 / |eps|^2: the share of the error inside the samples' span
+        pc_z_rms         sqrt(mean_{j <= pc_count} q_j^2 / lambda_j): 1 when the error along the components is the size
+                         they predict -- the correlated counterpart of `z_rms`
+    The last two are NaN without an original or with |eps|^2 = 0; everything but the two counts is NaN at rank 0."""
+    gram = np.asarray(gram, dtype=np.float64)
+    G, n = gram.shape[0], gram.shape[-1]
+    count = int(count)
+    out = {k: np.full(G, np.nan) for k in PCS_KEYS}
+    out['pc_count'], out['pc_rank'] = np.zeros(G), np.zeros(G)
+    eigenvalues, coef = np.full((G, n - 1), np.nan), np.zeros((G, count, n))
+    centre = np.eye(n) - np.full((n, n), 1.0 / n)
+    for g in range(G):
+        Sd = np.zeros((n, n))
+        Sd[1:, 1:] = gram[g, :n - 1, :n - 1]
+        if not np.isfinite(Sd).all():
+            continue
+        lam, V = np.linalg.eigh(centre @ Sd @ centre / (n - 1.0))
+        lam, V = lam[::-1][:n - 1], V[:, ::-1][:, :n - 1]
+        eigenvalues[g] = lam
+        if not np.isfinite(lam).all() or not lam[0] > 0.0:
+            continue
+        rank = int((lam > PCS_RANK_TOL * lam[0]).sum())
+        served = min(count, rank)
+        total = lam.sum()
+        a = V[:, :rank] / np.sqrt((n - 1.0) * lam[:rank])                    # [n, rank]: unit directions
+        big = np.abs(a).argmax(axis=0)
+        a = a * np.where(a[big, np.arange(rank)] < 0.0, -1.0, 1.0)
+        coef[g, :served] = (a[:, :served] * np.sqrt(lam[:served])).T
+        out['pc_count'][g], out['pc_rank'][g] = served, rank
+        out['pc_var_first'][g], out['pc_var_top'][g] = lam[0] / total, lam[:served].sum() / total
+        out['pc_eff_rank'][g] = total * total / (lam * lam).sum()
+        last = gram[g, n - 1]
+        if not np.isfinite(last).all():
+            continue
+        gw = np.concatenate([[0.0], last[:n - 1]])                            # <t - d_1, u_i>, i = 0 ... n - 1
+        eps2 = last[n - 1] - 2.0 * gw.mean() + Sd.mean()                      # |t - d_1 - mean u|^2
+        if not eps2 > 0.0:
+            continue
+        q = a.T @ (gw - Sd.mean(axis=0))                                      # sum a_j = 0: the mean's own part drops out
+        out['pc_err_in_span'][g] = (q * q).sum() / eps2
+        out['pc_z_rms'][g] = np.sqrt((q[:served] ** 2 / lam[:served]).mean())
+    return dict(out, eigenvalues=eigenvalues, coef=coef)
+
+
+def _pcs_count(count):
+    count = int(count)
+    if not 1 <= count <= PCS_MAX_COUNT:
+        raise _lib.NhmcError(f'pcs: count must be 1 ... {PCS_MAX_COUNT}, got {count}')
+    return count
+
+
+def _pcs_result(samples, replicas, host_gram, count):
+    """The host part after the read: the eigen-solve, then the projection with uploaded coefficients."""
+    res = pcs_from_gram(host_gram, count)
+    coef = torch.from_numpy(np.ascontiguousarray(res.pop('coef'))).to(samples.device)
+    return dict(directions=K.sample_project(samples, coef, replicas), eigenvalues=res.pop('eigenvalues'), **res)
+
+
+def pcs(samples, x_orig=None, replicas=1, count=3):
+    """The principal components of an image's pooled draws (the Gram matrix is defined in include/nhmc.h, the figures in
+    `pcs_from_gram`).  samples [G * K, S, C, H, W] with 2 <= K * S <= 256, x_orig [G, C, H, W] or None, 1 <= count <= 8
+    -> dict: `directions` (device, float32 [G, count, C, H, W]: sqrt(lambda_j) v_j, zero past pc_count), `eigenvalues`
+    (float64 numpy [G, K * S - 1]) and PCS_KEYS as float64 numpy [G], with one device->host read.  Nothing of the size of
+    the covariance is formed: the n x n Gram matrix comes from the device, its eigenvectors from numpy."""
+    samples, x_orig, _ = _block(samples, x_orig)
+    count = _pcs_count(count)
+    gram = K.sample_gram(samples, x_orig, replicas)
+    return _pcs_result(samples, replicas, gram.cpu().numpy(), count)
+
+
+def _no_pcs(G):
+    return dict(directions=None, eigenvalues=None, **{k: np.full(G, np.nan) for k in PCS_KEYS})
+
+
+def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1, calibration=None, credible=None, pcs=None):
     """Everything the report prints or saves for B chains with S samples each, with one device->host read.
 
     -> dict of float64 numpy arrays [B]: psnr_mean, psnr_std, ssim_mean, ssim_std (np.mean / np.std(ddof=1) over the
@@ -228,9 +325,14 @@ def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1, calibration=None,
 
     credible = level (None, the default, changes nothing): the dict gains, after everything else, what `credible` returns
     for the pooled K * S samples -- `lower`, `median`, `upper` and CREDIBLE_KEYS -- in the same single read.  With fewer
-    than two pooled samples the three maps are None and the figures NaN."""
+    than two pooled samples the three maps are None and the figures NaN.
+
+    pcs = count (None, the default, changes nothing): the dict gains, after everything else, what `pcs` returns for the
+    pooled K * S samples -- `directions`, `eigenvalues` and PCS_KEYS.  The Gram matrix rides in the same single read; the
+    projection is launched after it with uploaded coefficients.  With fewer than two or more than 256 pooled samples
+    `directions` and `eigenvalues` are None and the figures NaN."""
     replicas = int(replicas)
-    if replicas == 1 and calibration is None and credible is None:
+    if replicas == 1 and calibration is None and credible is None and pcs is None:
         return _summarize(samples, x_orig)
     samples, x_orig, _ = _block(samples, x_orig)
     B, S = samples.shape[:2]
@@ -242,8 +344,10 @@ def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1, calibration=None,
     n = replicas * S
     rank = coverage_rank(n, credible) if credible is not None and n >= 2 else None
     cred = None if rank is None else K.credible(samples, x_orig, replicas, rank)
+    count = None if pcs is None else _pcs_count(pcs)
+    gram = K.sample_gram(samples, x_orig, replicas) if count is not None and 2 <= n <= PCS_MAX_N else None
     extra = ([] if diag is None else [diag[2]]) + ([] if cal is None else [cal[3], cal[2].double()]) + \
-        ([] if cred is None else [cred[3]])
+        ([] if cred is None else [cred[3]]) + ([] if gram is None else [gram.reshape(G, n * n)])
     out = _summarize(samples.reshape((G, replicas * S) + tuple(samples.shape[2:])), x_orig,
                      extra=torch.cat(extra, dim=1) if extra else None)
     host = out.pop('extra', None)
@@ -252,15 +356,21 @@ def summarize(samples, x_orig, replicas=1, rhat_threshold=1.1, calibration=None,
         out['rhat'], out['ess'] = (None, None) if diag is None else diag[:2]
         for i, k in enumerate(CONVERGENCE_KEYS):
             out[k] = np.full(G, np.nan) if diag is None else host[:, i].copy()
+    # the blocks of `extra`, in its order; each one that rode along moves the offset on, whatever the other flags are
     at = 0 if diag is None else len(CONVERGENCE_KEYS)
+    at_cal, at = at, at + (0 if cal is None else len(CALIBRATION_SUMS) + n + 1)
+    at_cred, at = at, at + (0 if cred is None else len(CREDIBLE_SUMS))
+    at_gram = at
     if calibration is not None:
         out.update(_no_calibration(G) if cal is None else _calibration_result(
-            cal[0], cal[1], host[:, at:at + len(CALIBRATION_SUMS) + n + 1], cal[0][0].numel(), calibration))
+            cal[0], cal[1], host[:, at_cal:at_cred], cal[0][0].numel(), calibration))
     if credible is not None:
-        at += 0 if cal is None else len(CALIBRATION_SUMS) + n + 1
         out.update(_no_credible(G) if cred is None else dict(
             lower=cred[0], median=cred[1], upper=cred[2],
-            **credible_from_sums(host[:, at:at + len(CREDIBLE_SUMS)], n, rank, cred[0][0].numel())))
+            **credible_from_sums(host[:, at_cred:at_gram], n, rank, cred[0][0].numel())))
+    if count is not None:
+        out.update(_no_pcs(G) if gram is None else _pcs_result(
+            samples, replicas, host[:, at_gram:at_gram + n * n].reshape(G, n, n), count))
     return out
 
 
