@@ -377,6 +377,51 @@ int nhmc_data_phase_vjp(const float* xt_next, const float* y, const float* fac, 
                         float* tmp, int n_chains, int channels, int dim, int pad, nhmc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * General 2-D PSF blur (--deg deblur_motion): camera shake, defocus, any measured PSF.  Not in the reference's
+ * prepare_measurement (its README names an external motion-blur generator that is never wired); the two blurs it has
+ * are separable and run through the spectral chain above.
+ *
+ * PSF: k[K][K] fp32, K odd, 1 <= K <= 63, R = (K - 1) / 2; one PSF for every channel (depthwise), any sign.  M = N and
+ * y has the image's shape [n_chains][C][dim][dim].
+ * Tap list: the host compacts the PSF's NON-ZERO entries in row-major order (i ascending, then j) into n_taps taps
+ * (dy, dx, w) with dy = i - R, dx = j - R.  A zero entry is not a tap: a PSF with a rim of zeros added has the same list
+ * and gives the same bits, and an inf under a zero entry stays out (no 0 * inf = NaN).  Everything is defined on the list:
+ *   (H x)[c][r][s]   = sum_t w_t x[c][r + dy_t][s + dx_t]      correlation form, terms outside the image omitted
+ *                      (zero boundary) -- F.conv2d(x, k, padding = R) per plane
+ *   (H^T w)[c][r][s] = sum_t w_t w[c][r - dy_t][s - dx_t]      the exact adjoint: the same list, offsets negated
+ * Both accumulate the taps in list order from 0.0f, one fmaf per tap; where the zero boundary applies the term is a
+ * +0 * w_t product of a finite weight, which changes no bit of a finite sum.
+ * taps_off: DEVICE int32[n_taps][2] = (dy, dx), 8-byte aligned; taps_w: DEVICE float[n_taps]; ksize = K, or any smaller
+ * odd size that still holds every offset (the kernels stage a halo of (ksize - 1) / 2 pixels, so the list's own extent
+ * 2 max(|dy|, |dx|) + 1 is the cheapest; the result does not depend on it).
+ * The entries reject an even K, K > 63, n_taps < 1 or > K^2 (NHMC_ERR_SHAPE) and dim % 4 != 0 (NHMC_ERR_ALIGN).  They
+ * cannot read the device list: nhmc_blur2d_check_taps does the same checks and the offset range [-R, R] on the HOST copy
+ * (the Python front end calls it when it builds a list), and the kernels clamp an offset into that range (no read leaves the
+ * staged halo whatever the device list holds).
+ *   nhmc_blur2d_apply    : out = H x, or H^T x when transpose != 0 (out != x).
+ *   nhmc_blur2d_tiles    : loss partials per chain of the two data terms.
+ *   nhmc_data_blur2d     : loss partials of sum (y - H v)^2, v = clip(xt) when apply_clip else xt (fp32 squares, fp64 tile
+ *                          partials, nhmc_sum_partials adds them in a fixed order), and autograd's gradient
+ *                          g_xt = H^T(-2 r) [1[|xt| <= 1] when apply_clip, selected as nhmc_masked does].  Two passes;
+ *                          the residual r lives in tmp (float[n_chains * C * dim * dim], not aliasing xt or g_xt).
+ *   nhmc_data_blur2d_vjp : the same on xt_next (the clipped decode of the LAST DDIM step, no further clip) with that
+ *                          step's VJP (inputs xt_in, e) as the epilogue of the adjoint pass: writes g_xt and channels
+ *                          [0, C) of g_e, and zeros channels [C, 2C) when fill_sigma and e_channels == 2C
+ *                          (as nhmc_mix_bwd_hdr).
+ * ---------------------------------------------------------------------------------- */
+int nhmc_blur2d_check_taps(const int32_t* host_off, int n_taps, int ksize);
+int nhmc_blur2d_tiles(int channels, int dim);
+int nhmc_blur2d_apply(const float* x, const int32_t* taps_off, const float* taps_w, int n_taps, int ksize, int transpose,
+                      float* out, int n_chains, int channels, int dim, nhmc_stream_t stream);
+int nhmc_data_blur2d(const float* xt, const float* y, const int32_t* taps_off, const float* taps_w, int n_taps, int ksize,
+                     int apply_clip, float* g_xt, double* loss_ws, float* tmp, int n_chains, int channels, int dim,
+                     nhmc_stream_t stream);
+int nhmc_data_blur2d_vjp(const float* xt_next, const float* y, const int32_t* taps_off, const float* taps_w, int n_taps,
+                         int ksize, const float* xt_in, const float* e, int e_channels, const float* at,
+                         const float* at_next, float* g_xt, float* g_e, int fill_sigma, double* loss_ws, float* tmp,
+                         int n_chains, int channels, int dim, nhmc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * a5  Hamiltonian                          main_sampling.py:697,717-718
  *   H = (0.5*Sx + (1/(2 sigma_y^2))*loss) + (0.5*Sp)*m^-1, per chain, in the reference's fp32
  *   op order on fp32-rounded sums; Sx,Sp summed (fixed order, fp64) from the leapfrog partials.

@@ -74,6 +74,11 @@ SIGNATURES = {
     'nhmc_phase_adjoint': (I, [P, P, P, P, I, I, I, I, P]),
     'nhmc_data_phase': (I, [P, P, P, I, P, P, P, I, I, I, I, P]),
     'nhmc_data_phase_vjp': (I, [P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, P]),
+    'nhmc_blur2d_check_taps': (I, [P, I, I]),
+    'nhmc_blur2d_tiles': (I, [I, I]),
+    'nhmc_blur2d_apply': (I, [P, P, P, I, I, I, P, I, I, I, P]),
+    'nhmc_data_blur2d': (I, [P, P, P, P, I, I, I, P, P, P, I, I, I, P]),
+    'nhmc_data_blur2d_vjp': (I, [P, P, P, P, I, I, P, P, I, P, P, P, P, I, P, P, I, I, I, P]),
     'nhmc_hamiltonian': (I, [P, I, P, P, D, P, P, I, P]),
     'nhmc_metropolis': (I, [P, P, P, P, P, P, I, P]),
     'nhmc_schedule_begin': (I, [P, P, P, P, P, P, D, I, I, I, P]),

@@ -18,6 +18,10 @@ image's result does not depend on the number of ranks (nor, up to the score netw
 convolution rounding, on `--chains`).  `--spectral_projected` switches the two blur operators to the four-product data
 term (operators.Deblurring2D).
 
+`--deg deblur_motion` (not wired in the reference) blurs with a seeded camera-shake PSF (operators.motion_kernel, drawn
+from the global torch RNG right after the seed is set, so every rank holds the same one) through the general 2-D blur
+kernels (operators.Blur2D); with `--save_images` rank 0 also writes `blur_kernel.png`, the PSF min-max normalised, once.
+
 `--replicas K` spends the chains on K replica chains per image instead (a batch then holds `--chains` // K images, chain
 i * K + r being replica r of the batch's image i): all replicas see the same measurement, replica 0 starts where the
 single chain starts, replicas r >= 1 start from their own N(0,1) draw keyed by (seed, s, r), and the Philox stream of
@@ -257,6 +261,11 @@ def _setup(opt, latent):
     size, ch = config['data']['image_size'], config['data']['channels']
     # mask = first torch RNG draw, as in the reference
     op = operators.build_operator(opt.deg, ch, size, device, spectral_projected=opt.spectral_projected or None)
+    if opt.save_images and rank == 0 and isinstance(op, operators.Blur2D):
+        k = op.kernel
+        span = float(k.max() - k.min())
+        k01 = (k - k.min()) / span if span > 0 else torch.ones_like(k)
+        sampler._save_png((2 * k01 - 1)[None].expand(3, -1, -1), os.path.join(opt.image_folder, 'blur_kernel.png'))
     opt.sigma_0 = 2 * opt.sigma_0                                           # [-1,1] scaling, main_sampling.py:348
     if world > 1 and not opt.philox:
         if rank == 0:

@@ -746,6 +746,96 @@ def data_phase_vjp(xt_next, y, fac, pad, xt, e, at, at_next, g_e_out=None, loss_
     return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
 
 
+# ---- general 2-D PSF blur (deblur_motion) --------------------------------------------------------
+class BlurTaps:
+    """The compacted tap list of a 2-D PSF (include/nhmc.h): the non-zero entries of k [K, K] in row-major order as
+    (dy, dx) = (i - R, j - R) and w.  `off` int32 [T, 2] and `w` float32 [T] are the host copies, `off_dev` / `w_dev` what
+    the kernels read.  Built and checked once (nhmc_blur2d_check_taps); constructible on 'cpu' (no device copies used)."""
+
+    def __init__(self, kernel2d, device):
+        k = torch.as_tensor(kernel2d).detach().cpu()
+        if k.dim() != 2 or k.shape[0] != k.shape[1]:
+            raise _lib.NhmcError(f'a PSF is a square [K, K] array, got {tuple(k.shape)}')
+        k = k.to(torch.float32).contiguous()
+        self.ksize = K_ = int(k.shape[0])
+        if K_ % 2 == 0 or K_ > 63:
+            raise _lib.NhmcError(f'PSF size must be odd and at most 63, got {K_}')
+        self.radius = R = (K_ - 1) // 2
+        ij = torch.nonzero(k)                                       # row-major: i ascending, then j
+        if ij.shape[0] == 0:
+            raise _lib.NhmcError('the PSF has no non-zero entry')
+        self.off = (ij - R).to(torch.int32).contiguous()
+        self.w = k[ij[:, 0], ij[:, 1]].contiguous()
+        self.n = int(ij.shape[0])
+        rc = _lib.load().nhmc_blur2d_check_taps(C.c_void_p(self.off.data_ptr()), self.n, K_)
+        _lib.check(rc, 'nhmc_blur2d_check_taps')
+        self.off_dev, self.w_dev = self.off.to(device), self.w.to(device)
+        # the halo the kernels stage is (ksize - 1) / 2: hand them the list's own extent, not the array's (a camera-shake
+        # path seldom fills its 61 x 61 support, and a rim of zeros then costs nothing)
+        self.extent = 2 * int(self.off.abs().max()) + 1
+
+    def args(self):
+        return _p(self.off_dev, torch.int32, 'taps_off'), _p(self.w_dev, torch.float32, 'taps_w'), self.n, self.extent
+
+
+def _blur_shapes(x):
+    if x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise _lib.NhmcError(f'the 2-D blur takes [B, C, d, d] planes, got {tuple(x.shape)}')
+    return x.shape[0], x.shape[1], x.shape[2]
+
+
+def blur2d_tiles(channels, dim):
+    return _lib.load().nhmc_blur2d_tiles(channels, dim)
+
+
+def blur2d_apply(x, taps, transpose=False):
+    """H x (correlation with the PSF, zero boundary), or the exact adjoint H^T x -> same shape."""
+    lib = _lib.load()
+    B, Cc, dim = _blur_shapes(x)
+    out = torch.empty_like(x)
+    rc = lib.nhmc_blur2d_apply(_p(x, torch.float32, 'x'), *taps.args(), int(transpose), _p(out), B, Cc, dim, _stream())
+    _lib.check(rc, 'nhmc_blur2d_apply')
+    return out
+
+
+def _blur_y(y, xt):
+    if tuple(y.shape) != tuple(xt.shape):
+        raise _lib.NhmcError(f'the blur observation has the image shape {tuple(xt.shape)}, got {tuple(y.shape)}')
+
+
+def data_blur2d(xt, y, taps, apply_clip=True, loss_out=None):
+    """-> (loss [B] float64, g_xt) for H = the PSF blur; y [B, C, d, d]."""
+    lib = _lib.load()
+    B, Cc, dim = _blur_shapes(xt)
+    _blur_y(y, xt)
+    tiles = lib.nhmc_blur2d_tiles(Cc, dim)
+    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
+    tmp, g = torch.empty_like(xt), torch.empty_like(xt)
+    rc = lib.nhmc_data_blur2d(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), *taps.args(), int(apply_clip), _p(g),
+                              _p(ws), _p(tmp), B, Cc, dim, _stream())
+    _lib.check(rc, 'nhmc_data_blur2d')
+    return sum_partials(ws, tiles, B, out=loss_out), g
+
+
+def data_blur2d_vjp(xt_next, y, taps, xt, e, at, at_next, g_e_out=None, loss_out=None):
+    """Blur data term on the clipped decode `xt_next` + VJP of the last DDIM step (inputs xt, e) in the adjoint pass's
+    epilogue -> (loss [B] float64, g_xt, g_e)."""
+    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
+    lib = _lib.load()
+    _, _, dim = _blur_shapes(xt)
+    _blur_y(y, xt)
+    if xt_next.shape != xt.shape:
+        raise _lib.NhmcError('xt_next must have the shape of xt')
+    tiles = lib.nhmc_blur2d_tiles(Cc, dim)
+    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
+    tmp = torch.empty_like(xt)
+    rc = lib.nhmc_data_blur2d_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y, torch.float32, 'y'), *taps.args(),
+                                  _p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next), _p(g_xt),
+                                  _p(g_e, torch.float32, 'g_e'), int(g_e_out is None), _p(ws), _p(tmp), B, Cc, dim, _stream())
+    _lib.check(rc, 'nhmc_data_blur2d_vjp')
+    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+
+
 # ---- a5-a7 ----------------------------------------------------------------------------------
 def hamiltonian(sums_ws, n_elem, loss, sigma_y, m_inv, want_terms=False, sel=None):
     """sel (int32 [B]): loss is then the gradient cache's loss_pair [2, B] and chain c uses loss[sel[c], c]."""

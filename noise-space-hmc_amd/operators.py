@@ -1,5 +1,6 @@
-"""Forward operators with the reference's `H_functions` surface, on the HIP kernels (the linear ones, and the two
-nonlinear ones that need nothing from outside: HDR and phase retrieval).
+"""Forward operators with the reference's `H_functions` surface, on the HIP kernels (the linear ones, the two
+nonlinear ones that need nothing from outside: HDR and phase retrieval, and a general 2-D PSF blur, `Blur2D`, which the
+reference does not have).
 
 Mirrors obs_functions/Hfuncs.py for the three operators on the HMC hot path -- same constructor
 arguments, same `H / Ht / H_pinv / is_linear`, inputs `[B, ...]`, outputs `[B, flat]` -- but each
@@ -559,6 +560,102 @@ class PhaseRetrievalOperator(H_functions):
                                 loss_out=loss_out)
 
 
+class Blur2D(H_functions):
+    """A general 2-D point-spread function (camera shake, defocus, a measured PSF): H = F.conv2d(x, k, padding=R) per
+    channel plane (correlation, zero boundary -- what `_band_matrix` gives the separable blurs), H^T its exact adjoint;
+    M = C d^2.  Not in the reference's prepare_measurement.  The operator is carried as the compacted list of the PSF's
+    non-zero taps (include/nhmc.h); `kernel2d` is any [K, K] array, K odd and at most 63."""
+
+    def __init__(self, kernel2d, channels, img_dim, device):
+        self.channels, self.img_dim, self.device = channels, img_dim, device
+        if img_dim % 4:
+            raise NhmcError('the 2-D blur needs img_dim % 4 == 0')
+        self._taps = K.BlurTaps(kernel2d, device)
+        self.kernel = torch.as_tensor(kernel2d).detach().cpu().float().clone()
+        self.M = channels * img_dim ** 2
+
+    def taps(self):
+        """The compacted tap list -> (off int32 [T, 2] = (dy, dx), w float32 [T]), host tensors, row-major order."""
+        return self._taps.off, self._taps.w
+
+    def H(self, vec):
+        x = _img(vec, self.channels, self.img_dim)
+        return K.blur2d_apply(x, self._taps).reshape(x.shape[0], -1)
+
+    def Ht(self, vec):
+        y = _img(vec, self.channels, self.img_dim)
+        return K.blur2d_apply(y, self._taps, transpose=True).reshape(y.shape[0], -1)
+
+    def H_pinv(self, vec):
+        raise NotImplementedError('a general PSF has no closed-form pseudo-inverse here; no sampler calls H_pinv')
+
+    def _obs(self, y, shape):
+        y = y.reshape(shape)
+        return y if y.is_contiguous() else y.contiguous()
+
+    def data_term(self, xt, y, apply_clip=True, loss_out=None):
+        return K.data_blur2d(xt, self._obs(y, xt.shape), self._taps, apply_clip, loss_out=loss_out)
+
+    fused_wants_decode = True              # the engine hands over the clipped decode it already holds
+
+    def fused_last_vjp(self, xt_in, e, at, at_next, y, g_e_out=None, xt_next=None, loss_out=None):
+        """Data term + VJP of the last DDIM step (the adjoint pass's epilogue) -> (loss, g_xt, g_e)."""
+        if xt_next is None:
+            xt_next = K.ddim_mix_fwd(xt_in, e, at, at_next, final_clip=True)['xt_next']
+        return K.data_blur2d_vjp(xt_next, self._obs(y, xt_in.shape), self._taps, xt_in, e, at, at_next, g_e_out=g_e_out,
+                                 loss_out=loss_out)
+
+
+def motion_kernel(size=61, intensity=0.5, generator=None):
+    """A seeded camera-shake PSF [size, size] (fp32, >= 0, sum 1, centroid at the centre), our own construction.
+    A random walk with inertia: `steps` unit-ish steps whose heading turns by Gaussian noise scaled by `intensity`
+    (0: a straight segment) with an occasional sharp turn, drawn on the CPU from `generator` (the global torch RNG when
+    None, so every rank holds the same PSF after torch.manual_seed).  The path is scaled to fit the support, shifted so
+    that its centroid is the centre pixel, splatted bilinearly (at most 4 non-zeros per path point), normalised in float64."""
+    if size < 1 or size % 2 == 0 or size > 63:
+        raise NhmcError(f'motion_kernel: size must be odd and in [1, 63], got {size}')
+    if not 0.0 <= intensity <= 1.0:
+        raise NhmcError('motion_kernel: intensity lies in [0, 1]')
+    if size == 1:
+        return torch.ones(1, 1)
+    steps = 2 * size
+    draws = torch.rand(2 + 2 * steps, generator=generator, dtype=torch.float64)            # one draw, fixed length
+    normal = torch.randn(steps, generator=generator, dtype=torch.float64)
+    heading = float(draws[0]) * 2 * math.pi
+    length = (0.4 + 0.4 * float(draws[1])) * (size - 1)                                     # path length in pixels
+    step = length / steps
+    pts = torch.zeros(steps + 1, 2, dtype=torch.float64)
+    turn = 0.0
+    for i in range(steps):
+        # inertia: the turning rate is a damped random walk; a rare jerk (more likely at high intensity) kicks it
+        turn = 0.7 * turn + intensity * 0.25 * float(normal[i])
+        if float(draws[2 + i]) < 0.1 * intensity:
+            turn += (float(draws[2 + steps + i]) - 0.5) * math.pi * intensity
+        heading += turn
+        pts[i + 1, 0] = pts[i, 0] + step * math.sin(heading)
+        pts[i + 1, 1] = pts[i, 1] + step * math.cos(heading)
+    pts = pts - pts.mean(0, keepdim=True)                               # the centroid of the (equally weighted) points
+    reach = float(pts.abs().max())
+    limit = (size - 1) / 2 - 1.0                                        # the bilinear footprint stays inside the support
+    if reach > limit:
+        pts = pts * (limit / reach)
+    pts = pts + (size - 1) / 2
+    k = torch.zeros(size, size, dtype=torch.float64)
+    i0 = pts.floor().long()
+    f = pts - i0
+    for di in (0, 1):
+        for dj in (0, 1):
+            wgt = (f[:, 0] if di else 1 - f[:, 0]) * (f[:, 1] if dj else 1 - f[:, 1])
+            k.index_put_((i0[:, 0] + di, i0[:, 1] + dj), wgt, accumulate=True)
+    k = k / k.sum()
+    return k.float()
+
+
+def motion_kernel_points(size):
+    """Number of path points `motion_kernel(size)` splats (the PSF has at most 4 non-zeros per point)."""
+    return 1 if size == 1 else 2 * size + 1
+
+
 def bicubic_taps(factor, a=-0.5):
     """main_sampling.py:266-279."""
     def w(x):
@@ -602,6 +699,9 @@ def build_operator(deg, channels, img_dim, device, generator=None, spectral_proj
         return Deblurring2D(gaussian_taps(1.0), gaussian_taps(20.0), channels, img_dim, device, projected=spectral_projected)
     if deg == 'deblur_gauss':
         return Deblurring(gaussian_taps(10.0, half=2), channels, img_dim, device, projected=spectral_projected)  # main_sampling.py:308-314
+    if deg == 'deblur_motion':                                          # not wired in the reference: our own seeded PSF
+        size = 61 if img_dim >= 61 else (img_dim - 1) - (img_dim % 2)   # the largest odd size <= img_dim - 1
+        return Blur2D(motion_kernel(size, 0.5, generator), channels, img_dim, device)
     if 'phase' in deg:                                                  # main_sampling.py:315-318 (substring match, as there)
         return PhaseRetrievalOperator(2.0, device, channels=channels, img_dim=img_dim)
     if 'hdr' in deg:                                                    # :319-322

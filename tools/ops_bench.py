@@ -80,3 +80,32 @@ print(f'phase_retrieval B={B}: data term {ms*1e3:.1f} us {flf/ms/1e9:.1f} TFLOP/
       f'({flf/1e9:.1f} GFLOP);  deblur_aniso + last VJP, same session: {msa*1e3:.1f} us')
 ms = timeit(lambda: opf.H(x), 10)
 print(f'phase_retrieval H B={B}: {ms*1e3:.1f} us')
+# the general 2-D PSF blur (deblur_motion): the seeded sparse camera-shake PSF and a dense K = 61 one.  Yardstick in the
+# same process with windows alternating: torch's depthwise F.conv2d for H, its autograd for the data term.  Bound: the tap
+# loop moves one LDS dword per FMA and ds_read_b32 runs at 32 lanes/clk/CU -> 256 CUs x 32 x 2.4 GHz = 19.7 T FMA/s.
+import torch.nn.functional as F
+def alternate(f, g, windows=3, n=5):
+    a, b = [], []
+    for _ in range(windows):
+        a.append(timeit(f, n)); b.append(timeit(g, n))
+    return sorted(a)[len(a) // 2], sorted(b)[len(b) // 2]
+gen = torch.Generator().manual_seed(5678)
+dense = torch.rand(61, 61, generator=gen) + 0.1
+for name, psf in (('deblur_motion sparse', operators.motion_kernel(61, 0.5, gen)), ('dense K=61', dense / dense.sum())):
+    om = operators.Blur2D(psf, 3, 256, dev)
+    Tn = om.taps()[1].numel()
+    wt = psf.to(dev)[None, None].expand(3, 1, 61, 61).contiguous()
+    ym = K.randn_philox((B, 3, 256, 256), 1, 0, 3)
+    def torch_H():
+        return F.conv2d(x, wt, padding=30, groups=3)
+    def torch_data():
+        xl = x.detach().requires_grad_(True)
+        loss = ((ym - F.conv2d(xl.clamp(-1, 1), wt, padding=30, groups=3)) ** 2).sum()
+        return torch.autograd.grad(loss, xl)
+    fma = B * 3 * 256 * 256 * Tn
+    msH, msHt = alternate(lambda: om.H(x), torch_H)
+    msD, msDt = alternate(lambda: om.data_term(x, ym, True), torch_data)
+    msV = timeit(lambda: om.fused_last_vjp(x, e6, at, an, ym, g_e_out=ge, xt_next=cur), 5)
+    print(f'{name} (T = {Tn}) B={B}: H {msH*1e3:.1f} us ({fma/msH/1e9:.2f} T FMA/s, {100*fma/msH/1e9/19.7:.0f}% of the LDS bound), '
+          f'torch conv2d {msHt*1e3:.1f} us;  data term {msD*1e3:.1f} us ({2*fma/msD/1e9:.2f} T FMA/s, '
+          f'{100*2*fma/msD/1e9/19.7:.0f}%), torch autograd {msDt*1e3:.1f} us;  data term + last VJP {msV*1e3:.1f} us')
