@@ -422,6 +422,56 @@ int nhmc_data_blur2d_vjp(const float* xt_next, const float* y, const int32_t* ta
                          int n_chains, int channels, int dim, nhmc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Sparse linear operators (operators.SparseLinear; --deg ct<V>, --deg sparse --operator FILE.npz): tomography,
+ * spatially varying blur, irregular sampling, mosaics -- any linear forward model given as a sparse matrix.  Not in the
+ * reference.  The general form of "operator as data": the 2-D blur above carries a tap list, this carries a matrix.
+ *
+ * One matrix A in R^{m x n}, n = dim * dim, applied to every channel plane alike (depthwise).  M = C * m and
+ * y is [n_chains][C][m].
+ * Canonical form, built once on the host (nhmc.kernels.SparseMatrix): entries sorted by (row, column); duplicate entries
+ * summed in float64, then rounded to fp32; an entry whose fp32 value is 0 is dropped -- a zero is not an entry, so an inf
+ * or NaN under it stays out (no 0 * inf = NaN), as for a zero tap.  A is stored as CSR: row_ptr int32[m + 1],
+ * col int32[nnz], val float[nnz].  A^T is stored as CSR too, built by a stable transpose: within a row of A^T the
+ * entries ascend by their row in A, with the same fp32 values.  Both lists stay resident on the DEVICE.
+ *   (A x)[c][i]   = sum_k val_k x[c][col_k]  over the entries k of row i
+ *   (A^T w)[c][j] = the same sum on the transposed list: the exact adjoint, both lists hold the same fp32 numbers.
+ * Summation: the entries of a row in list order from 0.0f, one fmaf per entry.  The same inputs give the same bits; a
+ * plane's result does not depend on n_chains, on channels or on where the plane sits in the batch.
+ * An empty row gives +0.  A NaN in x reaches exactly the outputs that have an entry on it.
+ * Limits: dim % 4 == 0 (NHMC_ERR_ALIGN, the data terms); 1 <= m, 1 <= nnz < 2^31, n_chains <= 65535, channels <= 65535,
+ * n_chains * channels <= 65535 * 64 (NHMC_ERR_SHAPE).  Image pointers and tmp 16-byte aligned.
+ * The entries cannot read the device lists: nhmc_sparse_check validates a HOST copy (row_ptr[0] = 0, row_ptr monotone,
+ * row_ptr[m] = nnz, every column in [0, n); the Python front end calls it for both lists), and the kernels clamp the row
+ * bounds into [0, nnz] and a column into [0, n), so no read leaves a buffer whatever the device lists hold.
+ *   nhmc_sparse_tiles      : loss partials per chain of the two data terms.
+ *   nhmc_sparse_tmp_floats : floats of tmp for every entry below (the plane-minor operand and result).
+ *   nhmc_sparse_apply      : out [n_chains][C][rows] = A x for x [n_chains][C][cols]; given the transposed list (rows = n,
+ *                            cols = m) the same entry computes A^T w.  out, x and tmp do not alias.
+ *   nhmc_data_sparse       : loss partials of sum (y - A v)^2, v = clip(xt) when apply_clip else xt (fp32 squares, fp64 tile
+ *                            partials, nhmc_sum_partials adds them in a fixed order), and autograd's gradient
+ *                            g_xt = A^T(-2 r) [1[|xt| <= 1] when apply_clip, selected as nhmc_masked does].  (row_ptr, col,
+ *                            val) is A, (t_row_ptr, t_col, t_val) is A^T, both with nnz entries.  The residual r lives in
+ *                            tmp (not aliasing xt or g_xt).
+ *   nhmc_data_sparse_vjp   : the same on xt_next (the clipped decode of the LAST DDIM step, no further clip) with that
+ *                            step's VJP (inputs xt_in, e) as the epilogue of the adjoint pass: writes g_xt and channels
+ *                            [0, C) of g_e, and zeros channels [C, 2C) when fill_sigma and e_channels == 2C
+ *                            (as nhmc_data_blur2d_vjp).
+ * ---------------------------------------------------------------------------------- */
+int nhmc_sparse_check(const int32_t* host_row_ptr, const int32_t* host_col, int m, int n, int nnz);
+int nhmc_sparse_tiles(int channels, int m);
+size_t nhmc_sparse_tmp_floats(int n_chains, int channels, int m, int n);
+int nhmc_sparse_apply(const float* x, const int32_t* row_ptr, const int32_t* col, const float* val, int rows, int cols,
+                      int nnz, float* out, float* tmp, int n_chains, int channels, nhmc_stream_t stream);
+int nhmc_data_sparse(const float* xt, const float* y, const int32_t* row_ptr, const int32_t* col, const float* val,
+                     const int32_t* t_row_ptr, const int32_t* t_col, const float* t_val, int m, int nnz, int apply_clip,
+                     float* g_xt, double* loss_ws, float* tmp, int n_chains, int channels, int dim, nhmc_stream_t stream);
+int nhmc_data_sparse_vjp(const float* xt_next, const float* y, const int32_t* row_ptr, const int32_t* col,
+                         const float* val, const int32_t* t_row_ptr, const int32_t* t_col, const float* t_val, int m,
+                         int nnz, const float* xt_in, const float* e, int e_channels, const float* at,
+                         const float* at_next, float* g_xt, float* g_e, int fill_sigma, double* loss_ws, float* tmp,
+                         int n_chains, int channels, int dim, nhmc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * a5  Hamiltonian                          main_sampling.py:697,717-718
  *   H = (0.5*Sx + (1/(2 sigma_y^2))*loss) + (0.5*Sp)*m^-1, per chain, in the reference's fp32
  *   op order on fp32-rounded sums; Sx,Sp summed (fixed order, fp64) from the leapfrog partials.

@@ -79,6 +79,12 @@ SIGNATURES = {
     'nhmc_blur2d_apply': (I, [P, P, P, I, I, I, P, I, I, I, P]),
     'nhmc_data_blur2d': (I, [P, P, P, P, I, I, I, P, P, P, I, I, I, P]),
     'nhmc_data_blur2d_vjp': (I, [P, P, P, P, I, I, P, P, I, P, P, P, P, I, P, P, I, I, I, P]),
+    'nhmc_sparse_check': (I, [P, P, I, I, I]),
+    'nhmc_sparse_tiles': (I, [I, I]),
+    'nhmc_sparse_tmp_floats': (SZ, [I, I, I, I]),
+    'nhmc_sparse_apply': (I, [P, P, P, P, I, I, I, P, P, I, I, P]),
+    'nhmc_data_sparse': (I, [P, P, P, P, P, P, P, P, I, I, I, P, P, P, I, I, I, P]),
+    'nhmc_data_sparse_vjp': (I, [P, P, P, P, P, P, P, P, I, I, P, P, I, P, P, P, P, I, P, P, I, I, I, P]),
     'nhmc_hamiltonian': (I, [P, I, P, P, D, P, P, I, P]),
     'nhmc_metropolis': (I, [P, P, P, P, P, P, I, P]),
     'nhmc_schedule_begin': (I, [P, P, P, P, P, P, D, I, I, I, P]),

@@ -22,6 +22,11 @@ term (operators.Deblurring2D).
 from the global torch RNG right after the seed is set, so every rank holds the same one) through the general 2-D blur
 kernels (operators.Blur2D); with `--save_images` rank 0 also writes `blur_kernel.png`, the PSF min-max normalised, once.
 
+`--deg ct<V>` (not in the reference) is sparse-view parallel-beam CT with V views (operators.radon_matrix) through the
+sparse-operator kernels (operators.SparseLinear).  `--deg sparse --operator FILE.npz` samples the posterior of any linear
+forward model: FILE.npz holds a CSR matrix [m, image_size^2] in the layout `scipy.sparse.save_npz` writes (`data`,
+`indices`, `indptr`, `shape`), applied to every channel plane alike; it is read with numpy alone.
+
 `--replicas K` spends the chains on K replica chains per image instead (a batch then holds `--chains` // K images, chain
 i * K + r being replica r of the batch's image i): all replicas see the same measurement, replica 0 starts where the
 single chain starts, replicas r >= 1 start from their own N(0,1) draw keyed by (seed, s, r), and the Philox stream of
@@ -92,6 +97,9 @@ def get_parser(latent=False):
                    help='write the per-image report (PSNR, SSIM, std-map range) as a JSON list to this path')
     p.add_argument('--spectral_projected', action='store_true',
                    help='deblur_aniso / deblur_gauss: residual in the left singular basis, 4 products instead of 8 (rounds differently)')
+    p.add_argument('--operator', type=str, default=None, metavar='FILE.npz',
+                   help='--deg sparse: the forward model as a CSR matrix [m, image_size^2] in the layout scipy.sparse.save_npz '
+                        'writes (data, indices, indptr, shape), applied to every channel plane')
     p.add_argument('--graph', dest='use_graph', action='store_true',
                    help='replay each decode+gradient chunk as a hipGraph (helps single-chain runs: ~1.2x)')
     p.add_argument('--hmc_epochs', type=int, default=60, help='annealing epochs (reference: 60, main_sampling.py:665)')
@@ -260,7 +268,16 @@ def _setup(opt, latent):
     random.seed(opt.seed)
     size, ch = config['data']['image_size'], config['data']['channels']
     # mask = first torch RNG draw, as in the reference
-    op = operators.build_operator(opt.deg, ch, size, device, spectral_projected=opt.spectral_projected or None)
+    operator_file = getattr(opt, 'operator', None)
+    if opt.deg == 'sparse' or operator_file:
+        if opt.deg != 'sparse' or not operator_file:
+            raise SystemExit('--deg sparse and --operator FILE.npz go together')
+        try:
+            op = operators.build_operator(opt.deg, ch, size, device, operator_file=operator_file)
+        except operators.NhmcError as exc:
+            raise SystemExit(str(exc))
+    else:
+        op = operators.build_operator(opt.deg, ch, size, device, spectral_projected=opt.spectral_projected or None)
     if opt.save_images and rank == 0 and isinstance(op, operators.Blur2D):
         k = op.kernel
         span = float(k.max() - k.min())

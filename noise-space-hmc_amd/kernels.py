@@ -836,6 +836,172 @@ def data_blur2d_vjp(xt_next, y, taps, xt, e, at, at_next, g_e_out=None, loss_out
     return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
 
 
+# ---- sparse linear operators (SparseLinear, ct<V>) -----------------------------------------------
+def _is_scipy_like(a):
+    return all(hasattr(a, k) for k in ('tocoo', 'shape')) and not isinstance(a, torch.Tensor)
+
+
+def _coo_of(matrix, shape):
+    """Any accepted matrix form -> (rows int64, cols int64, vals float64, (m, n)), host tensors, entries in any order."""
+    if isinstance(matrix, torch.Tensor):
+        a = matrix.detach().cpu()
+        if a.dim() != 2:
+            raise _lib.NhmcError(f'a sparse operator is a 2-D matrix, got {tuple(a.shape)}')
+        if a.layout == torch.sparse_csr:
+            crow, col, val = a.crow_indices().long(), a.col_indices().long(), a.values()
+            row = torch.repeat_interleave(torch.arange(a.shape[0]), crow[1:] - crow[:-1])
+        elif a.layout == torch.sparse_coo:
+            idx = a._indices() if not a.is_coalesced() else a.indices()
+            val = a._values() if not a.is_coalesced() else a.values()
+            row, col = idx[0].long(), idx[1].long()
+        else:
+            raise _lib.NhmcError('a torch matrix must be sparse COO or sparse CSR (use .to_sparse())')
+        return row, col, val.to(torch.float64), (int(a.shape[0]), int(a.shape[1]))
+    if _is_scipy_like(matrix):                                   # duck-typed: scipy is not a dependency
+        coo = matrix.tocoo()
+        as_t = lambda v, dt: torch.as_tensor(v.astype(dt))
+        return (as_t(coo.row, 'int64'), as_t(coo.col, 'int64'), as_t(coo.data, 'float64'),
+                (int(coo.shape[0]), int(coo.shape[1])))
+    if isinstance(matrix, (tuple, list)) and len(matrix) == 3:
+        if shape is None or len(shape) != 2:
+            raise _lib.NhmcError('the (row_ptr, col, val) form needs shape=(m, n)')
+        m, n = int(shape[0]), int(shape[1])
+        rp, col, val = (torch.as_tensor(v).detach().cpu().reshape(-1) for v in matrix)
+        rp, col = rp.long(), col.long()
+        if m < 1:
+            raise _lib.NhmcError(f'a sparse operator needs at least one row, got m = {m}')
+        if rp.numel() != m + 1 or col.numel() != val.numel():
+            raise _lib.NhmcError(f'(row_ptr, col, val): row_ptr has m + 1 = {m + 1} entries and col as many as val')
+        cnt = rp[1:] - rp[:-1]
+        if int(rp[0]) != 0 or int(rp[-1]) != col.numel() or bool((cnt < 0).any()):
+            raise _lib.NhmcError('(row_ptr, col, val): row_ptr must start at 0, end at nnz and not decrease')
+        row = torch.repeat_interleave(torch.arange(m), cnt)
+        return row, col, val.to(torch.float64), (m, n)
+    raise _lib.NhmcError('a sparse operator is a torch sparse COO / CSR tensor, a scipy.sparse matrix or a triple '
+                         '(row_ptr, col, val) with shape=')
+
+
+def _csr_lists(row, col, val, m):
+    """Entries sorted by (row, col) -> (row_ptr int32 [m + 1], col int32, val float32)."""
+    rp = torch.zeros(m + 1, dtype=torch.int64)
+    rp[1:] = torch.cumsum(torch.bincount(row, minlength=m), 0)
+    return rp.to(torch.int32).contiguous(), col.to(torch.int32).contiguous(), val.contiguous()
+
+
+class SparseMatrix:
+    """The canonical CSR pair of a sparse operator (include/nhmc.h): A [m, n] and A^T, each as (row_ptr int32, col int32,
+    val float32).  Entries sorted by (row, column), duplicates summed in float64 and rounded to fp32, an entry whose fp32
+    value is 0 dropped; A^T by a stable transpose (within its rows the entries ascend by their row in A, same fp32 values).
+    `row_ptr / col / val` and `t_row_ptr / t_col / t_val` are the host copies, `dev` / `t_dev` what the kernels read.  Built
+    and checked once (nhmc_sparse_check on both lists); constructible on 'cpu' (no device copies used)."""
+
+    def __init__(self, matrix, device, shape=None):
+        row, col, val, (m, n) = _coo_of(matrix, shape)
+        if m < 1 or n < 1:
+            raise _lib.NhmcError(f'a sparse operator needs at least one row and one column, got {m} x {n}')
+        if row.numel() and (int(row.min()) < 0 or int(row.max()) >= m):
+            raise _lib.NhmcError(f'a row index lies outside [0, {m})')
+        if col.numel() and (int(col.min()) < 0 or int(col.max()) >= n):
+            raise _lib.NhmcError(f'a column index lies outside [0, {n})')
+        key = row * n + col
+        ukey, inv = torch.unique(key, return_inverse=True)                  # sorted by (row, col)
+        order = torch.argsort(inv, stable=True)                             # duplicates are summed in input order
+        sval = torch.zeros(ukey.numel(), dtype=torch.float64).index_add_(0, inv[order], val[order]).to(torch.float32)
+        keep = sval != 0                                                    # a zero is not an entry (NaN != 0 stays)
+        ukey, sval = ukey[keep], sval[keep]
+        if ukey.numel() < 1:
+            raise _lib.NhmcError('the sparse operator has no non-zero entry')
+        if ukey.numel() >= 2 ** 31:
+            raise _lib.NhmcError('the sparse operator has 2^31 entries or more')
+        self.m, self.n, self.nnz = m, n, int(ukey.numel())
+        r, c = torch.div(ukey, n, rounding_mode='floor'), ukey % n
+        self.row_ptr, self.col, self.val = _csr_lists(r, c, sval, m)
+        t_order = torch.argsort(c, stable=True)                             # stable: rows of A ascend within a row of A^T
+        self.t_row_ptr, self.t_col, self.t_val = _csr_lists(c[t_order], r[t_order], sval[t_order], n)
+        lib = _lib.load()
+        for rp, cl, rows, cols in ((self.row_ptr, self.col, m, n), (self.t_row_ptr, self.t_col, n, m)):
+            rc = lib.nhmc_sparse_check(C.c_void_p(rp.data_ptr()), C.c_void_p(cl.data_ptr()), rows, cols, self.nnz)
+            _lib.check(rc, 'nhmc_sparse_check')
+        self.dev = tuple(t.to(device) for t in (self.row_ptr, self.col, self.val))
+        self.t_dev = tuple(t.to(device) for t in (self.t_row_ptr, self.t_col, self.t_val))
+
+    @staticmethod
+    def _ptrs(lists):
+        return (_p(lists[0], torch.int32, 'row_ptr'), _p(lists[1], torch.int32, 'col'), _p(lists[2], torch.float32, 'val'))
+
+    def args(self, transpose=False):
+        """-> (row_ptr, col, val, rows, cols, nnz) of A, or of A^T."""
+        if transpose:
+            return (*self._ptrs(self.t_dev), self.n, self.m, self.nnz)
+        return (*self._ptrs(self.dev), self.m, self.n, self.nnz)
+
+    def both(self):
+        """-> the six list pointers of the data terms: A, then A^T."""
+        return (*self._ptrs(self.dev), *self._ptrs(self.t_dev))
+
+
+def sparse_tiles(channels, m):
+    return _lib.load().nhmc_sparse_tiles(channels, m)
+
+
+def _sparse_planes(x, cols, what):
+    if x.dim() != 3 or x.shape[2] != cols:
+        raise _lib.NhmcError(f'{what} takes [B, C, {cols}] planes, got {tuple(x.shape)}')
+    return x.shape[0], x.shape[1]
+
+
+def sparse_apply(x, mat, transpose=False):
+    """A x for x [B, C, n] -> [B, C, m], or the exact adjoint A^T x for x [B, C, m] -> [B, C, n]."""
+    lib = _lib.load()
+    rp, cl, vl, rows, cols, nnz = mat.args(transpose)
+    B, Cc = _sparse_planes(x, cols, 'the sparse product')
+    out = torch.empty(B, Cc, rows, dtype=torch.float32, device=x.device)
+    tmp = torch.empty(lib.nhmc_sparse_tmp_floats(B, Cc, mat.m, mat.n), dtype=torch.float32, device=x.device)
+    rc = lib.nhmc_sparse_apply(_p(x, torch.float32, 'x'), rp, cl, vl, rows, cols, nnz, _p(out), _p(tmp), B, Cc, _stream())
+    _lib.check(rc, 'nhmc_sparse_apply')
+    return out
+
+
+def _sparse_io(xt, y, mat):
+    if xt.dim() != 4 or xt.shape[2] != xt.shape[3] or xt.shape[2] * xt.shape[3] != mat.n:
+        raise _lib.NhmcError(f'the sparse operator takes [B, C, d, d] images with d * d = {mat.n}, got {tuple(xt.shape)}')
+    B, Cc, dim = xt.shape[0], xt.shape[1], xt.shape[2]
+    if tuple(y.shape) != (B, Cc, mat.m):
+        raise _lib.NhmcError(f'the sparse observation has the shape {(B, Cc, mat.m)}, got {tuple(y.shape)}')
+    lib = _lib.load()
+    tiles = lib.nhmc_sparse_tiles(Cc, mat.m)
+    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
+    tmp = torch.empty(lib.nhmc_sparse_tmp_floats(B, Cc, mat.m, mat.n), dtype=torch.float32, device=xt.device)
+    return B, Cc, dim, tiles, ws, tmp
+
+
+def data_sparse(xt, y, mat, apply_clip=True, loss_out=None):
+    """-> (loss [B] float64, g_xt) for the sparse operator `mat`; xt [B, C, d, d], y [B, C, m]."""
+    lib = _lib.load()
+    B, Cc, dim, tiles, ws, tmp = _sparse_io(xt, y, mat)
+    g = torch.empty_like(xt)
+    rc = lib.nhmc_data_sparse(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), *mat.both(), mat.m, mat.nnz,
+                              int(apply_clip), _p(g), _p(ws), _p(tmp), B, Cc, dim, _stream())
+    _lib.check(rc, 'nhmc_data_sparse')
+    return sum_partials(ws, tiles, B, out=loss_out), g
+
+
+def data_sparse_vjp(xt_next, y, mat, xt, e, at, at_next, g_e_out=None, loss_out=None):
+    """Sparse data term on the clipped decode `xt_next` + VJP of the last DDIM step (inputs xt, e) in the adjoint pass's
+    epilogue -> (loss [B] float64, g_xt, g_e)."""
+    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
+    lib = _lib.load()
+    if xt_next.shape != xt.shape:
+        raise _lib.NhmcError('xt_next must have the shape of xt')
+    _, _, dim, tiles, ws, tmp = _sparse_io(xt, y, mat)
+    rc = lib.nhmc_data_sparse_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y, torch.float32, 'y'), *mat.both(), mat.m,
+                                  mat.nnz, _p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
+                                  _p(g_xt), _p(g_e, torch.float32, 'g_e'), int(g_e_out is None), _p(ws), _p(tmp), B, Cc, dim,
+                                  _stream())
+    _lib.check(rc, 'nhmc_data_sparse_vjp')
+    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+
+
 # ---- a5-a7 ----------------------------------------------------------------------------------
 def hamiltonian(sums_ws, n_elem, loss, sigma_y, m_inv, want_terms=False, sel=None):
     """sel (int32 [B]): loss is then the gradient cache's loss_pair [2, B] and chain c uses loss[sel[c], c]."""

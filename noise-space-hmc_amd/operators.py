@@ -1,6 +1,6 @@
 """Forward operators with the reference's `H_functions` surface, on the HIP kernels (the linear ones, the two
-nonlinear ones that need nothing from outside: HDR and phase retrieval, and a general 2-D PSF blur, `Blur2D`, which the
-reference does not have).
+nonlinear ones that need nothing from outside: HDR and phase retrieval, and two that the reference does not have: a
+general 2-D PSF blur, `Blur2D`, and any linear operator given as a sparse matrix, `SparseLinear`).
 
 Mirrors obs_functions/Hfuncs.py for the three operators on the HMC hot path -- same constructor
 arguments, same `H / Ht / H_pinv / is_linear`, inputs `[B, ...]`, outputs `[B, flat]` -- but each
@@ -14,6 +14,7 @@ reference's O(N*M) Python list comprehension (Hfuncs.py:125) -- and stay residen
 """
 import math
 import os
+import warnings
 
 import torch
 
@@ -656,6 +657,117 @@ def motion_kernel_points(size):
     return 1 if size == 1 else 2 * size + 1
 
 
+class SparseLinear(H_functions):
+    """Any linear forward model given as a sparse matrix A [m, img_dim^2] (tomography, spatially varying blur, irregular
+    sampling, mosaics): H = A x per channel plane, H^T the exact adjoint on the transposed list; M = C m.  Not in the
+    reference.  `matrix` is a torch sparse COO or CSR tensor, a scipy.sparse matrix (duck-typed: scipy is not a dependency)
+    or a triple (row_ptr, col, val) with shape=(m, n); it is canonicalised once on the host (include/nhmc.h) and both
+    lists stay resident on the device."""
+
+    def __init__(self, matrix, channels, img_dim, device, shape=None):
+        self.channels, self.img_dim, self.device = channels, img_dim, device
+        if img_dim % 4:
+            raise NhmcError('the sparse operator needs img_dim % 4 == 0')
+        self._mat = K.SparseMatrix(matrix, device, shape=shape)
+        if self._mat.n != img_dim ** 2:
+            raise NhmcError(f'the sparse operator has {self._mat.n} columns, the image has img_dim^2 = {img_dim ** 2} pixels')
+        self.m = self._mat.m
+        self.M = channels * self.m
+
+    def csr(self, transpose=False):
+        """The canonical host lists -> (row_ptr int32 [m + 1], col int32 [nnz], val float32 [nnz]) of A, or of A^T."""
+        a = self._mat
+        return (a.t_row_ptr, a.t_col, a.t_val) if transpose else (a.row_ptr, a.col, a.val)
+
+    def H(self, vec):
+        x = vec.reshape(vec.shape[0], self.channels, self.img_dim ** 2).contiguous()
+        return K.sparse_apply(x, self._mat).reshape(x.shape[0], -1)
+
+    def Ht(self, vec):
+        y = vec.reshape(vec.shape[0], self.channels, self.m).contiguous()
+        return K.sparse_apply(y, self._mat, transpose=True).reshape(y.shape[0], -1)
+
+    def H_pinv(self, vec):
+        raise NotImplementedError('a general sparse operator has no closed-form pseudo-inverse here; no sampler calls H_pinv')
+
+    def _obs(self, y, B):
+        y = y.reshape(B, self.channels, self.m)
+        return y if y.is_contiguous() else y.contiguous()
+
+    def data_term(self, xt, y, apply_clip=True, loss_out=None):
+        return K.data_sparse(xt, self._obs(y, xt.shape[0]), self._mat, apply_clip, loss_out=loss_out)
+
+    fused_wants_decode = True              # the engine hands over the clipped decode it already holds
+
+    def fused_last_vjp(self, xt_in, e, at, at_next, y, g_e_out=None, xt_next=None, loss_out=None):
+        """Data term + VJP of the last DDIM step (the adjoint pass's epilogue) -> (loss, g_xt, g_e)."""
+        if xt_next is None:
+            xt_next = K.ddim_mix_fwd(xt_in, e, at, at_next, final_clip=True)['xt_next']
+        return K.data_sparse_vjp(xt_next, self._obs(y, xt_in.shape[0]), self._mat, xt_in, e, at, at_next, g_e_out=g_e_out,
+                                 loss_out=loss_out)
+
+
+def radon_matrix(img_dim, n_views):
+    """Sparse-view parallel-beam CT as a torch sparse CSR [V D, d^2] (fp32 values computed in float64), our own
+    construction: pixel-driven, linear splat.  d = img_dim, D = 2 ceil(d / sqrt(2)) + 3 bins per view, c = (d - 1) / 2;
+    pixel (r, s) sits at (x, y) = (s - c, c - r); theta_v = pi v / V; u = x cos(theta_v) + y sin(theta_v) + (D - 1) / 2,
+    i0 = floor(u), f = u - i0: row v D + i0 gets (1 - f) / d and row v D + i0 + 1 gets f / d in column r d + s.  The 1 / d
+    keeps y on the image's scale."""
+    d, V = int(img_dim), int(n_views)
+    if d < 1 or V < 1:
+        raise NhmcError(f'radon_matrix: img_dim and n_views must be positive, got {img_dim}, {n_views}')
+    D = 2 * math.ceil(d / math.sqrt(2.0)) + 3
+    c = (d - 1) / 2
+    r = torch.arange(d, dtype=torch.float64)
+    x = (r - c)[None, :].expand(d, d).reshape(-1)                       # s - c
+    y = (c - r)[:, None].expand(d, d).reshape(-1)                       # c - r
+    pix = torch.arange(d * d, dtype=torch.int64)
+    rows, cols, vals = [], [], []
+    for v in range(V):
+        theta = math.pi * v / V
+        u = x * math.cos(theta) + y * math.sin(theta) + (D - 1) / 2
+        i0 = torch.floor(u)
+        f = u - i0
+        i0 = i0.long() + v * D
+        rows += [i0, i0 + 1]
+        cols += [pix, pix]
+        vals += [(1 - f) / d, f / d]
+    rows, cols, vals = torch.cat(rows), torch.cat(cols), torch.cat(vals).to(torch.float32)
+    keep = vals != 0                                                    # f = 0 on a bin centre: a zero is not an entry
+    order = torch.argsort(rows[keep] * (d * d) + cols[keep], stable=True)
+    rows, cols, vals = rows[keep][order], cols[keep][order], vals[keep][order]
+    crow = torch.zeros(V * D + 1, dtype=torch.int64)
+    crow[1:] = torch.cumsum(torch.bincount(rows, minlength=V * D), 0)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', UserWarning)                    # torch announces sparse CSR as beta on first use
+        return torch.sparse_csr_tensor(crow, cols, vals, size=(V * D, d * d))
+
+
+def load_sparse_npz(path):
+    """A CSR matrix in the layout scipy.sparse.save_npz writes (data, indices, indptr, shape [, format = 'csr']), read with
+    numpy alone -> ((row_ptr, col, val), (m, n)) for SparseLinear's triple form."""
+    import numpy as np
+    if not os.path.isfile(path):
+        raise NhmcError(f'--operator: no such file: {path}')
+    try:
+        z = np.load(path, allow_pickle=False)
+        names = set(z.files)
+    except Exception as exc:
+        raise NhmcError(f'--operator: {path} is not an .npz archive ({exc})') from exc
+    missing = {'data', 'indices', 'indptr', 'shape'} - names
+    if missing:
+        raise NhmcError(f'--operator: {path} lacks {sorted(missing)}: expected what scipy.sparse.save_npz writes for CSR')
+    fmt = z['format'].item() if 'format' in names else 'csr'
+    fmt = fmt.decode() if isinstance(fmt, bytes) else str(fmt)
+    if fmt != 'csr':
+        raise NhmcError(f'--operator: {path} holds a {fmt!r} matrix; save it as CSR (scipy.sparse.csr_matrix)')
+    shape = tuple(int(v) for v in z['shape'])
+    if len(shape) != 2:
+        raise NhmcError(f'--operator: {path}: shape {shape} is not 2-D')
+    triple = tuple(torch.from_numpy(np.ascontiguousarray(z[k])) for k in ('indptr', 'indices', 'data'))
+    return triple, shape
+
+
 def bicubic_taps(factor, a=-0.5):
     """main_sampling.py:266-279."""
     def w(x):
@@ -677,9 +789,10 @@ def gaussian_taps(sigma, half=4):
     return k / k.sum()
 
 
-def build_operator(deg, channels, img_dim, device, generator=None, spectral_projected=None):
+def build_operator(deg, channels, img_dim, device, generator=None, spectral_projected=None, operator_file=None):
     """`prepare_measurement` (main_sampling.py:261-351) for the degradations on the HMC hot path.
-    spectral_projected: the four-product data term of the two blur operators (see Deblurring2D)."""
+    spectral_projected: the four-product data term of the two blur operators (see Deblurring2D).
+    operator_file: the CSR .npz of `sparse` (load_sparse_npz)."""
     if deg.startswith('sr_bicubic') and deg[10:].isdigit():
         factor = int(deg[10:])
         return SRConv(bicubic_taps(factor), channels, img_dim, device, stride=factor)
@@ -710,4 +823,15 @@ def build_operator(deg, channels, img_dim, device, generator=None, spectral_proj
         return Colorization(img_dim, device)
     if deg.startswith('cs') and deg[2:].isdigit():
         return WalshHadamardCS(channels, img_dim, int(deg[2:]), torch.randperm(img_dim ** 2, generator=generator), device)
+    if deg.startswith('ct') and deg[2:].isdigit():                      # not in the reference: sparse-view parallel-beam CT
+        if int(deg[2:]) < 1:
+            raise NhmcError('ct<V> needs at least one view')
+        return SparseLinear(radon_matrix(img_dim, int(deg[2:])), channels, img_dim, device)
+    if deg == 'sparse':                                                 # any linear operator, as a CSR .npz
+        if not operator_file:
+            raise NhmcError('--deg sparse needs --operator FILE.npz (a CSR matrix as scipy.sparse.save_npz writes it)')
+        triple, shape = load_sparse_npz(operator_file)
+        if shape[1] != img_dim ** 2:
+            raise NhmcError(f'--operator: {operator_file} has {shape[1]} columns, the image has {img_dim}^2 = {img_dim ** 2} pixels')
+        return SparseLinear(triple, channels, img_dim, device, shape=shape)
     raise NotImplementedError(f'degradation {deg!r} is outside the HMC hot path of this build')

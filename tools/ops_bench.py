@@ -109,3 +109,54 @@ for name, psf in (('deblur_motion sparse', operators.motion_kernel(61, 0.5, gen)
     print(f'{name} (T = {Tn}) B={B}: H {msH*1e3:.1f} us ({fma/msH/1e9:.2f} T FMA/s, {100*fma/msH/1e9/19.7:.0f}% of the LDS bound), '
           f'torch conv2d {msHt*1e3:.1f} us;  data term {msD*1e3:.1f} us ({2*fma/msD/1e9:.2f} T FMA/s, '
           f'{100*2*fma/msD/1e9/19.7:.0f}%), torch autograd {msDt*1e3:.1f} us;  data term + last VJP {msV*1e3:.1f} us')
+# sparse linear operators (operators.SparseLinear): ct32 = sparse-view parallel-beam CT, 32 views, m = 11 744 rows,
+# 4 193 792 entries.  10 warm-up calls, then 100 timed ones between two events.  Yardstick in the same process:
+# torch.sparse.mm on the CSR tensor over the plane-minor operand [n, P] (handed to it ready-made: it pays no transposes)
+# and autograd for the gradient; if this torch build does not serve that on the device, the dense product at 64 x 64.
+# Row reads of one product pass: nnz rows of 4 P bytes, against the 8.6 TB/s measured for index-gathered ~1 KiB rows.
+def timeit100(f):
+    for _ in range(10): f()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(100): f()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / 100
+oct = operators.build_operator('ct32', 3, 256, dev)
+Pn = B * 3
+nnz = oct.csr()[2].numel()
+yc = K.randn_philox((B, oct.M), 1, 0, 4)
+msH, msHt = timeit100(lambda: oct.H(x)), timeit100(lambda: oct.Ht(yc))
+msD = timeit100(lambda: oct.data_term(x, yc, True))
+msV = timeit100(lambda: oct.fused_last_vjp(x, e6, at, an, yc, g_e_out=ge, xt_next=cur))
+gather = nnz * 4 * Pn
+print(f'ct32 (m = {oct.m}, nnz = {nnz}) B={B}: H {msH*1e3:.1f} us, Ht {msHt*1e3:.1f} us, data term {msD*1e3:.1f} us, '
+      f'data term + last VJP {msV*1e3:.1f} us;  row reads {gather/1e9:.2f} GB per product: two products over '
+      f'the whole time of the data term = {2*gather/msD/1e9:.2f} TB/s of row reads (gather figure: 8.6 TB/s)')
+try:
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', UserWarning)
+        Acsr = operators.radon_matrix(256, 32).to(dev)
+    xm = x.reshape(Pn, -1).t().contiguous()                      # [n, P]
+    ym = yc.reshape(Pn, -1).t().contiguous()                     # [m, P]
+    def torch_H():
+        return torch.sparse.mm(Acsr, xm)
+    def torch_data():
+        xl = xm.detach().requires_grad_(True)
+        loss = ((ym - torch.sparse.mm(Acsr, xl.clamp(-1, 1))) ** 2).sum()
+        return torch.autograd.grad(loss, xl)
+    tH, tD = timeit100(torch_H), timeit100(torch_data)
+    print(f'    torch.sparse.mm CSR [n, P] B={B}: H {tH*1e3:.1f} us ({tH/msH:.2f} x ours), data term by autograd {tD*1e3:.1f} us '
+          f'({tD/msD:.2f} x ours)')
+except Exception as exc:                                         # say so, and measure the dense product at 64 x 64 instead
+    print(f'    torch.sparse.mm on a CSR tensor with autograd is not served on this device: {type(exc).__name__}: {exc}')
+    o64 = operators.build_operator('ct32', 3, 64, dev)
+    x64, y64 = torch.randn(B, 3, 64, 64, device=dev), torch.randn(B, o64.M, device=dev)
+    A64 = operators.radon_matrix(64, 32).to_dense().to(dev)
+    def dense_data():
+        xl = x64.reshape(Pn, -1).detach().requires_grad_(True)
+        loss = ((y64.reshape(Pn, -1) - xl.clamp(-1, 1) @ A64.t()) ** 2).sum()
+        return torch.autograd.grad(loss, xl)
+    m64, t64 = timeit100(lambda: o64.data_term(x64, y64, True)), timeit100(dense_data)
+    print(f'    ct32 at 64 x 64 B={B}: data term {m64*1e3:.1f} us, torch dense product + autograd {t64*1e3:.1f} us ({t64/m64:.2f} x ours)')
