@@ -19,14 +19,16 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _p(t, dtype=None, name='tensor'):
+def _p(t, dtype=None, name='tensor', contiguous=True):
+    """The checked pointer of an operand (None -> null).  contiguous=False: a strided view whose strides the caller has
+    checked and hands to the library."""
     if t is None:
         return C.c_void_p(0)
     if not t.is_cuda:
         raise _lib.NhmcError(f'{name} must live on the GPU (got {t.device}); libnhmc has no CPU path')
     if dtype is not None and t.dtype != dtype:
         raise _lib.NhmcError(f'{name} must be {dtype}, got {t.dtype}')
-    if not t.is_contiguous():
+    if not t.is_contiguous() and contiguous:
         raise _lib.NhmcError(f'{name} must be contiguous')
     return C.c_void_p(t.data_ptr())
 
@@ -52,6 +54,13 @@ def leapfrog_tiles(n_elem):
 
 def leapfrog_ws(n_chains, n_elem, device):
     return torch.empty(n_chains * leapfrog_tiles(n_elem) * 2, dtype=torch.float64, device=device)
+
+
+def _sums_ws(sums_ws, B, N):
+    """The checked pointer of a leapfrog sums workspace (leapfrog_ws(B, N, device))."""
+    if sums_ws is None or sums_ws.numel() < B * leapfrog_tiles(N) * 2:
+        raise _lib.NhmcError('sums_ws missing or too small')
+    return _p(sums_ws, torch.float64, 'sums_ws')
 
 
 def leapfrog_fused(mode, x, p, g, eps, sigma_y, m_inv, sums_ws=None, g2=None):
@@ -81,40 +90,42 @@ def leapfrog_first(x_in, x_out, p, g, eps, sigma_y, m_inv, sums_ws, g2=None):
     if x_out.data_ptr() == x_in.data_ptr():
         raise _lib.NhmcError('leapfrog_first is out of place: x_out must not alias x_in')
     eps, sigma_y = _f64(eps, B, x_in.device), _f64(sigma_y, B, x_in.device)
-    if sums_ws is None or sums_ws.numel() < B * leapfrog_tiles(N) * 2:
-        raise _lib.NhmcError('sums_ws missing or too small')
     rc = lib.nhmc_leapfrog_first(_p(x_in, torch.float32, 'x_in'), _p(x_out, torch.float32, 'x_out'), _p(p, torch.float32, 'p'),
                                  _p(g, torch.float32, 'g'), _p(g2, torch.float32, 'g2'), _p(eps, torch.float64, 'eps'),
-                                 _p(sigma_y, torch.float64, 'sigma_y'), float(m_inv), B, N,
-                                 _p(sums_ws, torch.float64, 'sums_ws'), _stream())
+                                 _p(sigma_y, torch.float64, 'sigma_y'), float(m_inv), B, N, _sums_ws(sums_ws, B, N), _stream())
     _lib.check(rc, 'nhmc_leapfrog_first')
 
 
 # ---- gradient cache (nhmc.h "Gradient cache") -------------------------------------------------
-def _cache_args(g_pair, loss_pair, sel, B, N):
-    """g_pair: a [2, B_total, ...] float32 tensor or a [:, lo:hi] view of one; loss_pair [2, B_total] float64 likewise;
-    sel int32 [B].  -> (pair_stride, loss_stride) in elements."""
+def _g_pair(g_pair, sel, B, N):
+    """g_pair: a [2, B_total, ...] float32 tensor or a [:, lo:hi] view of one; sel int32 [B].
+    -> (g_pair pointer, sel pointer, pair_stride in elements)"""
     if g_pair.dim() < 2 or g_pair.shape[0] != 2 or g_pair.shape[1] != B or g_pair[0, 0].numel() != N:
         raise _lib.NhmcError(f'g_pair must be [2, {B}, ...] with {N} elements per chain, got {tuple(g_pair.shape)}')
-    if not g_pair[0].is_contiguous() or g_pair.dtype != torch.float32 or not g_pair.is_cuda:
-        raise _lib.NhmcError('g_pair: float32 on the GPU, each slot contiguous')
-    if loss_pair.shape != (2, B) or loss_pair.dtype != torch.float64 or loss_pair.stride(1) != 1:
-        raise _lib.NhmcError('loss_pair must be float64 [2, n_chains] (or a [:, lo:hi] view)')
-    if sel.dtype != torch.int32 or sel.numel() != B or not sel.is_contiguous():
+    if not g_pair[0].is_contiguous():
+        raise _lib.NhmcError('g_pair: each slot must be contiguous')
+    if sel.numel() != B:
         raise _lib.NhmcError('sel must be int32 [n_chains]')
-    return g_pair.stride(0), loss_pair.stride(0)
+    return _p(g_pair, torch.float32, 'g_pair', contiguous=False), _p(sel, torch.int32, 'sel'), g_pair.stride(0)
+
+
+def _loss_pair(loss_pair, B):
+    """loss_pair: float64 [2, B_total] or a [:, lo:hi] view of one -> (pointer, stride in elements)"""
+    if loss_pair.shape != (2, B) or loss_pair.stride(1) != 1:
+        raise _lib.NhmcError('loss_pair must be float64 [2, n_chains] (or a [:, lo:hi] view)')
+    return _p(loss_pair, torch.float64, 'loss_pair', contiguous=False), loss_pair.stride(0)
 
 
 def grad_cache_store(g, g2, loss, g_pair, loss_pair, sel, flip=0):
     """slot (sel ^ flip) of every chain <- (g + g2, loss)"""
     lib = _lib.load()
     B, N = _chains_elems(g)
-    ps, ls = _cache_args(g_pair, loss_pair, sel, B, N)
+    gp, sp, ps = _g_pair(g_pair, sel, B, N)
+    lp, ls = _loss_pair(loss_pair, B)
     if g2 is not None and g2.shape != g.shape:
         raise _lib.NhmcError('g and g2 must have the same shape')
     rc = lib.nhmc_grad_cache_store(_p(g, torch.float32, 'g'), _p(g2, torch.float32, 'g2'), _p(loss, torch.float64, 'loss'),
-                                   C.c_void_p(g_pair.data_ptr()), C.c_void_p(loss_pair.data_ptr()), _p(sel, torch.int32),
-                                   int(flip), ps, ls, B, N, _stream())
+                                   gp, lp, sp, int(flip), ps, ls, B, N, _stream())
     _lib.check(rc, 'nhmc_grad_cache_store')
 
 
@@ -124,16 +135,11 @@ def leapfrog_first_cached(x_in, x_out, p, g_pair, sel, eps, sigma_y, m_inv, sums
     B, N = _chains_elems(x_in)
     if x_out.shape != x_in.shape or p.shape != x_in.shape:
         raise _lib.NhmcError('x_in, x_out, p must have the same shape')
-    if g_pair.dim() < 2 or g_pair.shape[0] != 2 or g_pair.shape[1] != B or g_pair[0, 0].numel() != N or \
-            not g_pair[0].is_contiguous() or sel.numel() != B:
-        raise _lib.NhmcError('g_pair must be [2, n_chains, ...] like x, sel int32 [n_chains]')
+    gp, sp, ps = _g_pair(g_pair, sel, B, N)
     eps, sigma_y = _f64(eps, B, x_in.device), _f64(sigma_y, B, x_in.device)
-    if sums_ws is None or sums_ws.numel() < B * leapfrog_tiles(N) * 2:
-        raise _lib.NhmcError('sums_ws missing or too small')
     rc = lib.nhmc_leapfrog_first_cached(_p(x_in, torch.float32, 'x_in'), _p(x_out, torch.float32, 'x_out'),
-                                        _p(p, torch.float32, 'p'), C.c_void_p(g_pair.data_ptr()), _p(sel, torch.int32, 'sel'),
-                                        g_pair.stride(0), _p(eps, torch.float64), _p(sigma_y, torch.float64), float(m_inv),
-                                        B, N, _p(sums_ws, torch.float64), _stream())
+                                        _p(p, torch.float32, 'p'), gp, sp, ps, _p(eps, torch.float64), _p(sigma_y, torch.float64),
+                                        float(m_inv), B, N, _sums_ws(sums_ws, B, N), _stream())
     _lib.check(rc, 'nhmc_leapfrog_first_cached')
 
 
@@ -143,17 +149,15 @@ def leapfrog_last_cached(x, p, g, g2, g_pair, loss_pair, sel, loss, eps, sigma_y
     B, N = _chains_elems(x)
     if p.shape != x.shape or g.shape != x.shape or (g2 is not None and g2.shape != x.shape):
         raise _lib.NhmcError('x, p, g (and g2) must have the same shape')
-    ps, ls = _cache_args(g_pair, loss_pair, sel, B, N)
+    gp, sp, ps = _g_pair(g_pair, sel, B, N)
+    lp, ls = _loss_pair(loss_pair, B)
     eps, sigma_y = _f64(eps, B, x.device), _f64(sigma_y, B, x.device)
-    if sums_ws is None or sums_ws.numel() < B * leapfrog_tiles(N) * 2:
-        raise _lib.NhmcError('sums_ws missing or too small')
     if loss.numel() != B:
         raise _lib.NhmcError('loss must have one entry per chain')
     rc = lib.nhmc_leapfrog_last_cached(_p(x, torch.float32, 'x'), _p(p, torch.float32, 'p'), _p(g, torch.float32, 'g'),
-                                       _p(g2, torch.float32, 'g2'), C.c_void_p(g_pair.data_ptr()), _p(sel, torch.int32),
-                                       ps, _p(loss, torch.float64, 'loss'), C.c_void_p(loss_pair.data_ptr()), ls,
+                                       _p(g2, torch.float32, 'g2'), gp, sp, ps, _p(loss, torch.float64, 'loss'), lp, ls,
                                        _p(eps, torch.float64), _p(sigma_y, torch.float64), float(m_inv), B, N,
-                                       _p(sums_ws, torch.float64), _stream())
+                                       _sums_ws(sums_ws, B, N), _stream())
     _lib.check(rc, 'nhmc_leapfrog_last_cached')
 
 
@@ -184,17 +188,23 @@ def _alpha(a, B, device):
 
 
 def _last_vjp_io(xt, e, at, at_next, g_e_out, fills_sigma):
-    """What every fused "data term + last DDIM-step VJP" wrapper starts with -> (B, C, hw, e_channels, at, at_next, g_xt, g_e).
+    """What every fused "data term + last DDIM-step VJP" wrapper starts with -> (dims, mix, grads, outs, alphas):
+        dims    (B, C, hw): the chunk's chains, channels and pixels per plane
+        mix     the five mix arguments in ABI order: xt, e, e_channels, at, at_next
+        grads   the gradient outputs in ABI order: g_xt, g_e (and fill_sigma when the entry takes it)
+        outs    (g_xt, g_e): the tensors behind `grads`, which the wrapper returns after its loss
+        alphas  the alpha-bar arrays behind `mix`: the caller holds them until after its launch call (see ddim_map_back)
     fills_sigma: the kernel zero-fills the learned-sigma half of a fresh g_e itself (its fill_sigma argument); the others
-    write channels [0, C) only and get a zeroed one.  A caller's g_e_out is checked before anything is allocated or launched.
-    The callers hold the alpha-bar arrays until after their launch call (see ddim_map_back)."""
+    write channels [0, C) only and get a zeroed one.  A caller's g_e_out is checked before anything is allocated or launched."""
     B, Cc, hw, ec = _mix_shapes(xt, e)
     if g_e_out is not None and g_e_out.shape != e.shape:
         raise _lib.NhmcError(f'g_e_out must have the shape of the score output {tuple(e.shape)}, got {tuple(g_e_out.shape)}')
     at, at_next = _alpha(at, B, xt.device), _alpha(at_next, B, xt.device)
+    mix = (_p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next))
     g_xt = torch.empty_like(xt)
     g_e = g_e_out if g_e_out is not None else (torch.empty_like(e) if fills_sigma else torch.zeros_like(e))
-    return B, Cc, hw, ec, at, at_next, g_xt, g_e
+    grads = (_p(g_xt), _p(g_e, torch.float32, 'g_e'), int(g_e_out is None)) if fills_sigma else (_p(g_xt), _p(g_e, torch.float32, 'g_e'))
+    return (B, Cc, hw), mix, grads, (g_xt, g_e), (at, at_next)
 
 
 def ddim_mix_fwd(xt, e, at, at_next, final_clip=False, want=('xt_next',), out=None):
@@ -243,48 +253,51 @@ def ddim_mix_bwd(gout, xt, e, at, at_next, final_clip=False, gout2=None, g_x0=No
 
 def ddim_mix_bwd_inpaint(xt, e, at, at_next, y, slot, g_e_out=None, loss_out=None):
     """Last-step VJP fused with the inpainting data term -> (loss [B] float64, g_xt, g_e)."""
-    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
-    lib = _lib.load()
-    tiles = leapfrog_tiles(Cc * hw)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    rc = lib.nhmc_ddim_mix_bwd_inpaint(_p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
-                                       _p(y, torch.float32, 'y'), _p(slot, torch.int32, 'slot'), y.shape[1], _p(g_xt),
-                                       _p(g_e), int(g_e_out is None), _p(ws), B, Cc, hw, _stream())
-    _lib.check(rc, 'nhmc_ddim_mix_bwd_inpaint')
-    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+    dims, mix, grads, outs, alphas = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
+    loss = _two_pass('nhmc_ddim_mix_bwd_inpaint', leapfrog_tiles(dims[1] * dims[2]), dims[0], xt.device, loss_out,
+                     (*mix, _p(y, torch.float32, 'y'), _p(slot, torch.int32, 'slot'), y.shape[1], *grads), dims)
+    return (loss, *outs)
 
 
 def ddim_mix_bwd_inpaint_px(xt, e, at, at_next, y, mask_words, prefix, g_e_out=None, loss_out=None):
     """Whole-pixel-mask form of ddim_mix_bwd_inpaint: bit mask + prefix counts instead of the dense slot map."""
-    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
+    (B, Cc, hw), mix, grads, (g_xt, g_e), alphas = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
+    # _two_pass written out: the flagship's per-step wrapper, and at one chain per call the step is launch-bound
     lib = _lib.load()
     tiles = lib.nhmc_inpaint_px_tiles(Cc, hw)
     ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    rc = lib.nhmc_ddim_mix_bwd_inpaint_px(_p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
-                                          _p(y, torch.float32, 'y'), _p(mask_words, torch.int32, 'mask_words'),
-                                          _p(prefix, torch.int32, 'prefix'), y.shape[1], _p(g_xt), _p(g_e),
-                                          int(g_e_out is None), _p(ws), B, Cc, hw, _stream())
+    rc = lib.nhmc_ddim_mix_bwd_inpaint_px(*mix, _p(y, torch.float32, 'y'), _p(mask_words, torch.int32, 'mask_words'),
+                                          _p(prefix, torch.int32, 'prefix'), y.shape[1], *grads, _p(ws), B, Cc, hw, _stream())
     _lib.check(rc, 'nhmc_ddim_mix_bwd_inpaint_px')
     return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
 
 
+def _square(xt):
+    if xt.shape[3] != xt.shape[2]:
+        raise _lib.NhmcError('square images only')
+    return xt.shape[0], xt.shape[1], xt.shape[2]
+
+
 def ddim_mix_bwd_sr(xt, e, at, at_next, y, ratio, g_e_out=None, loss_out=None):
     """Last-step VJP fused with the super-resolution data term -> (loss [B] float64, g_xt, g_e)."""
-    dim = xt.shape[2]
-    if xt.shape[3] != dim:
-        raise _lib.NhmcError('square images only')
-    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
-    lib = _lib.load()
-    tiles = lib.nhmc_sr_vjp_tiles(Cc, dim, ratio)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    rc = lib.nhmc_ddim_mix_bwd_sr(_p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
-                                  _p(y, torch.float32, 'y'), ratio, _p(g_xt), _p(g_e), _p(ws), B, Cc, dim, _stream())
-    _lib.check(rc, 'nhmc_ddim_mix_bwd_sr')
-    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+    B, Cc, dim = _square(xt)
+    _, mix, grads, outs, alphas = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
+    loss = _two_pass('nhmc_ddim_mix_bwd_sr', _lib.load().nhmc_sr_vjp_tiles(Cc, dim, ratio), B, xt.device, loss_out,
+                     (*mix, _p(y, torch.float32, 'y'), ratio, *grads), (B, Cc, dim))
+    return (loss, *outs)
 
 
 # ---- a12-a15 --------------------------------------------------------------------------------
 NO_LOSS = object()      # pass as loss_out: the per-chain loss is not wanted (a MID leapfrog step uses only the gradient)
+
+
+def _two_pass(entry, tiles, n_chains, device, loss_out, before, after):
+    """The two-pass loss every data-term entry shares: `entry(*before, partials, *after, stream)` leaves `tiles` float64
+    partials per chain, which sum_partials adds into loss_out -> the loss [n_chains] (None under NO_LOSS).  The caller
+    holds the tensors behind the pointers in `before` / `after` until this returns."""
+    ws = torch.empty(n_chains * tiles, dtype=torch.float64, device=device)
+    _lib.check(getattr(_lib.load(), entry)(*before, _p(ws), *after, _stream()), entry)
+    return sum_partials(ws, tiles, n_chains, out=loss_out)
 
 
 def sum_partials(ws, tiles, n_chains, stride=1, offset=0, out=None):
@@ -305,18 +318,15 @@ def sum_partials(ws, tiles, n_chains, stride=1, offset=0, out=None):
 
 def data_inpaint(xt, y, slot, apply_clip=True, loss_out=None):
     """-> (loss [B] float64, g_xt).  slot: int32 [N] CHW map into y (-1 = masked)."""
-    lib = _lib.load()
     B, N = _chains_elems(xt)
     M = y.shape[1]
     if slot.numel() != N or y.shape[0] != B:
         raise _lib.NhmcError('slot / y shape mismatch')
-    tiles = lib.nhmc_data_tiles(N)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
     g = torch.empty_like(xt)
-    rc = lib.nhmc_data_inpaint(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), _p(slot, torch.int32, 'slot'),
-                               int(apply_clip), _p(g), _p(ws), B, N, M, _stream())
-    _lib.check(rc, 'nhmc_data_inpaint')
-    return sum_partials(ws, tiles, B, out=loss_out), g
+    loss = _two_pass('nhmc_data_inpaint', _lib.load().nhmc_data_tiles(N), B, xt.device, loss_out,
+                     (_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), _p(slot, torch.int32, 'slot'), int(apply_clip), _p(g)),
+                     (B, N, M))
+    return loss, g
 
 
 def inpaint_H(x, kept_chw):
@@ -339,17 +349,11 @@ def inpaint_Ht(y, slot, n_elem):
 
 
 def data_sr(xt, y, ratio, apply_clip=True, loss_out=None):
-    lib = _lib.load()
-    B, Cc, dim = xt.shape[0], xt.shape[1], xt.shape[2]
-    if xt.shape[3] != dim:
-        raise _lib.NhmcError('square images only')
-    tiles = lib.nhmc_sr_tiles(Cc, dim, ratio)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
+    B, Cc, dim = _square(xt)
     g = torch.empty_like(xt)
-    rc = lib.nhmc_data_sr(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), ratio, int(apply_clip), _p(g),
-                          _p(ws), B, Cc, dim, _stream())
-    _lib.check(rc, 'nhmc_data_sr')
-    return sum_partials(ws, tiles, B, out=loss_out), g
+    loss = _two_pass('nhmc_data_sr', _lib.load().nhmc_sr_tiles(Cc, dim, ratio), B, xt.device, loss_out,
+                     (_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), ratio, int(apply_clip), _p(g)), (B, Cc, dim))
+    return loss, g
 
 
 def sr_H(x, ratio):
@@ -379,29 +383,21 @@ def _host_w(w, channels):
 
 def data_color(xt, y, w, apply_clip=True, loss_out=None):
     """w: host sequence [V[0,0] .. V[C-1,0], s, U[0,0]] of the grey row's SVD -> (loss [B] float64, g_xt)"""
-    lib = _lib.load()
     B, Cc, hw = xt.shape[0], xt.shape[1], xt[0, 0].numel()
-    tiles = lib.nhmc_color_tiles(hw)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
     g = torch.empty_like(xt)
     wp, keep = _host_w(w, Cc)
-    rc = lib.nhmc_data_color(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), wp, int(apply_clip), _p(g), _p(ws),
-                             B, Cc, hw, _stream())
-    _lib.check(rc, 'nhmc_data_color')
-    return sum_partials(ws, tiles, B, out=loss_out), g
+    loss = _two_pass('nhmc_data_color', _lib.load().nhmc_color_tiles(hw), B, xt.device, loss_out,
+                     (_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), wp, int(apply_clip), _p(g)), (B, Cc, hw))
+    return loss, g
 
 
 def ddim_mix_bwd_color(xt, e, at, at_next, y, w, g_e_out=None, loss_out=None):
     """Last-step VJP fused with the colorization data term -> (loss [B] float64, g_xt, g_e)."""
-    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
-    lib = _lib.load()
-    tiles = lib.nhmc_color_tiles(hw)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    wp, keep = _host_w(w, Cc)
-    rc = lib.nhmc_ddim_mix_bwd_color(_p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
-                                     _p(y, torch.float32, 'y'), wp, _p(g_xt), _p(g_e), _p(ws), B, Cc, hw, _stream())
-    _lib.check(rc, 'nhmc_ddim_mix_bwd_color')
-    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+    dims, mix, grads, outs, alphas = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
+    wp, keep = _host_w(w, dims[1])
+    loss = _two_pass('nhmc_ddim_mix_bwd_color', _lib.load().nhmc_color_tiles(dims[2]), dims[0], xt.device, loss_out,
+                     (*mix, _p(y, torch.float32, 'y'), wp, *grads), dims)
+    return (loss, *outs)
 
 
 def color_H(x, w):
@@ -442,42 +438,34 @@ def cs_Ht(y, kslot, channels, dim):
     return x.reshape(B, -1)
 
 
-def _cs_tmp(xt, dim):
-    return torch.empty((1 if dim == 256 else 2,) + tuple(xt.shape), dtype=torch.float32, device=xt.device)
+def _cs_io(xt, y_spec):
+    """What data_cs and data_cs_vjp share -> (B, C, dim, tiles, tmp) after the shape check."""
+    B, Cc, dim = xt.shape[0], xt.shape[1], xt.shape[2]
+    if y_spec.numel() != xt.numel():
+        raise _lib.NhmcError('data_cs: y_spec must have one entry per image element (spectrum layout)')
+    tmp = torch.empty((1 if dim == 256 else 2,) + tuple(xt.shape), dtype=torch.float32, device=xt.device)
+    return B, Cc, dim, _lib.load().nhmc_cs_tiles(Cc, dim), tmp
 
 
 def data_cs(xt, y_spec, apply_clip=True, loss_out=None):
     """y_spec: the observation in spectrum layout [B, C, d, d], NaN where not observed (nhmc.h, nhmc_data_cs)."""
-    lib = _lib.load()
-    B, Cc, dim = xt.shape[0], xt.shape[1], xt.shape[2]
-    if y_spec.numel() != xt.numel():
-        raise _lib.NhmcError('data_cs: y_spec must have one entry per image element (spectrum layout)')
-    tiles = lib.nhmc_cs_tiles(Cc, dim)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    tmp = _cs_tmp(xt, dim)
+    B, Cc, dim, tiles, tmp = _cs_io(xt, y_spec)
     g = torch.empty_like(xt)
-    rc = lib.nhmc_data_cs(_p(xt, torch.float32, 'xt'), _p(y_spec, torch.float32, 'y_spec'), int(apply_clip),
-                          _p(g), _p(ws), _p(tmp), B, Cc, dim, _stream())
-    _lib.check(rc, 'nhmc_data_cs')
-    return sum_partials(ws, tiles, B, out=loss_out), g
+    loss = _two_pass('nhmc_data_cs', tiles, B, xt.device, loss_out,
+                     (_p(xt, torch.float32, 'xt'), _p(y_spec, torch.float32, 'y_spec'), int(apply_clip), _p(g)),
+                     (_p(tmp), B, Cc, dim))
+    return loss, g
 
 
 def data_cs_vjp(xt_next, y_spec, xt, e, at, at_next, g_e_out=None, loss_out=None):
     """Walsh-Hadamard CS data term on the clipped decode + VJP of the last DDIM step in the last row pass
     -> (loss [B] float64, g_xt, g_e).  y_spec: as in data_cs."""
-    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
-    lib = _lib.load()
-    dim = xt.shape[2]
-    if y_spec.numel() != xt.numel():
-        raise _lib.NhmcError('data_cs_vjp: y_spec must have one entry per image element (spectrum layout)')
-    tiles = lib.nhmc_cs_tiles(Cc, dim)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    tmp = _cs_tmp(xt, dim)
-    rc = lib.nhmc_data_cs_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y_spec, torch.float32, 'y_spec'),
-                              _p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next), _p(g_xt),
-                              _p(g_e), _p(ws), _p(tmp), B, Cc, dim, _stream())
-    _lib.check(rc, 'nhmc_data_cs_vjp')
-    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+    _, mix, grads, outs, alphas = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
+    B, Cc, dim, tiles, tmp = _cs_io(xt, y_spec)
+    loss = _two_pass('nhmc_data_cs_vjp', tiles, B, xt.device, loss_out,
+                     (_p(xt_next, torch.float32, 'xt_next'), _p(y_spec, torch.float32, 'y_spec'), *mix, *grads),
+                     (_p(tmp), B, Cc, dim))
+    return (loss, *outs)
 
 
 def spectral_apply(x, L, R, Dmap, LoT, RoT):
@@ -509,46 +497,37 @@ def sandwich_rect(x, S1, S2, mul=None):
     return out
 
 
-def _srconv_factors(f, dim):
-    """f = (V1 [d, sd], V1T [sd, d], U [sd, sd], UT [sd, sd], S [sd, sd]) -> sd, after a shape check"""
+def _srconv_io(xt, f):
+    """What data_srconv and data_srconv_vjp share: f = (V1 [d, sd], V1T [sd, d], U [sd, sd], UT [sd, sd], S [sd, sd])
+    -> (the five factor pointers, tiles, tmp, the trailing (B, C, dim, sd)) after a shape check"""
+    B, Cc, dim = xt.shape[0], xt.shape[1], xt.shape[2]
     V1, V1T, U, UT, S = f
     sd = U.shape[0]
     if tuple(V1.shape) != (dim, sd) or tuple(V1T.shape) != (sd, dim) or tuple(U.shape) != (sd, sd) or \
             tuple(UT.shape) != (sd, sd) or tuple(S.shape) != (sd, sd):
         raise _lib.NhmcError('SRConv factors: V1 [d, sd], V1^T [sd, d], U, U^T, S [sd, sd]')
-    return sd
+    tmp = torch.empty(B * Cc * (dim * sd + 3 * sd * sd), dtype=torch.float32, device=xt.device)
+    return [_p(t, torch.float32) for t in f], _lib.load().nhmc_srconv_tiles(Cc, sd), tmp, (B, Cc, dim, sd)
 
 
 def data_srconv(xt, y, factors, apply_clip=True, loss_out=None):
     """factors: (V1, V1T, U, UT, S) as nhmc.operators.SRConv keeps them -> (loss [B] float64, g_xt)"""
-    lib = _lib.load()
-    B, Cc, dim = xt.shape[0], xt.shape[1], xt.shape[2]
-    sd = _srconv_factors(factors, dim)
-    tiles = lib.nhmc_srconv_tiles(Cc, sd)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    tmp = torch.empty(B * Cc * (dim * sd + 3 * sd * sd), dtype=torch.float32, device=xt.device)
+    fac, tiles, tmp, dims = _srconv_io(xt, factors)
     g = torch.empty_like(xt)
-    rc = lib.nhmc_data_srconv(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), *[_p(t, torch.float32) for t in factors],
-                              int(apply_clip), _p(g), _p(ws), _p(tmp), B, Cc, dim, sd, _stream())
-    _lib.check(rc, 'nhmc_data_srconv')
-    return sum_partials(ws, tiles, B, out=loss_out), g
+    loss = _two_pass('nhmc_data_srconv', tiles, dims[0], xt.device, loss_out,
+                     (_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), *fac, int(apply_clip), _p(g)), (_p(tmp), *dims))
+    return loss, g
 
 
 def data_srconv_vjp(xt_next, y, factors, xt, e, at, at_next, g_e_out=None, loss_out=None):
     """Bicubic / strided-convolution data term on the clipped decode + VJP of the last DDIM step in the last product's
     epilogue -> (loss [B] float64, g_xt, g_e)."""
-    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
-    lib = _lib.load()
-    dim = xt.shape[2]
-    sd = _srconv_factors(factors, dim)
-    tiles = lib.nhmc_srconv_tiles(Cc, sd)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    tmp = torch.empty(B * Cc * (dim * sd + 3 * sd * sd), dtype=torch.float32, device=xt.device)
-    rc = lib.nhmc_data_srconv_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y, torch.float32, 'y'),
-                                  *[_p(t, torch.float32) for t in factors], _p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec,
-                                  _p(at), _p(at_next), _p(g_xt), _p(g_e), _p(ws), _p(tmp), B, Cc, dim, sd, _stream())
-    _lib.check(rc, 'nhmc_data_srconv_vjp')
-    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+    _, mix, grads, outs, alphas = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
+    fac, tiles, tmp, dims = _srconv_io(xt, factors)
+    loss = _two_pass('nhmc_data_srconv_vjp', tiles, dims[0], xt.device, loss_out,
+                     (_p(xt_next, torch.float32, 'xt_next'), _p(y, torch.float32, 'y'), *fac, *mix, *grads),
+                     (_p(tmp), *dims))
+    return (loss, *outs)
 
 
 def spectral_project(y, L, R):
@@ -567,48 +546,36 @@ def data_spectral(xt, y, factors, Dmap, apply_clip=True, loss_out=None, projecte
     Eight-product (reference-order) form: `y` is the observation with every channel plane TRANSPOSED and DmapT the
     multiplier map likewise (nhmc.h, nhmc_data_spectral).  projected: `y` is spectral_project(y, U1, U2) (natural
     orientation) and the four-product form runs."""
-    lib = _lib.load()
-    B, Cc, dim = xt.shape[0], xt.shape[1], xt.shape[2]
-    tiles = lib.nhmc_spectral_tiles(Cc, dim)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    tmp = torch.empty((1 if projected else 2,) + tuple(xt.shape), dtype=torch.float32, device=xt.device)
+    entry, ops, tiles, tmp, dims = _spectral_io(xt, y, factors, Dmap, DmapT, projected)
     g = torch.empty_like(xt)
-    if projected:
-        rc = lib.nhmc_data_spectral_proj(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), _p(factors, torch.float32, 'factors'),
-                                         _p(Dmap, torch.float32), int(apply_clip), _p(g), _p(ws), _p(tmp), B, Cc, dim, _stream())
-    else:
+    loss = _two_pass(entry, tiles, dims[0], xt.device, loss_out, (_p(xt, torch.float32, 'xt'), *ops, int(apply_clip), _p(g)),
+                     (_p(tmp), *dims))
+    return loss, g
+
+
+def _spectral_io(xt, y, factors, Dmap, DmapT, projected):
+    """What data_spectral and data_spectral_vjp share, and the one place that chooses between the two forms
+    -> (entry of the data term (the VJP form's is entry + '_vjp'), the operands after the image: y, factors and the
+    form's multiplier maps, tiles, tmp, the trailing (B, C, dim))"""
+    B, Cc, dim = xt.shape[0], xt.shape[1], xt.shape[2]
+    ops = (_p(y, torch.float32, 'y' if projected else 'yT'), _p(factors, torch.float32, 'factors'), _p(Dmap, torch.float32, 'Dmap'))
+    if not projected:
         if DmapT is None:
             raise _lib.NhmcError('data_spectral: the eight-product form needs DmapT (Dmap with every plane transposed)')
-        rc = lib.nhmc_data_spectral(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'yT'), _p(factors, torch.float32, 'factors'),
-                                    _p(Dmap, torch.float32), _p(DmapT, torch.float32, 'DmapT'), int(apply_clip), _p(g), _p(ws), _p(tmp),
-                                    B, Cc, dim, _stream())
-    _lib.check(rc, 'nhmc_data_spectral')
-    return sum_partials(ws, tiles, B, out=loss_out), g
+        ops += (_p(DmapT, torch.float32, 'DmapT'),)
+    tmp = torch.empty((1 if projected else 2,) + tuple(xt.shape), dtype=torch.float32, device=xt.device)
+    entry = 'nhmc_data_spectral_proj' if projected else 'nhmc_data_spectral'
+    return entry, ops, _lib.load().nhmc_spectral_tiles(Cc, dim), tmp, (B, Cc, dim)
 
 
 def data_spectral_vjp(xt_next, y, factors, Dmap, xt, e, at, at_next, g_e_out=None, loss_out=None, projected=False, DmapT=None):
     """Spectral data term on the clipped decode `xt_next` + VJP of the last DDIM step (inputs xt, e) in the last
     product's epilogue -> (loss [B] float64, g_xt, g_e).  y / DmapT / projected: as in data_spectral."""
-    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
-    lib = _lib.load()
-    dim = xt.shape[2]
-    tiles = lib.nhmc_spectral_tiles(Cc, dim)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    tmp = torch.empty((1 if projected else 2,) + tuple(xt.shape), dtype=torch.float32, device=xt.device)
-    if projected:
-        rc = lib.nhmc_data_spectral_proj_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y, torch.float32, 'y'),
-                                             _p(factors, torch.float32, 'factors'), _p(Dmap, torch.float32),
-                                             _p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
-                                             _p(g_xt), _p(g_e), _p(ws), _p(tmp), B, Cc, dim, _stream())
-    else:
-        if DmapT is None:
-            raise _lib.NhmcError('data_spectral_vjp: the eight-product form needs DmapT (Dmap with every plane transposed)')
-        rc = lib.nhmc_data_spectral_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y, torch.float32, 'yT'),
-                                        _p(factors, torch.float32, 'factors'), _p(Dmap, torch.float32), _p(DmapT, torch.float32, 'DmapT'),
-                                        _p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
-                                        _p(g_xt), _p(g_e), _p(ws), _p(tmp), B, Cc, dim, _stream())
-    _lib.check(rc, 'nhmc_data_spectral_vjp')
-    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+    _, mix, grads, outs, alphas = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
+    entry, ops, tiles, tmp, dims = _spectral_io(xt, y, factors, Dmap, DmapT, projected)
+    loss = _two_pass(entry + '_vjp', tiles, dims[0], xt.device, loss_out,
+                     (_p(xt_next, torch.float32, 'xt_next'), *ops, *mix, *grads), (_p(tmp), *dims))
+    return (loss, *outs)
 
 
 # ---- nonlinear operators: HDR, phase retrieval -------------------------------------------------
@@ -629,28 +596,20 @@ def _dense_y(y, xt):
 
 def data_hdr(xt, y, apply_clip=True, loss_out=None):
     """-> (loss [B] float64, g_xt) for H = clip(2 x); y dense, one entry per image element."""
-    lib = _lib.load()
     B, N = _dense_y(y, xt)
-    tiles = lib.nhmc_data_tiles(N)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
     g = torch.empty_like(xt)
-    rc = lib.nhmc_data_hdr(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), int(apply_clip), _p(g), _p(ws), B, N, _stream())
-    _lib.check(rc, 'nhmc_data_hdr')
-    return sum_partials(ws, tiles, B, out=loss_out), g
+    loss = _two_pass('nhmc_data_hdr', _lib.load().nhmc_data_tiles(N), B, xt.device, loss_out,
+                     (_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), int(apply_clip), _p(g)), (B, N))
+    return loss, g
 
 
 def mix_bwd_hdr(xt, e, at, at_next, y, g_e_out=None, loss_out=None):
     """Last-step VJP fused with the HDR data term -> (loss [B] float64, g_xt, g_e)."""
-    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
-    lib = _lib.load()
+    dims, mix, grads, outs, alphas = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
     _dense_y(y, xt)
-    tiles = leapfrog_tiles(Cc * hw)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    rc = lib.nhmc_mix_bwd_hdr(_p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
-                              _p(y, torch.float32, 'y'), _p(g_xt), _p(g_e, torch.float32, 'g_e'), int(g_e_out is None),
-                              _p(ws), B, Cc, hw, _stream())
-    _lib.check(rc, 'nhmc_mix_bwd_hdr')
-    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+    loss = _two_pass('nhmc_mix_bwd_hdr', leapfrog_tiles(dims[1] * dims[2]), dims[0], xt.device, loss_out,
+                     (*mix, _p(y, torch.float32, 'y'), *grads), dims)
+    return (loss, *outs)
 
 
 def _phase_shapes(x, fac, pad, side=None):
@@ -707,43 +666,40 @@ def phase_adjoint(w, fac, pad):
     return out
 
 
-def _phase_y(y, B, Cc, n):
+def _phase_io(xt, y, fac, pad):
+    """What data_phase and data_phase_vjp share -> (tiles, tmp, the trailing (B, C, dim, pad)) after the shape checks."""
+    B, Cc, dim, n = _phase_shapes(xt, fac, pad)
     if tuple(y.shape) != (B, Cc, n, n):
         raise _lib.NhmcError(f'phase observation must be [{B}, {Cc}, {n}, {n}], got {tuple(y.shape)}')
+    return _lib.load().nhmc_phase_tiles(Cc, dim, pad), _phase_tmp(B, Cc, dim, pad, xt.device), (B, Cc, dim, pad)
+
+
+def _xt_next(xt_next, xt):
+    """The checked pointer of the clipped decode handed to a VJP form."""
+    if xt_next.shape != xt.shape:
+        raise _lib.NhmcError('xt_next must have the shape of xt')
+    return _p(xt_next, torch.float32, 'xt_next')
 
 
 def data_phase(xt, y, fac, pad, apply_clip=True, loss_out=None):
     """-> (loss [B] float64, g_xt) for H = |fft2c(pad(x))|; y [B, C, n, n]."""
-    lib = _lib.load()
-    B, Cc, dim, n = _phase_shapes(xt, fac, pad)
-    _phase_y(y, B, Cc, n)
-    tiles = lib.nhmc_phase_tiles(Cc, dim, pad)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    tmp = _phase_tmp(B, Cc, dim, pad, xt.device)
+    tiles, tmp, dims = _phase_io(xt, y, fac, pad)
     g = torch.empty_like(xt)
-    rc = lib.nhmc_data_phase(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), _p(fac, torch.float32, 'fac'), int(apply_clip),
-                             _p(g), _p(ws), _p(tmp), B, Cc, dim, pad, _stream())
-    _lib.check(rc, 'nhmc_data_phase')
-    return sum_partials(ws, tiles, B, out=loss_out), g
+    loss = _two_pass('nhmc_data_phase', tiles, dims[0], xt.device, loss_out,
+                     (_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), _p(fac, torch.float32, 'fac'), int(apply_clip), _p(g)),
+                     (_p(tmp), *dims))
+    return loss, g
 
 
 def data_phase_vjp(xt_next, y, fac, pad, xt, e, at, at_next, g_e_out=None, loss_out=None):
     """Phase-retrieval data term on the clipped decode `xt_next` + VJP of the last DDIM step (inputs xt, e) in the last
     product's epilogue -> (loss [B] float64, g_xt, g_e)."""
-    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
-    lib = _lib.load()
-    _, _, dim, n = _phase_shapes(xt, fac, pad)
-    _phase_y(y, B, Cc, n)
-    if xt_next.shape != xt.shape:
-        raise _lib.NhmcError('xt_next must have the shape of xt')
-    tiles = lib.nhmc_phase_tiles(Cc, dim, pad)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    tmp = _phase_tmp(B, Cc, dim, pad, xt.device)
-    rc = lib.nhmc_data_phase_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y, torch.float32, 'y'), _p(fac, torch.float32, 'fac'),
-                                 _p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next), _p(g_xt),
-                                 _p(g_e, torch.float32, 'g_e'), _p(ws), _p(tmp), B, Cc, dim, pad, _stream())
-    _lib.check(rc, 'nhmc_data_phase_vjp')
-    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+    _, mix, grads, outs, alphas = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
+    tiles, tmp, dims = _phase_io(xt, y, fac, pad)
+    loss = _two_pass('nhmc_data_phase_vjp', tiles, dims[0], xt.device, loss_out,
+                     (_xt_next(xt_next, xt), _p(y, torch.float32, 'y'), _p(fac, torch.float32, 'fac'), *mix, *grads),
+                     (_p(tmp), *dims))
+    return (loss, *outs)
 
 
 # ---- general 2-D PSF blur (deblur_motion) --------------------------------------------------------
@@ -798,42 +754,32 @@ def blur2d_apply(x, taps, transpose=False):
     return out
 
 
-def _blur_y(y, xt):
+def _blur_io(xt, y):
+    """What data_blur2d and data_blur2d_vjp share -> (tiles, tmp, the trailing (B, C, dim)) after the shape checks."""
+    dims = _blur_shapes(xt)
     if tuple(y.shape) != tuple(xt.shape):
         raise _lib.NhmcError(f'the blur observation has the image shape {tuple(xt.shape)}, got {tuple(y.shape)}')
+    return _lib.load().nhmc_blur2d_tiles(dims[1], dims[2]), torch.empty_like(xt), dims
 
 
 def data_blur2d(xt, y, taps, apply_clip=True, loss_out=None):
     """-> (loss [B] float64, g_xt) for H = the PSF blur; y [B, C, d, d]."""
-    lib = _lib.load()
-    B, Cc, dim = _blur_shapes(xt)
-    _blur_y(y, xt)
-    tiles = lib.nhmc_blur2d_tiles(Cc, dim)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    tmp, g = torch.empty_like(xt), torch.empty_like(xt)
-    rc = lib.nhmc_data_blur2d(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), *taps.args(), int(apply_clip), _p(g),
-                              _p(ws), _p(tmp), B, Cc, dim, _stream())
-    _lib.check(rc, 'nhmc_data_blur2d')
-    return sum_partials(ws, tiles, B, out=loss_out), g
+    tiles, tmp, dims = _blur_io(xt, y)
+    g = torch.empty_like(xt)
+    loss = _two_pass('nhmc_data_blur2d', tiles, dims[0], xt.device, loss_out,
+                     (_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), *taps.args(), int(apply_clip), _p(g)),
+                     (_p(tmp), *dims))
+    return loss, g
 
 
 def data_blur2d_vjp(xt_next, y, taps, xt, e, at, at_next, g_e_out=None, loss_out=None):
     """Blur data term on the clipped decode `xt_next` + VJP of the last DDIM step (inputs xt, e) in the adjoint pass's
     epilogue -> (loss [B] float64, g_xt, g_e)."""
-    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
-    lib = _lib.load()
-    _, _, dim = _blur_shapes(xt)
-    _blur_y(y, xt)
-    if xt_next.shape != xt.shape:
-        raise _lib.NhmcError('xt_next must have the shape of xt')
-    tiles = lib.nhmc_blur2d_tiles(Cc, dim)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
-    tmp = torch.empty_like(xt)
-    rc = lib.nhmc_data_blur2d_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y, torch.float32, 'y'), *taps.args(),
-                                  _p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next), _p(g_xt),
-                                  _p(g_e, torch.float32, 'g_e'), int(g_e_out is None), _p(ws), _p(tmp), B, Cc, dim, _stream())
-    _lib.check(rc, 'nhmc_data_blur2d_vjp')
-    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+    _, mix, grads, outs, alphas = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
+    tiles, tmp, dims = _blur_io(xt, y)
+    loss = _two_pass('nhmc_data_blur2d_vjp', tiles, dims[0], xt.device, loss_out,
+                     (_xt_next(xt_next, xt), _p(y, torch.float32, 'y'), *taps.args(), *mix, *grads), (_p(tmp), *dims))
+    return (loss, *outs)
 
 
 # ---- sparse linear operators (SparseLinear, ct<V>) -----------------------------------------------
@@ -963,68 +909,54 @@ def sparse_apply(x, mat, transpose=False):
 
 
 def _sparse_io(xt, y, mat):
+    """What data_sparse and data_sparse_vjp share -> (the operands after the image: y, both lists, m, nnz; tiles; tmp;
+    the trailing (B, C, dim)) after the shape checks."""
     if xt.dim() != 4 or xt.shape[2] != xt.shape[3] or xt.shape[2] * xt.shape[3] != mat.n:
         raise _lib.NhmcError(f'the sparse operator takes [B, C, d, d] images with d * d = {mat.n}, got {tuple(xt.shape)}')
     B, Cc, dim = xt.shape[0], xt.shape[1], xt.shape[2]
     if tuple(y.shape) != (B, Cc, mat.m):
         raise _lib.NhmcError(f'the sparse observation has the shape {(B, Cc, mat.m)}, got {tuple(y.shape)}')
     lib = _lib.load()
-    tiles = lib.nhmc_sparse_tiles(Cc, mat.m)
-    ws = torch.empty(B * tiles, dtype=torch.float64, device=xt.device)
     tmp = torch.empty(lib.nhmc_sparse_tmp_floats(B, Cc, mat.m, mat.n), dtype=torch.float32, device=xt.device)
-    return B, Cc, dim, tiles, ws, tmp
+    ops = (_p(y, torch.float32, 'y'), *mat.both(), mat.m, mat.nnz)
+    return ops, lib.nhmc_sparse_tiles(Cc, mat.m), tmp, (B, Cc, dim)
 
 
 def data_sparse(xt, y, mat, apply_clip=True, loss_out=None):
     """-> (loss [B] float64, g_xt) for the sparse operator `mat`; xt [B, C, d, d], y [B, C, m]."""
-    lib = _lib.load()
-    B, Cc, dim, tiles, ws, tmp = _sparse_io(xt, y, mat)
+    ops, tiles, tmp, dims = _sparse_io(xt, y, mat)
     g = torch.empty_like(xt)
-    rc = lib.nhmc_data_sparse(_p(xt, torch.float32, 'xt'), _p(y, torch.float32, 'y'), *mat.both(), mat.m, mat.nnz,
-                              int(apply_clip), _p(g), _p(ws), _p(tmp), B, Cc, dim, _stream())
-    _lib.check(rc, 'nhmc_data_sparse')
-    return sum_partials(ws, tiles, B, out=loss_out), g
+    loss = _two_pass('nhmc_data_sparse', tiles, dims[0], xt.device, loss_out,
+                     (_p(xt, torch.float32, 'xt'), *ops, int(apply_clip), _p(g)), (_p(tmp), *dims))
+    return loss, g
 
 
 def data_sparse_vjp(xt_next, y, mat, xt, e, at, at_next, g_e_out=None, loss_out=None):
     """Sparse data term on the clipped decode `xt_next` + VJP of the last DDIM step (inputs xt, e) in the adjoint pass's
     epilogue -> (loss [B] float64, g_xt, g_e)."""
-    B, Cc, hw, ec, at, at_next, g_xt, g_e = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
-    lib = _lib.load()
-    if xt_next.shape != xt.shape:
-        raise _lib.NhmcError('xt_next must have the shape of xt')
-    _, _, dim, tiles, ws, tmp = _sparse_io(xt, y, mat)
-    rc = lib.nhmc_data_sparse_vjp(_p(xt_next, torch.float32, 'xt_next'), _p(y, torch.float32, 'y'), *mat.both(), mat.m,
-                                  mat.nnz, _p(xt, torch.float32, 'xt'), _p(e, torch.float32, 'e'), ec, _p(at), _p(at_next),
-                                  _p(g_xt), _p(g_e, torch.float32, 'g_e'), int(g_e_out is None), _p(ws), _p(tmp), B, Cc, dim,
-                                  _stream())
-    _lib.check(rc, 'nhmc_data_sparse_vjp')
-    return sum_partials(ws, tiles, B, out=loss_out), g_xt, g_e
+    _, mix, grads, outs, alphas = _last_vjp_io(xt, e, at, at_next, g_e_out, True)
+    ops, tiles, tmp, dims = _sparse_io(xt, y, mat)
+    loss = _two_pass('nhmc_data_sparse_vjp', tiles, dims[0], xt.device, loss_out,
+                     (_xt_next(xt_next, xt), *ops, *mix, *grads), (_p(tmp), *dims))
+    return (loss, *outs)
 
 
 # ---- a5-a7 ----------------------------------------------------------------------------------
 def hamiltonian(sums_ws, n_elem, loss, sigma_y, m_inv, want_terms=False, sel=None):
     """sel (int32 [B]): loss is then the gradient cache's loss_pair [2, B] and chain c uses loss[sel[c], c]."""
     lib = _lib.load()
-    if sel is not None:
-        B = sel.numel()
-        if loss.shape != (2, B) or loss.dtype != torch.float64 or loss.stride(1) != 1:
-            raise _lib.NhmcError('hamiltonian(sel=...): loss must be the float64 [2, n_chains] cache')
-        H = torch.empty(B, dtype=torch.float32, device=loss.device)
-        terms = torch.empty(B, 3, dtype=torch.float64, device=loss.device) if want_terms else None
-        sy = _f64(sigma_y, B, loss.device)
-        rc = lib.nhmc_hamiltonian_cached(_p(sums_ws, torch.float64), leapfrog_tiles(n_elem), C.c_void_p(loss.data_ptr()),
-                                         _p(sel, torch.int32, 'sel'), loss.stride(0), _p(sy), float(m_inv), _p(H), _p(terms),
-                                         B, _stream())
-        _lib.check(rc, 'nhmc_hamiltonian_cached')
-        return (H, terms) if want_terms else H
-    B = loss.numel()
+    B = loss.numel() if sel is None else sel.numel()
     H = torch.empty(B, dtype=torch.float32, device=loss.device)
     terms = torch.empty(B, 3, dtype=torch.float64, device=loss.device) if want_terms else None
     sy = _f64(sigma_y, B, loss.device)
-    rc = lib.nhmc_hamiltonian(_p(sums_ws, torch.float64), leapfrog_tiles(n_elem), _p(loss, torch.float64, 'loss'),
-                              _p(sy), float(m_inv), _p(H), _p(terms), B, _stream())
-    _lib.check(rc, 'nhmc_hamiltonian')
+    if sel is None:
+        rc = lib.nhmc_hamiltonian(_p(sums_ws, torch.float64), leapfrog_tiles(n_elem), _p(loss, torch.float64, 'loss'),
+                                  _p(sy), float(m_inv), _p(H), _p(terms), B, _stream())
+    else:
+        lp, ls = _loss_pair(loss, B)
+        rc = lib.nhmc_hamiltonian_cached(_p(sums_ws, torch.float64), leapfrog_tiles(n_elem), lp, _p(sel, torch.int32, 'sel'),
+                                         ls, _p(sy), float(m_inv), _p(H), _p(terms), B, _stream())
+    _lib.check(rc, 'nhmc_hamiltonian' if sel is None else 'nhmc_hamiltonian_cached')
     return (H, terms) if want_terms else H
 
 
@@ -1145,6 +1077,7 @@ def vq_nearest(z, codebook):
 
 
 def _gn_shape(shape, gamma, groups, film, pre):
+    """-> (B, C, hw, the four conditioning arguments in ABI order: film, its row stride, pre, its row stride)"""
     B, Cc, hw = shape[0], shape[1], 1
     for d in shape[2:]:
         hw *= d
@@ -1156,13 +1089,15 @@ def _gn_shape(shape, gamma, groups, film, pre):
             raise _lib.NhmcError('fused GroupNorm: film must be [B, 2C] (scale | shift) with unit inner stride')
         stride = film.stride(0)
     if pre is not None:
-        if pre.dtype != torch.float32 or not pre.is_cuda or pre.stride(-1) != 1 or pre.shape not in ((Cc,), (B, Cc)):
-            raise _lib.NhmcError('fused GroupNorm: pre must be float32 [C] or [B, C] on the GPU')
+        if pre.stride(-1) != 1 or pre.shape not in ((Cc,), (B, Cc)):
+            raise _lib.NhmcError('fused GroupNorm: pre must be float32 [C] or [B, C] with unit inner stride')
         pstride = pre.stride(0) if pre.dim() == 2 else 0
-    return B, Cc, hw, stride, pstride
+    return B, Cc, hw, (_p(film, torch.float32, 'film', contiguous=False), stride,
+                       _p(pre, torch.float32, 'pre', contiguous=False), pstride)
 
 
 def _ptr(t):
+    """The unchecked address of a tensor: no wrapper uses it; tests/test_gn_onepass_gpu.py calls the raw ABI with it."""
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
@@ -1188,7 +1123,7 @@ def gn_act_fwd(x, gamma, beta, groups, eps, act, film=None, pre=None, x2=None, f
         raise _lib.NhmcError('fused GroupNorm: the two sources must agree in batch and spatial shape')
     C1 = x.shape[1]
     shape = x.shape if x2 is None else (x.shape[0], C1 + x2.shape[1]) + tuple(x.shape[2:])
-    B, Cc, hw, stride, pstride = _gn_shape(shape, gamma, groups, film, pre)
+    B, Cc, hw, cond = _gn_shape(shape, gamma, groups, film, pre)
     one = gn_onepass_splits(B, Cc, groups, hw)
     if x2 is not None and not one:
         raise _lib.NhmcError('fused GroupNorm: two sources need the one-pass kernels, which do not cover this shape')
@@ -1199,14 +1134,14 @@ def gn_act_fwd(x, gamma, beta, groups, eps, act, film=None, pre=None, x2=None, f
         ws = torch.empty(B * groups * (one + 1) * 2, dtype=torch.float64, device=x.device)   # partials, then the slab totals
         x_cat = torch.empty_like(y) if x2 is not None else None
         rc = lib.nhmc_gn_onepass_fwd(_p(x, torch.float32, 'x'), _p(x2, torch.float32, 'x2'), C1, _p(gamma, torch.float32, 'gamma'),
-                                     _p(beta, torch.float32, 'beta'), _ptr(film), stride, _ptr(pre), pstride, float(eps), int(act),
+                                     _p(beta, torch.float32, 'beta'), *cond, float(eps), int(act),
                                      _p(y), _p(x_cat), _p(ws), int(flags), B, Cc, groups, hw, _stream())
         _lib.check(rc, 'nhmc_gn_onepass_fwd')
         return (y, ws, one) if x2 is None else (y, ws, one, x_cat)
     splits = lib.nhmc_gn_splits(B, Cc, groups, hw)
     ws = torch.empty(B * groups * splits * 2, dtype=torch.float64, device=x.device)
     rc = lib.nhmc_gn_act_fwd(_p(x, torch.float32, 'x'), _p(gamma, torch.float32, 'gamma'), _p(beta, torch.float32, 'beta'),
-                             _ptr(film), stride, _ptr(pre), pstride, float(eps), int(act), _p(y), _p(ws), splits, B, Cc, groups,
+                             *cond, float(eps), int(act), _p(y), _p(ws), splits, B, Cc, groups,
                              hw, _stream())
     _lib.check(rc, 'nhmc_gn_act_fwd')
     return y, ws, splits
@@ -1218,7 +1153,7 @@ def gn_act_bwd(x, dy, gamma, beta, groups, eps, act, film, fwd_ws, splits, pre=N
     c1 (optional, 0 < c1 < C): the gradient is returned as two contiguous tensors (dx[:, :c1], dx[:, c1:]); needs the
     one-pass kernels.  onepass: as in gn_act_fwd."""
     lib = _lib.load()
-    B, Cc, hw, stride, pstride = _gn_shape(x.shape, gamma, groups, film, pre)
+    B, Cc, hw, cond = _gn_shape(x.shape, gamma, groups, film, pre)
     one = gn_onepass_splits(B, Cc, groups, hw)
     if c1 is not None and not one:
         raise _lib.NhmcError('fused GroupNorm: a split gradient needs the one-pass kernels, which do not cover this shape')
@@ -1226,7 +1161,7 @@ def gn_act_bwd(x, dy, gamma, beta, groups, eps, act, film, fwd_ws, splits, pre=N
         one = 0
     if add is not None and add.shape != x.shape:
         raise _lib.NhmcError('gn_act_bwd: `add` must have the shape of x')
-    addp = _p(add, torch.float32, 'add') if add is not None else _ptr(None)
+    addp = _p(add, torch.float32, 'add')
     fwd_splits, own = splits, splits
     fwd_p = _p(fwd_ws, torch.float64)
     if fwd_ws.numel() == B * groups * (splits + 1) * 2:
@@ -1242,7 +1177,7 @@ def gn_act_bwd(x, dy, gamma, beta, groups, eps, act, film, fwd_ws, splits, pre=N
             dx1 = torch.empty((B, c1) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
             dx2 = torch.empty((B, Cc - c1) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
         rc = lib.nhmc_gn_onepass_bwd(_p(x, torch.float32, 'x'), _p(dy, torch.float32, 'dy'), _p(gamma, torch.float32, 'gamma'),
-                                     _p(beta, torch.float32, 'beta'), _ptr(film), stride, _ptr(pre), pstride, float(eps), int(act),
+                                     _p(beta, torch.float32, 'beta'), *cond, float(eps), int(act),
                                      fwd_p, int(fwd_splits), addp, _p(dx1), _p(dx2), Cc if c1 is None else int(c1),
                                      _p(ws), int(flags), B, Cc, groups, hw, _stream())
         _lib.check(rc, 'nhmc_gn_onepass_bwd')
@@ -1250,7 +1185,7 @@ def gn_act_bwd(x, dy, gamma, beta, groups, eps, act, film, fwd_ws, splits, pre=N
     ws = torch.empty(B * groups * own * 2, dtype=torch.float64, device=x.device)
     dx = torch.empty_like(x)
     rc = lib.nhmc_gn_act_bwd_fs(_p(x, torch.float32, 'x'), _p(dy, torch.float32, 'dy'), _p(gamma, torch.float32, 'gamma'),
-                                _p(beta, torch.float32, 'beta'), _ptr(film), stride, _ptr(pre), pstride, float(eps), int(act),
+                                _p(beta, torch.float32, 'beta'), *cond, float(eps), int(act),
                                 fwd_p, int(fwd_splits), addp, _p(dx), _p(ws), own, B, Cc, groups, hw, _stream())
     _lib.check(rc, 'nhmc_gn_act_bwd_fs')
     return dx
@@ -1444,18 +1379,30 @@ def std_map_normalise(std_map, minmax):
     return out
 
 
+def _pooled(samples, n_replicas, what, x_orig=None):
+    """-> (G, K, S, N): the images, replicas, samples per chain and elements of a [G * K, S, C, H, W] block on the GPU,
+    after checking it and an x_orig [G, C, H, W] given with it."""
+    if not samples.is_cuda:
+        raise _lib.NhmcError(f'{what}: samples must live on the GPU (got {samples.device}); libnhmc has no CPU path')
+    B, S, Cc, H, W = _sample_block(samples)
+    K = int(n_replicas)
+    if K < 1 or B % K:
+        raise _lib.NhmcError(f'{what}: {B} chains are not a multiple of {n_replicas} replicas')
+    G = B // K
+    if x_orig is not None and (x_orig.dim() != 4 or x_orig.shape[0] != G or x_orig.shape[1:] != samples.shape[2:]):
+        raise _lib.NhmcError(f'x_orig {tuple(x_orig.shape)} does not match {G} images of samples {tuple(samples.shape)}')
+    return G, K, S, Cc * H * W
+
+
 def chain_diag(samples, n_replicas, rhat_threshold=1.1):
     """Split R-hat and ESS per element over the replicas of every image (nhmc.h "Convergence of replica chains").
     samples [G * n_replicas, S, C, H, W], chain g * n_replicas + r being replica r of image g
     -> (rhat [G, C, H, W], ess [G, C, H, W] float32, summary [G, 6] float64)."""
+    G, K, S, N = _pooled(samples, n_replicas, 'chain_diag')
     lib = _lib.load()
-    B, S, Cc, H, W = _sample_block(samples)
-    K = int(n_replicas)
-    if K < 1 or B % K:
-        raise _lib.NhmcError(f'chain_diag: {B} chains are not a multiple of {n_replicas} replicas')
-    G, N, dev = B // K, Cc * H * W, samples.device
-    rhat = torch.empty((G, Cc, H, W), dtype=torch.float32, device=dev)
-    ess = torch.empty((G, Cc, H, W), dtype=torch.float32, device=dev)
+    dev, img = samples.device, (G,) + tuple(samples.shape[2:])
+    rhat = torch.empty(img, dtype=torch.float32, device=dev)
+    ess = torch.empty(img, dtype=torch.float32, device=dev)
     summary = torch.empty((G, 6), dtype=torch.float64, device=dev)
     ws = torch.empty(lib.nhmc_chain_diag_ws_bytes(G, N) // 8, dtype=torch.float64, device=dev)
     _lib.check(lib.nhmc_chain_diag(_p(samples, torch.float32, 'samples'), _p(rhat), _p(ess), _p(summary), _p(ws), G, K, S, N,
@@ -1468,16 +1415,13 @@ def calibration(samples, x_orig, n_replicas=1):
     samples [G * n_replicas, S, C, H, W], chain g * n_replicas + r being replica r of image g, and x_orig [G, C, H, W]
     -> (z [G, C, H, W] float32, counts [G, C, H, W] int32 = below + 65536 * equal, hist [G, n + 1] int64 with
     n = n_replicas * S, summary [G, 8] float64)."""
+    if x_orig is None:
+        raise _lib.NhmcError('calibration: x_orig is needed')
+    G, K, S, N = _pooled(samples, n_replicas, 'calibration', x_orig)
     lib = _lib.load()
-    B, S, Cc, H, W = _sample_block(samples)
-    K = int(n_replicas)
-    if K < 1 or B % K:
-        raise _lib.NhmcError(f'calibration: {B} chains are not a multiple of {n_replicas} replicas')
-    G, N, dev = B // K, Cc * H * W, samples.device
-    if x_orig.dim() != 4 or x_orig.shape[0] != G or x_orig.shape[1:] != samples.shape[2:]:
-        raise _lib.NhmcError(f'x_orig {tuple(x_orig.shape)} does not match {G} images of samples {tuple(samples.shape)}')
-    z = torch.empty((G, Cc, H, W), dtype=torch.float32, device=dev)
-    counts = torch.empty((G, Cc, H, W), dtype=torch.int32, device=dev)
+    dev, img = samples.device, (G,) + tuple(samples.shape[2:])
+    z = torch.empty(img, dtype=torch.float32, device=dev)
+    counts = torch.empty(img, dtype=torch.int32, device=dev)
     hist = torch.empty((G, K * S + 1), dtype=torch.int64, device=dev)
     summary = torch.empty((G, 8), dtype=torch.float64, device=dev)
     ws = torch.empty(lib.nhmc_calibration_ws_bytes(G, N) // 8, dtype=torch.float64, device=dev)
@@ -1491,15 +1435,10 @@ def credible(samples, x_orig, n_replicas=1, k=1):
     samples [G * n_replicas, S, C, H, W], chain g * n_replicas + r being replica r of image g, x_orig [G, C, H, W] or None,
     1 <= k <= n // 2 with n = n_replicas * S -> (lower, median, upper [G, C, H, W] float32: d_(k), the median and
     d_(n+1-k) of the n draws in torch.sort's order, summary [G, 6] float64)."""
+    G, K, S, N = _pooled(samples, n_replicas, 'credible', x_orig)
     lib = _lib.load()
-    B, S, Cc, H, W = _sample_block(samples)
-    K = int(n_replicas)
-    if K < 1 or B % K:
-        raise _lib.NhmcError(f'credible: {B} chains are not a multiple of {n_replicas} replicas')
-    G, N, dev = B // K, Cc * H * W, samples.device
-    if x_orig is not None and (x_orig.dim() != 4 or x_orig.shape[0] != G or x_orig.shape[1:] != samples.shape[2:]):
-        raise _lib.NhmcError(f'x_orig {tuple(x_orig.shape)} does not match {G} images of samples {tuple(samples.shape)}')
-    lower, median, upper = (torch.empty((G, Cc, H, W), dtype=torch.float32, device=dev) for _ in range(3))
+    dev = samples.device
+    lower, median, upper = (torch.empty((G,) + tuple(samples.shape[2:]), dtype=torch.float32, device=dev) for _ in range(3))
     summary = torch.empty((G, 6), dtype=torch.float64, device=dev)
     ws = torch.empty(lib.nhmc_credible_ws_bytes(G, N) // 8, dtype=torch.float64, device=dev)
     _lib.check(lib.nhmc_credible(_p(samples, torch.float32, 'samples'), _p(x_orig, torch.float32, 'x_orig'), _p(lower),
@@ -1507,28 +1446,14 @@ def credible(samples, x_orig, n_replicas=1, k=1):
     return lower, median, upper, summary
 
 
-def _pooled(samples, n_replicas, what):
-    """-> (G, S, N): the images, samples per chain and elements of a [G * n_replicas, S, C, H, W] block on the GPU."""
-    if not samples.is_cuda:
-        raise _lib.NhmcError(f'{what}: samples must live on the GPU (got {samples.device}); libnhmc has no CPU path')
-    B, S, Cc, H, W = _sample_block(samples)
-    K = int(n_replicas)
-    if K < 1 or B % K:
-        raise _lib.NhmcError(f'{what}: {B} chains are not a multiple of {n_replicas} replicas')
-    return B // K, S, Cc * H * W
-
-
 def sample_gram(samples, x_orig, n_replicas=1):
     """Gram matrix of an image's pooled draws about the first one (nhmc.h "Principal components of the posterior samples").
     samples [G * n_replicas, S, C, H, W], chain g * n_replicas + r being replica r of image g, x_orig [G, C, H, W] or None,
     2 <= n = n_replicas * S <= 256 -> [G, n, n] float64: rows u_1 ... u_{n-1} = d_2 - d_1 ... d_n - d_1 and u_n = t - d_1
     (NaN without x_orig), exactly symmetric."""
-    G, S, N = _pooled(samples, n_replicas, 'sample_gram')
+    G, K, S, N = _pooled(samples, n_replicas, 'sample_gram', x_orig)
     lib = _lib.load()
-    K, dev = int(n_replicas), samples.device
-    if x_orig is not None and (x_orig.dim() != 4 or x_orig.shape[0] != G or x_orig.shape[1:] != samples.shape[2:]):
-        raise _lib.NhmcError(f'x_orig {tuple(x_orig.shape)} does not match {G} images of samples {tuple(samples.shape)}')
-    n = K * S
+    n, dev = K * S, samples.device
     gram = torch.empty((G, n, n), dtype=torch.float64, device=dev)
     ws = torch.empty(lib.nhmc_sample_gram_ws_bytes(G, n, N) // 8, dtype=torch.float64, device=dev)
     _lib.check(lib.nhmc_sample_gram(_p(samples, torch.float32, 'samples'), _p(x_orig, torch.float32, 'x_orig'), _p(gram),
@@ -1539,9 +1464,9 @@ def sample_gram(samples, x_orig, n_replicas=1):
 def sample_project(samples, coef, n_replicas=1):
     """Images from coefficients over an image's pooled draws: out[g, j] = sum_i coef[g, j, i] (d_i - d_1) in fp64, rounded
     once.  samples as for `sample_gram`, coef [G, J, n] float64 with 1 <= J <= 8 -> [G, J, C, H, W] float32."""
-    G, S, N = _pooled(samples, n_replicas, 'sample_project')
+    G, K, S, N = _pooled(samples, n_replicas, 'sample_project')
     lib = _lib.load()
-    K, n = int(n_replicas), int(n_replicas) * S
+    n = K * S
     if coef.dim() != 3 or coef.shape[0] != G or coef.shape[2] != n:
         raise _lib.NhmcError(f'coef {tuple(coef.shape)} does not match {G} images of {n} pooled draws')
     J = coef.shape[1]

@@ -46,6 +46,52 @@ class H_functions:
         return True
 
 
+class ObservationCache:
+    """A constant transform of the observation (`make(y)`), cached per observation buffer: the sampler passes the same
+    y_0 (or the same chunk views of it) in every leapfrog step of a run.  The key is (kind, address, version, shape); an
+    entry pins the buffer's storage, so its address cannot be handed to another tensor while the entry lives; an in-place
+    write bumps the version and misses; the oldest of 16 entries makes room for a new one.  A non-contiguous y is a
+    temporary: computed, never stored.  While the stream is being captured into a hipGraph the cache is bypassed in both
+    directions: the transform must be a launch OF the graph, because a replay refills the static observation buffer with
+    another chunk's y (the engine keys its graphs by shape, sampler.LeapfrogEngine._graphed_chunk) -- a cached form of
+    the buffer's warm-up content would silently serve every later chunk."""
+
+    def __init__(self):
+        self._entries = {}
+
+    def get(self, y, make, kind=None):
+        if not y.is_contiguous() or (y.is_cuda and torch.cuda.is_current_stream_capturing()):
+            return make(y)
+        key = (kind, y.data_ptr(), y._version, tuple(y.shape))
+        hit = self._entries.get(key)
+        if hit is None:
+            if len(self._entries) >= 16:
+                self._entries.pop(next(iter(self._entries)))
+            hit = self._entries[key] = (make(y), y.untyped_storage())
+        return hit[0]
+
+    def __len__(self):
+        return len(self._entries)
+
+    def clear(self):
+        self._entries.clear()
+
+
+class DecodeFused(H_functions):
+    """The operators whose fused kernel reads the clipped decode of the last DDIM step: the engine hands over the one it
+    already holds (`fused_wants_decode`).  A subclass supplies `_observation(y, shape)`, the observation as its data-term
+    kernels read it for images of `shape`, and `_data_vjp`, its kernel call."""
+
+    fused_wants_decode = True
+
+    def fused_last_vjp(self, xt_in, e, at, at_next, y, g_e_out=None, xt_next=None, loss_out=None):
+        """Data term + VJP of the last DDIM step (applied in the data term's last epilogue) -> (loss, g_xt, g_e).
+        xt_next: the clipped decode of that step (recomputed when the caller does not have it)."""
+        if xt_next is None:
+            xt_next = K.ddim_mix_fwd(xt_in, e, at, at_next, final_clip=True)['xt_next']
+        return self._data_vjp(xt_next, self._observation(y, xt_in.shape), xt_in, e, at, at_next, g_e_out, loss_out)
+
+
 class Inpainting(H_functions):
     """obs_functions/Hfuncs.py:119-154.  `missing_indices` index the HWC-flattened image."""
 
@@ -146,7 +192,7 @@ def _band_matrix(kernel, img_dim):
     return Hs
 
 
-class Deblurring2D(H_functions):
+class Deblurring2D(DecodeFused):
     """obs_functions/Hfuncs.py:448-523, carried as data: U1,U2,V1,V2 [d,d] and D [C,d,d].
 
     The reference tiles the sorted singular values (:519-520) while its Vt() interleaves channels
@@ -206,7 +252,7 @@ class Deblurring2D(H_functions):
         if projected and self.orthogonality_error >= 1e-5:
             raise NhmcError(f'projected spectral data term needs orthogonal U factors (|U^T U - I| = {self.orthogonality_error:.1e})')
         self.projected = bool(projected)
-        self._y_proj = {}
+        self._y_proj = ObservationCache()
 
     def _f(self, i):
         return self.factors[i]
@@ -224,52 +270,24 @@ class Deblurring2D(H_functions):
         y = _img(vec, self.channels, self.img_dim)
         return K.spectral_apply(y, self._f(0), self._f(1), self.Dpinv, self._f(6), self._f(7)).reshape(y.shape[0], -1)
 
-    def _observation_form(self, y, make, kind):
-        """A constant transform of the observation (`make(y)`), cached per observation buffer: the sampler passes the
-        same y_0 (or the same chunk views of it) in every leapfrog step of a run.  An entry pins the buffer's storage, so
-        its address cannot be handed to another tensor while the entry lives; an in-place write bumps the version and
-        misses.  While the stream is being captured into a hipGraph the cache is bypassed in both directions: the
-        transform must be a launch OF the graph, because a replay refills the static observation buffer with another
-        chunk's y (the engine keys its graphs by shape, sampler.LeapfrogEngine._graphed_chunk) -- a cached form of the
-        buffer's warm-up content would silently serve every later chunk."""
-        if y.is_cuda and torch.cuda.is_current_stream_capturing():
-            return make(y)
-        key = (kind, y.data_ptr(), y._version, tuple(y.shape))
-        hit = self._y_proj.get(key)
-        if hit is None:
-            if len(self._y_proj) >= 16:
-                self._y_proj.pop(next(iter(self._y_proj)))
-            hit = (make(y), y.untyped_storage())
-            self._y_proj[key] = hit
-        return hit[0]
-
     def project_observation(self, y):
         """y^ = U1^T y U2 (the four-product form's observation)."""
-        return self._observation_form(y, lambda t: K.spectral_project(t, self._f(0), self._f(1)), 'projected')
+        return self._y_proj.get(y, lambda t: K.spectral_project(t.contiguous(), self._f(0), self._f(1)), 'projected')
 
-    def _obs(self, y, shape):
+    def _observation(self, y, shape):
         """What the data-term kernels take as observation: y^ for the projected form, else y with every channel plane
         transposed (the adjoint chain runs right-factor-first on transposed operands; plain data movement)."""
-        y = y.reshape(shape)
-        make = (lambda t: K.spectral_project(t, self._f(0), self._f(1))) if self.projected else \
-            (lambda t: t.transpose(-1, -2).contiguous())
-        if y.is_contiguous():
-            return self._observation_form(y, make, 'projected' if self.projected else 'transposed')
-        return make(y.contiguous())                                 # a temporary: never cached
+        if self.projected:
+            return self.project_observation(y.reshape(shape))
+        return self._y_proj.get(y.reshape(shape), lambda t: t.transpose(-1, -2).contiguous(), 'transposed')
 
     def data_term(self, xt, y, apply_clip=True, loss_out=None):
-        return K.data_spectral(xt, self._obs(y, xt.shape), self.factors, self.Dmap, apply_clip, loss_out=loss_out,
+        return K.data_spectral(xt, self._observation(y, xt.shape), self.factors, self.Dmap, apply_clip, loss_out=loss_out,
                                projected=self.projected, DmapT=self.DmapT)
 
-    fused_wants_decode = True              # the engine hands over the clipped decode it already holds
-
-    def fused_last_vjp(self, xt_in, e, at, at_next, y, g_e_out=None, xt_next=None, loss_out=None):
-        """Data term + VJP of the last DDIM step (applied in the last product's epilogue) -> (loss, g_xt, g_e).
-        xt_next: the clipped decode of that step (recomputed when the caller does not have it)."""
-        if xt_next is None:
-            xt_next = K.ddim_mix_fwd(xt_in, e, at, at_next, final_clip=True)['xt_next']
-        return K.data_spectral_vjp(xt_next, self._obs(y, xt_in.shape), self.factors, self.Dmap, xt_in, e, at,
-                                   at_next, g_e_out=g_e_out, loss_out=loss_out, projected=self.projected, DmapT=self.DmapT)
+    def _data_vjp(self, xt_next, obs, xt_in, e, at, at_next, g_e_out, loss_out):
+        return K.data_spectral_vjp(xt_next, obs, self.factors, self.Dmap, xt_in, e, at, at_next, g_e_out=g_e_out,
+                                   loss_out=loss_out, projected=self.projected, DmapT=self.DmapT)
 
 
 class Deblurring(Deblurring2D):
@@ -310,7 +328,7 @@ class Colorization(H_functions):
         return K.ddim_mix_bwd_color(xt_in, e, at, at_next, y.contiguous(), self.w, g_e_out=g_e_out, loss_out=loss_out)
 
 
-class WalshHadamardCS(H_functions):
+class WalshHadamardCS(DecodeFused):
     """obs_functions/Hfuncs.py:611-651: y[k*C + c] = (FWHT(x_c)/d)[perm[k]] for k < d^2/ratio; H^T = H^+."""
 
     def __init__(self, channels, img_dim, ratio, perm, device):
@@ -324,7 +342,7 @@ class WalshHadamardCS(H_functions):
         self.kslot = kslot.to(device)
         self._singulars = torch.ones(self.M, device=device)
         self._pos = perm.detach().cpu().long()[:rows].to(device)      # spectrum position of observation row k
-        self._y_spec = {}
+        self._y_spec = ObservationCache()
 
     def singulars(self):
         return self._singulars
@@ -340,33 +358,22 @@ class WalshHadamardCS(H_functions):
     def spectrum_observation(self, y):
         """y [B, K*C] (row k, channel c at k*C + c) -> [B, C, d, d] in the transform's own layout, y_spec[b, c, perm[k]] =
         y[b, k*C + c] and NaN where the spectrum is not observed: what the data-term kernels read (coalesced, no gather).
-        Constant over a run: cached per observation buffer (pinned storage + version, as Deblurring2D does) and never
-        across a hipGraph capture.  Plain data movement."""
+        Constant over a run: cached per observation buffer (ObservationCache).  Plain data movement."""
         def make(t):
             B, d = t.shape[0], self.img_dim
             spec = torch.full((B, self.channels, d * d), float('nan'), dtype=torch.float32, device=t.device)
             spec[:, :, self._pos] = t.reshape(B, -1, self.channels).permute(0, 2, 1)
             return spec.reshape(B, self.channels, d, d)
-        if not y.is_contiguous() or (y.is_cuda and torch.cuda.is_current_stream_capturing()):
-            return make(y)
-        key = (y.data_ptr(), y._version, tuple(y.shape))
-        hit = self._y_spec.get(key)
-        if hit is None:
-            if len(self._y_spec) >= 16:
-                self._y_spec.pop(next(iter(self._y_spec)))
-            hit = self._y_spec[key] = (make(y), y.untyped_storage())
-        return hit[0]
+        return self._y_spec.get(y, make)
+
+    def _observation(self, y, shape):
+        return self.spectrum_observation(y)
 
     def data_term(self, xt, y, apply_clip=True, loss_out=None):
-        return K.data_cs(xt, self.spectrum_observation(y), apply_clip, loss_out=loss_out)
+        return K.data_cs(xt, self._observation(y, xt.shape), apply_clip, loss_out=loss_out)
 
-    fused_wants_decode = True
-
-    def fused_last_vjp(self, xt_in, e, at, at_next, y, g_e_out=None, xt_next=None, loss_out=None):
-        """Data term + VJP of the last DDIM step (in the last column pass) -> (loss, g_xt, g_e)."""
-        if xt_next is None:
-            xt_next = K.ddim_mix_fwd(xt_in, e, at, at_next, final_clip=True)['xt_next']
-        return K.data_cs_vjp(xt_next, self.spectrum_observation(y), xt_in, e, at, at_next, g_e_out=g_e_out, loss_out=loss_out)
+    def _data_vjp(self, xt_next, obs, xt_in, e, at, at_next, g_e_out, loss_out):
+        return K.data_cs_vjp(xt_next, obs, xt_in, e, at, at_next, g_e_out=g_e_out, loss_out=loss_out)
 
 
 def strided_conv_matrix(kernel, img_dim, stride):
@@ -380,7 +387,7 @@ def strided_conv_matrix(kernel, img_dim, stride):
     return Hs
 
 
-class SRConv(H_functions):
+class SRConv(DecodeFused):
     """obs_functions/Hfuncs.py:527-607 (`sr_bicubicN`), in the reference's stage order: with the SVD U diag(s) V^T of the
     strided 1-D kernel matrix (singular values < 3e-2 zeroed, :557-558), V1 = V[:, :sd] and S[i][j] = s_i s_j (:560),
 
@@ -418,7 +425,7 @@ class SRConv(H_functions):
         self.V1, self.V1T, self.U, self.UT, self.S, self.Sinv = dev(V1), dev(V1.t()), dev(U), dev(U.t()), dev(S), dev(Sinv)
         self.factors = (self.V1, self.V1T, self.U, self.UT, self.S)
         self.M = channels * sd * sd
-        self._y_t = {}
+        self._y_t = ObservationCache()
 
     def _planes(self, v, dim):
         return v.reshape(-1, dim, dim).contiguous()
@@ -439,31 +446,17 @@ class SRConv(H_functions):
     def H_pinv(self, vec):
         return self._adjoint(vec, self.Sinv)
 
-    def _obs_t(self, y):
-        """The observation with every channel plane transposed (what nhmc_data_srconv takes), cached per buffer as
-        Deblurring2D._observation_form does, and never across a graph capture."""
+    def _observation(self, y, shape):
+        """The observation with every channel plane transposed (what nhmc_data_srconv takes), cached per buffer
+        (ObservationCache)."""
         sd = self.small_dim
-        make = lambda t: t.reshape(t.shape[0], self.channels, sd, sd).transpose(-1, -2).contiguous()
-        if not y.is_contiguous() or (y.is_cuda and torch.cuda.is_current_stream_capturing()):
-            return make(y)
-        key = (y.data_ptr(), y._version, tuple(y.shape))
-        hit = self._y_t.get(key)
-        if hit is None:
-            if len(self._y_t) >= 16:
-                self._y_t.pop(next(iter(self._y_t)))
-            hit = self._y_t[key] = (make(y), y.untyped_storage())
-        return hit[0]
+        return self._y_t.get(y, lambda t: t.reshape(shape[0], self.channels, sd, sd).transpose(-1, -2).contiguous())
 
     def data_term(self, xt, y, apply_clip=True, loss_out=None):
-        return K.data_srconv(xt, self._obs_t(y), self.factors, apply_clip, loss_out=loss_out)
+        return K.data_srconv(xt, self._observation(y, xt.shape), self.factors, apply_clip, loss_out=loss_out)
 
-    fused_wants_decode = True
-
-    def fused_last_vjp(self, xt_in, e, at, at_next, y, g_e_out=None, xt_next=None, loss_out=None):
-        """Data term + VJP of the last DDIM step (in the last product's epilogue) -> (loss, g_xt, g_e)."""
-        if xt_next is None:
-            xt_next = K.ddim_mix_fwd(xt_in, e, at, at_next, final_clip=True)['xt_next']
-        return K.data_srconv_vjp(xt_next, self._obs_t(y), self.factors, xt_in, e, at, at_next, g_e_out=g_e_out, loss_out=loss_out)
+    def _data_vjp(self, xt_next, obs, xt_in, e, at, at_next, g_e_out, loss_out):
+        return K.data_srconv_vjp(xt_next, obs, self.factors, xt_in, e, at, at_next, g_e_out=g_e_out, loss_out=loss_out)
 
 
 class HDR(H_functions):
@@ -503,7 +496,7 @@ def centred_dft_factors(n, pad, dim):
     return Fc.real.contiguous(), Fc.imag.contiguous()
 
 
-class PhaseRetrievalOperator(H_functions):
+class PhaseRetrievalOperator(DecodeFused):
     """obs_functions/Hfuncs.py:318-366: H(x) = |fft2c(pad(x, p))| per channel plane with p = int(oversample / 8 * 256)
     WHATEVER the image size (so n = img_dim + 128 for the reference's oversample = 2), M = C n n; H^+(y) = crop(|ifft2c(y)|).
     The zero padding turns the padded centred DFT into rectangular real sandwiches with Fc = Cm + i Sm (nhmc.h), built
@@ -527,9 +520,8 @@ class PhaseRetrievalOperator(H_functions):
     def is_linear(self):
         return False
 
-    def _obs(self, y):
-        y = y.reshape(y.shape[0], self.channels, self.n, self.n)
-        return y if y.is_contiguous() else y.contiguous()
+    def _observation(self, y, shape):
+        return y.reshape(shape[0], self.channels, self.n, self.n).contiguous()
 
     def H(self, vec):
         x = _img(vec, self.channels, self.img_dim)
@@ -546,22 +538,16 @@ class PhaseRetrievalOperator(H_functions):
         return K.phase_adjoint(w.contiguous(), self.factors, self.pad)
 
     def H_pinv(self, vec):
-        return K.phase_pinv(self._obs(vec), self.factors, self.pad).reshape(vec.shape[0], -1)
+        return K.phase_pinv(self._observation(vec, vec.shape), self.factors, self.pad).reshape(vec.shape[0], -1)
 
     def data_term(self, xt, y, apply_clip=True, loss_out=None):
-        return K.data_phase(xt, self._obs(y), self.factors, self.pad, apply_clip, loss_out=loss_out)
+        return K.data_phase(xt, self._observation(y, xt.shape), self.factors, self.pad, apply_clip, loss_out=loss_out)
 
-    fused_wants_decode = True              # the engine hands over the clipped decode it already holds
-
-    def fused_last_vjp(self, xt_in, e, at, at_next, y, g_e_out=None, xt_next=None, loss_out=None):
-        """Data term + VJP of the last DDIM step (in the last product's epilogue) -> (loss, g_xt, g_e)."""
-        if xt_next is None:
-            xt_next = K.ddim_mix_fwd(xt_in, e, at, at_next, final_clip=True)['xt_next']
-        return K.data_phase_vjp(xt_next, self._obs(y), self.factors, self.pad, xt_in, e, at, at_next, g_e_out=g_e_out,
-                                loss_out=loss_out)
+    def _data_vjp(self, xt_next, obs, xt_in, e, at, at_next, g_e_out, loss_out):
+        return K.data_phase_vjp(xt_next, obs, self.factors, self.pad, xt_in, e, at, at_next, g_e_out=g_e_out, loss_out=loss_out)
 
 
-class Blur2D(H_functions):
+class Blur2D(DecodeFused):
     """A general 2-D point-spread function (camera shake, defocus, a measured PSF): H = F.conv2d(x, k, padding=R) per
     channel plane (correlation, zero boundary -- what `_band_matrix` gives the separable blurs), H^T its exact adjoint;
     M = C d^2.  Not in the reference's prepare_measurement.  The operator is carried as the compacted list of the PSF's
@@ -590,21 +576,14 @@ class Blur2D(H_functions):
     def H_pinv(self, vec):
         raise NotImplementedError('a general PSF has no closed-form pseudo-inverse here; no sampler calls H_pinv')
 
-    def _obs(self, y, shape):
-        y = y.reshape(shape)
-        return y if y.is_contiguous() else y.contiguous()
+    def _observation(self, y, shape):
+        return y.reshape(shape).contiguous()
 
     def data_term(self, xt, y, apply_clip=True, loss_out=None):
-        return K.data_blur2d(xt, self._obs(y, xt.shape), self._taps, apply_clip, loss_out=loss_out)
+        return K.data_blur2d(xt, self._observation(y, xt.shape), self._taps, apply_clip, loss_out=loss_out)
 
-    fused_wants_decode = True              # the engine hands over the clipped decode it already holds
-
-    def fused_last_vjp(self, xt_in, e, at, at_next, y, g_e_out=None, xt_next=None, loss_out=None):
-        """Data term + VJP of the last DDIM step (the adjoint pass's epilogue) -> (loss, g_xt, g_e)."""
-        if xt_next is None:
-            xt_next = K.ddim_mix_fwd(xt_in, e, at, at_next, final_clip=True)['xt_next']
-        return K.data_blur2d_vjp(xt_next, self._obs(y, xt_in.shape), self._taps, xt_in, e, at, at_next, g_e_out=g_e_out,
-                                 loss_out=loss_out)
+    def _data_vjp(self, xt_next, obs, xt_in, e, at, at_next, g_e_out, loss_out):
+        return K.data_blur2d_vjp(xt_next, obs, self._taps, xt_in, e, at, at_next, g_e_out=g_e_out, loss_out=loss_out)
 
 
 def motion_kernel(size=61, intensity=0.5, generator=None):
@@ -657,7 +636,7 @@ def motion_kernel_points(size):
     return 1 if size == 1 else 2 * size + 1
 
 
-class SparseLinear(H_functions):
+class SparseLinear(DecodeFused):
     """Any linear forward model given as a sparse matrix A [m, img_dim^2] (tomography, spatially varying blur, irregular
     sampling, mosaics): H = A x per channel plane, H^T the exact adjoint on the transposed list; M = C m.  Not in the
     reference.  `matrix` is a torch sparse COO or CSR tensor, a scipy.sparse matrix (duck-typed: scipy is not a dependency)
@@ -690,21 +669,14 @@ class SparseLinear(H_functions):
     def H_pinv(self, vec):
         raise NotImplementedError('a general sparse operator has no closed-form pseudo-inverse here; no sampler calls H_pinv')
 
-    def _obs(self, y, B):
-        y = y.reshape(B, self.channels, self.m)
-        return y if y.is_contiguous() else y.contiguous()
+    def _observation(self, y, shape):
+        return y.reshape(shape[0], self.channels, self.m).contiguous()
 
     def data_term(self, xt, y, apply_clip=True, loss_out=None):
-        return K.data_sparse(xt, self._obs(y, xt.shape[0]), self._mat, apply_clip, loss_out=loss_out)
+        return K.data_sparse(xt, self._observation(y, xt.shape), self._mat, apply_clip, loss_out=loss_out)
 
-    fused_wants_decode = True              # the engine hands over the clipped decode it already holds
-
-    def fused_last_vjp(self, xt_in, e, at, at_next, y, g_e_out=None, xt_next=None, loss_out=None):
-        """Data term + VJP of the last DDIM step (the adjoint pass's epilogue) -> (loss, g_xt, g_e)."""
-        if xt_next is None:
-            xt_next = K.ddim_mix_fwd(xt_in, e, at, at_next, final_clip=True)['xt_next']
-        return K.data_sparse_vjp(xt_next, self._obs(y, xt_in.shape[0]), self._mat, xt_in, e, at, at_next, g_e_out=g_e_out,
-                                 loss_out=loss_out)
+    def _data_vjp(self, xt_next, obs, xt_in, e, at, at_next, g_e_out, loss_out):
+        return K.data_sparse_vjp(xt_next, obs, self._mat, xt_in, e, at, at_next, g_e_out=g_e_out, loss_out=loss_out)
 
 
 def radon_matrix(img_dim, n_views):

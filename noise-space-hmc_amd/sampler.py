@@ -82,6 +82,23 @@ class TapeNoise:
         return self.u(it).to(device=device, dtype=torch.float32).contiguous()
 
 
+def _noise_from(opt):
+    """The noise source an entry point hands its chains: opt.noise_source if set, Philox keyed by opt.philox_seed (and
+    opt.chain_id0) if that is set, else the reference's torch draws."""
+    noise = getattr(opt, 'noise_source', None)
+    if noise is None:
+        seed = getattr(opt, 'philox_seed', None)
+        noise = PhiloxNoise(seed, getattr(opt, 'chain_id0', 0)) if seed is not None else TorchNoise()
+    return noise
+
+
+def _operator(H_funcs):
+    if not hasattr(H_funcs, 'data_term'):
+        raise TypeError('H_funcs must be an nhmc.operators operator (needs the fused data_term); '
+                        'wrap other linear operators before calling hmc()')
+    return H_funcs
+
+
 # --------------------------------------------------------------------------------------------- #
 # engine
 # --------------------------------------------------------------------------------------------- #
@@ -448,12 +465,8 @@ def hmc_chains(x, b, seq, seq_next, algo, opt, y_0, H_funcs, x_orig=None, *, noi
     L = max(1, math.floor(tau / epsilon))                                   # :664, fixed for the run
     total = epochs + 2 * sampling
     noise = noise or TorchNoise()
-    operator = H_funcs if hasattr(H_funcs, 'data_term') else None
-    if operator is None:
-        raise TypeError('H_funcs must be an nhmc.operators operator (needs the fused data_term); '
-                        'wrap other linear operators before calling hmc()')
     score = algo.score if hasattr(algo, 'score') else algo.model
-    engine = LeapfrogEngine(score, operator, b, seq, seq_next, device, chunk=chunk)
+    engine = LeapfrogEngine(score, _operator(H_funcs), b, seq, seq_next, device, chunk=chunk)
     x = x.detach().clone().contiguous()
     y_0 = y_0.contiguous()
     x_orig = x_orig.contiguous() if x_orig is not None else None
@@ -550,10 +563,7 @@ def hmc(x, n, b, seq, seq_next, algo, opt, y_0, H_funcs, x_orig):
     opt.quiet; the per-epoch PNGs are written only when opt.save_images is set (default off: encoding
     a PNG per accept was a host sync per trajectory in the reference)."""
     quiet = bool(getattr(opt, 'quiet', False))
-    noise = getattr(opt, 'noise_source', None)
-    if noise is None:
-        seed = getattr(opt, 'philox_seed', None)
-        noise = PhiloxNoise(seed, getattr(opt, 'chain_id0', 0)) if seed is not None else TorchNoise()
+    noise = _noise_from(opt)
 
     def log(it, status, state, out, x_orig_, ids):
         if quiet or 0 not in ids:
@@ -600,10 +610,8 @@ def hmc_mass_chains(x, b, seq, seq_next, algo, opt, y_0, H_funcs, x_orig=None, *
     total = burn + epochs + 4 * sampling
     n_keep = total - (epochs + sampling)
     noise = noise or TorchNoise()
-    if not hasattr(H_funcs, 'data_term'):
-        raise TypeError('H_funcs must be an nhmc.operators operator (needs the fused data_term)')
     score = algo.score if hasattr(algo, 'score') else algo.model
-    engine = LeapfrogEngine(score, H_funcs, b, seq, seq_next, device, chunk=chunk)
+    engine = LeapfrogEngine(score, _operator(H_funcs), b, seq, seq_next, device, chunk=chunk)
     sig = [sigma_0 + 0.9 if e < burn else sigma_0 + 0.9 * (1 - (e - burn) / epochs) ** 3 for e in range(epochs)] + [sigma_0]
     sigma_table = torch.tensor(sig, dtype=torch.float64, device=device)                      # :808-813 in Python floats
     x = x.detach().clone().contiguous()
@@ -667,10 +675,7 @@ def hmc_mass_chains(x, b, seq, seq_next, algo, opt, y_0, H_funcs, x_orig=None, *
 
 def hmc_test_conditioning(x, n, b, seq, seq_next, algo, opt, y_0, H_funcs, x_orig):
     """Reference entry point (main_sampling.py:776): [35, C, H, W] at n = 1, [n, 35, C, H, W] otherwise."""
-    noise = getattr(opt, 'noise_source', None)
-    if noise is None:
-        seed = getattr(opt, 'philox_seed', None)
-        noise = PhiloxNoise(seed, getattr(opt, 'chain_id0', 0)) if seed is not None else TorchNoise()
+    noise = _noise_from(opt)
     res = hmc_mass_chains(x, b, seq, seq_next, algo, opt, y_0, H_funcs, x_orig, noise=noise,
                           chunk=getattr(opt, 'score_chunk', None))
     return res.samples[0] if n == 1 else res.samples
@@ -691,10 +696,8 @@ def hmc_latent_chains(x, seq, seq_next, algo, opt, y_0, H_funcs, x_orig=None, *,
     sigma_0, sigma_y0 = float(opt.sigma_0), float(opt.sigma_y)
     L = max(1, math.floor(tau / epsilon))
     noise = noise or TorchNoise()
-    if not hasattr(H_funcs, 'data_term'):
-        raise TypeError('H_funcs must be an nhmc.operators operator (needs the fused data_term)')
     table = torch.cat([model.alphas_cumprod_prev[0:1], model.alphas_cumprod], dim=0)          # :771-773
-    engine = LeapfrogEngine(algo.score, H_funcs, None, seq, seq_next, device, chunk=chunk, alpha_table=table,
+    engine = LeapfrogEngine(algo.score, _operator(H_funcs), None, seq, seq_next, device, chunk=chunk, alpha_table=table,
                             image_map=model.differentiable_decode_first_stage)
     x = x.detach().clone().contiguous()
     y_0 = y_0.contiguous()
@@ -742,10 +745,7 @@ def ring_samples(ring, count, keep):
 def hmc_latent(x, n, seq, seq_next, algo, opt, y_0, H_funcs, x_orig):
     """Reference entry point (main_sampling_latent.py:623, called at :466): returns the stack of the last 10
     collected latents at n = 1; a list of such stacks for n > 1 (the reference raises there)."""
-    noise = getattr(opt, 'noise_source', None)
-    if noise is None:
-        seed = getattr(opt, 'philox_seed', None)
-        noise = PhiloxNoise(seed, getattr(opt, 'chain_id0', 0)) if seed is not None else TorchNoise()
+    noise = _noise_from(opt)
     res = hmc_latent_chains(x, seq, seq_next, algo, opt, y_0, H_funcs, x_orig, noise=noise,
                             chunk=getattr(opt, 'score_chunk', None))
     return res.samples[0] if n == 1 else res.samples

@@ -312,8 +312,8 @@ def test_fused_wrappers_refuse_a_wrongly_shaped_g_e_out(name, monkeypatch):
     b = osched.betas_fp32()
     t.at, t.atn = osched.alpha_bar(b, torch.full((1,), 250)).cuda(), osched.alpha_bar(b, torch.full((1,), -1)).cuda()
     t.cur = K.ddim_mix_fwd(t.xt, t.e, t.at, t.atn, final_clip=True)['xt_next']
-    t.obs = {'data_cs_vjp': lambda: op.spectrum_observation(t.y), 'data_srconv_vjp': lambda: op._obs_t(t.y),
-             'data_spectral_vjp': lambda: op._obs(t.y, t.xt.shape), 'data_phase_vjp': lambda: op._obs(t.y)}.get(name, lambda: None)()
+    t.obs = {'data_cs_vjp': lambda: op.spectrum_observation(t.y), 'data_srconv_vjp': lambda: op._observation(t.y, t.xt.shape),
+             'data_spectral_vjp': lambda: op._observation(t.y, t.xt.shape), 'data_phase_vjp': lambda: op._observation(t.y, t.xt.shape)}.get(name, lambda: None)()
     good = torch.full((1, 6, d, d), 7.0, device='cuda')
     _, _, g_e = call(K, op, t, good)                               # the case itself is a valid call ...
     assert g_e is good and not bool((good[:, :3] == 7.0).all())
