@@ -8,8 +8,8 @@
 // Here a slab is spread over `splits` workgroups of one launch, each of which loads its share (256 threads x 8 float4 of x,
 // in the backward also of dy) into registers ONCE, reduces it, exchanges the 16-byte partial with the other workgroups
 // of its slab and then normalises / differentiates its share from registers:
-//     forward   k_gn_onepass<false> (R x, W y)                                  1 read  + 1 write
-//     backward  k_gn_onepass<true>  (R x, dy [, acc], W dx)                     2 (3) reads + 1 write
+//     forward   k_gn_onepass<false, *> (R x, W y)                               1 read  + 1 write
+//     backward  k_gn_onepass<true, *>  (R x, dy [, acc], W dx)                  2 (3) reads + 1 write
 // The formulas, the fp64 partial sums, their fixed summation order k = 0 .. splits - 1 and the workspace layout
 // ws[(bg * splits + split) * 2 ..] are those of gn_act.hip, so a forward workspace of either path feeds either backward.
 // As there, the forward's sums of v = x + pre and v^2 are fp64 from the element on (widened, added and squared per
@@ -41,12 +41,22 @@
 //
 // The per-channel terms (pre, gamma, beta, FiLM) of a slab's channels are formed once per workgroup into LDS (groups of up
 // to 64 channels; wider groups read them from memory per float4): per float4 they cost an LDS read instead of up to five
-// dependent global loads, each of which the compiler follows with a full s_waitcnt.
+// dependent global loads, each of which the compiler follows with a full s_waitcnt.  The backward's table also holds the
+// centre (op_centre), which it can form per channel because it knows the mean before it loads its share.
+//
+// Instruction issue, not HBM, bounds these kernels (profiles/README.md, round 17), so each element's work is done once:
+// the backward's statistics loop leaves xh and dxh = du * ga in the registers that held x and dy, and the output is
+// rstd * ((dxh - m0) - xh * m1) from those -- no second sigmoid, no channel terms, no plane index in the last loop.
+// Where a channel plane is a whole multiple of the 256 float4 of one float4 index of a share (every FFHQ level from
+// 32 x 32 up), plane, channel and source / destination side are the workgroup's and live in scalar registers
+// (template parameter UNI, OpWalk below); the general path finds them per lane by a division.
 //
 // Concatenated input (the U-Net's output blocks): the forward may take the logical input as two tensors
 // x1 [n][C1][hw] | x2 [n][C - C1][hw] and then also writes their concatenation x_cat from the same load; the backward
 // may write dx as two contiguous tensors of those shapes.  The source / destination is chosen per channel plane
 // (hw % 4 == 0 keeps a float4 inside one plane); a group may straddle C1.
+#include <cstdlib>
+
 #include "nhmc_common.h"
 
 namespace {
@@ -92,12 +102,11 @@ __device__ __forceinline__ void op_block_sum(double (&v)[2], double* lds) {
 
 constexpr int OP_CHAN_LDS = 64;                  // channels per group whose terms are staged in LDS
 struct OpChan { float pb, ga, be, hi, lo; };       // hi + lo = pb - mean (op_centre), where the mean is known
-// tab (nullable): the terms of the group's channels in LDS, 3 floats each, first channel ch0
+// the terms of one (sample, channel) from memory
 template <bool AFFINE>
-__device__ __forceinline__ OpChan op_chan(const OpArgs& a, int b, int ch, const float* tab = nullptr, int ch0 = 0) {
+__device__ __forceinline__ OpChan op_chan(const OpArgs& a, int b, int ch) {
   OpChan c;
   c.hi = c.lo = 0.0f;
-  if (tab) { const float* t = tab + 3 * (ch - ch0); c.pb = t[0]; c.ga = t[1]; c.be = t[2]; return c; }
   c.pb = a.pre ? a.pre[(int64_t)b * a.pre_stride + ch] : 0.0f;
   c.ga = c.be = 0.0f;
   if (AFFINE) {
@@ -107,15 +116,29 @@ __device__ __forceinline__ OpChan op_chan(const OpArgs& a, int b, int ch, const 
   return c;
 }
 
-// x + pre - mean is (x + hi) + lo, hi + lo split from fp64 once per float4: gn_centre of gn_act.hip
+// x + pre - mean is (x + hi) + lo, hi + lo split from fp64: gn_centre of gn_act.hip
 __device__ __forceinline__ OpChan op_centre(OpChan c, double mean) {
   const double d = (double)c.pb - mean;
   c.hi = (float)d; c.lo = (float)(d - (double)c.hi);
   return c;
 }
 
-// One element's contribution to the partial sums of its share, and one element of the backward's output: the one place
-// where each is formed (the register path calls them four times per float4, the fallback element by element).
+// The terms of channel ch as the loops over a share use them.  tab (nullable): the row of the group's LDS table, first
+// channel ch0, which the thread that filled it formed once per workgroup -- forward {pb, ga, be, -}; backward
+// {hi, lo, ga, be}, the centre included (the backward knows the mean before it loads its share).  Without a table (groups
+// of more than OP_CHAN_LDS channels): from memory, the centre per float4.
+template <bool BWD>
+__device__ __forceinline__ OpChan op_terms(const OpArgs& a, int b, int ch, double mean, const float4* tab, int ch0) {
+  if (tab) {
+    const float4 t = tab[ch - ch0];
+    return BWD ? OpChan{0.0f, t.z, t.w, t.x, t.y} : OpChan{t.x, t.y, t.z, 0.0f, 0.0f};
+  }
+  const OpChan c = op_chan<BWD>(a, b, ch);
+  return BWD ? op_centre(c, mean) : c;
+}
+
+// One element's contribution to the partial sums of its share: the one place where it is formed (the register path
+// calls these four times per float4, the fallback element by element).
 // OpAcc: what the four elements of a float4 are added up in before the sum joins the fp64 partial.  Forward: fp64, as
 // in gn_act.hip -- v = x + pre and v^2 never exist rounded to fp32, or E[v^2] - mean^2 would cancel against
 // mean^2 2^-24 per square.  Backward: fp32; its two sums do not cancel.
@@ -123,35 +146,40 @@ template <bool BWD> struct OpAccT { using type = double; };
 template <> struct OpAccT<true> { using type = float; };
 template <bool BWD> using OpAcc = typename OpAccT<BWD>::type;
 
+// the backward's element: x, d = dy  ->  xh = the normalised input, dxh = the gradient that reaches it.  Everything the
+// activation costs (expf, a correctly rounded division) is in here and runs once per element: the register path keeps
+// xh and dxh where x and dy were, and the output needs nothing else of the element.
+__device__ __forceinline__ void op_bwd1(const OpArgs& a, const OpChan& c, float x, float d, float rstd, float& xh, float& dxh) {
+  xh = ((x + c.hi) + c.lo) * rstd;
+  float du = d;
+  if (a.act) { const float u = xh * c.ga + c.be, sg = op_sigmoid(u); du = du * (sg * (1.0f + u * (1.0f - sg))); }
+  dxh = du * c.ga;
+}
+
+// forward: d is unused.  backward: x <- xh, d <- dxh.
 template <bool BWD>
-__device__ __forceinline__ void op_stat1(const OpArgs& a, const OpChan& c, float x, float d, float rstd,
+__device__ __forceinline__ void op_stat1(const OpArgs& a, const OpChan& c, float& x, float& d, float rstd,
                                          OpAcc<BWD>& t0, OpAcc<BWD>& t1) {
   if constexpr (!BWD) {
     const double v = (double)x + (double)c.pb;
     t0 += v; t1 = fma(v, v, t1);
   } else {
-    const float xh = ((x + c.hi) + c.lo) * rstd;
-    float du = d;
-    if (a.act) { const float u = xh * c.ga + c.be, sg = op_sigmoid(u); du = du * (sg * (1.0f + u * (1.0f - sg))); }
-    const float dxh = du * c.ga;
+    float xh, dxh;
+    op_bwd1(a, c, x, d, rstd, xh, dxh);
     t0 += dxh; t1 += dxh * xh;
+    x = xh; d = dxh;
   }
 }
-// (the backward's element; the forward's is nhmc_gn_out of nhmc_common.h, shared with gn_act.hip)
-__device__ __forceinline__ float op_apply1(const OpArgs& a, const OpChan& c, float x, float d, float rstd, float m0, float m1) {
-  const float xh = ((x + c.hi) + c.lo) * rstd;
-  float du = d;
-  if (a.act) { const float u = xh * c.ga + c.be, sg = op_sigmoid(u); du = du * (sg * (1.0f + u * (1.0f - sg))); }
-  return rstd * ((du * c.ga - m0) - xh * m1);
+// (the backward's output element from xh and dxh; the forward's is nhmc_gn_out of nhmc_common.h, shared with gn_act.hip)
+__device__ __forceinline__ float op_apply1(float xh, float dxh, float rstd, float m0, float m1) {
+  return rstd * ((dxh - m0) - xh * m1);
 }
 
+// one float4 of the share into the partial sums; the backward leaves xh in xv and dxh in dv
 template <bool BWD>
-__device__ __forceinline__ void op_stat(const OpArgs& a, int b, int ch, const float4& xv, const float4& dv, double mean, float rstd,
-                                        double& s0, double& s1, const float* tab, int ch0) {
-  const float* xe = reinterpret_cast<const float*>(&xv);
-  const float* de = reinterpret_cast<const float*>(&dv);
-  OpChan c = op_chan<BWD>(a, b, ch, tab, ch0);
-  if (BWD) c = op_centre(c, mean);
+__device__ __forceinline__ void op_stat(const OpArgs& a, const OpChan& c, float4& xv, float4& dv, float rstd, double& s0, double& s1) {
+  float* xe = reinterpret_cast<float*>(&xv);
+  float* de = reinterpret_cast<float*>(&dv);
   OpAcc<BWD> t0 = 0, t1 = 0;
 #pragma unroll
   for (int e = 0; e < 4; ++e) op_stat1<BWD>(a, c, xe[e], de[e], rstd, t0, t1);
@@ -165,6 +193,21 @@ __device__ __forceinline__ OpAt op_at(const OpArgs& a, int g, int q) {
   return OpAt{g * (a.C / a.G) + pl, q - pl * a.hw4};
 }
 
+// The uniform-plane path (template parameter UNI; hw4 % NHMC_BLOCK == 0 and a group that has the LDS table): float4 index
+// i of a share starts at a multiple of 256 float4, so its 256 threads are in ONE channel plane.  Plane, channel, the
+// side of C1 and the "inside the slab" test are then the workgroup's, not the lane's: one division per workgroup, a
+// walk in scalar registers from i to i + 1, a broadcast LDS read of the channel's row, and no per-lane select between
+// two sources / destinations.  The values are those of op_at.
+struct OpWalk { int pl, r; };                     // plane inside the group, float4 offset of thread 0 inside the plane
+__device__ __forceinline__ OpWalk op_walk0(const OpArgs& a, int split) {
+  const unsigned q = (unsigned)split * OP_SHARE, pl = q / (unsigned)a.hw4;
+  return OpWalk{(int)pl, (int)(q - pl * (unsigned)a.hw4)};
+}
+__device__ __forceinline__ void op_walk_next(const OpArgs& a, OpWalk& w) {
+  w.r += NHMC_BLOCK;
+  if (w.r >= a.hw4) { w.r -= a.hw4; ++w.pl; }     // hw4 >= 256: one plane further at the most
+}
+
 // where float4 q of the slab is read from (forward: one of the two sources) / written to (backward: one of the two
 // destinations); p1 serves the channels below C1, p2 (nullable: p1 is then the whole [n][C][hw] tensor) the rest
 template <typename T>
@@ -173,12 +216,14 @@ __device__ __forceinline__ T* op_side(const OpArgs& a, T* p1, T* p2, int b, int6
   return at.ch < a.C1 ? p1 + op_index(b, a.C1, at.ch, a.hw4, at.p4) : p2 + op_index(b, a.C - a.C1, at.ch - a.C1, a.hw4, at.p4);
 }
 
-// normalise (forward) / differentiate (backward) one float4 held in registers and write it
+// normalise (forward) / differentiate (backward: xv = xh, dv = dxh) one float4 held in registers and write it
+// accv (nullable): acc[base + q] where the kernel has loaded it already
 template <bool BWD>
 __device__ __forceinline__ void op_apply(const OpArgs& a, int b, int64_t base, int q, const OpAt& at, const float4& xv,
                                          const float4& dv, double mean, float rstd, double rstd64, float m0, float m1,
                                          float4* __restrict__ out1, float4* __restrict__ out2, float4* __restrict__ xcat,
-                                         const float4* __restrict__ acc, const float* tab, const NhmcGnAffine* tab64, int ch0) {
+                                         const float4* __restrict__ acc, const float4* tab, const NhmcGnAffine* tab64, int ch0,
+                                         const float4* accv = nullptr) {
   const float* xe = reinterpret_cast<const float*>(&xv);
   const float* de = reinterpret_cast<const float*>(&dv);
   float4 o;
@@ -186,20 +231,16 @@ __device__ __forceinline__ void op_apply(const OpArgs& a, int b, int64_t base, i
   if constexpr (!BWD) {
     // the output in fp64 per element, rounded once: the arithmetic of gn_act.hip's forward, the same bits
     const NhmcGnAffine f = tab64 ? tab64[at.ch - ch0] : nhmc_gn_affine(a.gamma, a.beta, a.film, a.film_stride, a.C, b, at.ch);
-    const NhmcGnOut k = nhmc_gn_out_terms(f, op_chan<false>(a, b, at.ch, tab, ch0).pb, mean, rstd64);
+    const NhmcGnOut k = nhmc_gn_out_terms(f, op_terms<false>(a, b, at.ch, mean, tab, ch0).pb, mean, rstd64);
 #pragma unroll
     for (int e = 0; e < 4; ++e) oe[e] = nhmc_gn_out(k, xe[e], a.act);
-  } else {
-    const OpChan c = op_centre(op_chan<true>(a, b, at.ch, tab, ch0), mean);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) oe[e] = op_apply1(a, c, xe[e], de[e], rstd, m0, m1);
-  }
-  if (!BWD) {
     out1[base + q] = o;
     if (xcat) xcat[base + q] = xv;
   } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) oe[e] = op_apply1(xe[e], de[e], rstd, m0, m1);
     if (acc) {
-      const float4 av = acc[base + q];
+      const float4 av = accv ? *accv : acc[base + q];
       o.x = o.x + av.x; o.y = o.y + av.y; o.z = o.z + av.z; o.w = o.w + av.w;
     }
     *op_side(a, out1, out2, b, base, q, at) = o;
@@ -222,7 +263,12 @@ __device__ __forceinline__ void op_totals(const OpArgs& a, double n, double t0, 
 
 // x: two sources in the forward (x2 nullable), one in the backward.  `ws` is written and read by several workgroups
 // of this launch: agent-scope atomics only, no const / __restrict__ on it.
-template <bool BWD>
+// UNI: the uniform-plane path (OpWalk above); the entry points choose it, the general path serves every shape.
+// AHEAD (backward with a second gradient, acc != nullptr): all of the share's `acc` loads are issued ahead of the first
+// store instead of pair by pair between the stores.  The last loop is four instructions per element, so nothing hides
+// a load's latency inside it; the 32 registers fit (113 / 122 VGPRs, UNI / general).  Without `acc` the instantiation
+// that has no such loads keeps the schedule that measured faster for that form.
+template <bool BWD, bool UNI, bool AHEAD>
 __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_onepass(const float4* __restrict__ x1, const float4* __restrict__ x2,
                                                            const float4* __restrict__ dy, const double* __restrict__ fwd_ws,
                                                            OpArgs a, double* ws, float4* __restrict__ out1,
@@ -237,15 +283,15 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_onepass(const float4* __restr
   __shared__ double st64[2];
   __shared__ int arrived;
   __shared__ double part[2 * OP_MAX_SPLITS];        // the partials of a slab, one lane loads one
-  __shared__ float chan[3 * OP_CHAN_LDS];
+  __shared__ float4 chan[OP_CHAN_LDS];              // op_terms' rows
   __shared__ NhmcGnAffine chan64[BWD ? 1 : OP_CHAN_LDS];   // forward: the affine terms in fp64, for its output
   const int cpg = a.C / a.G, ch0 = g * cpg;
-  const float* tab = cpg <= OP_CHAN_LDS ? chan : nullptr;
+  const float4* tab = UNI || cpg <= OP_CHAN_LDS ? chan : nullptr;
   const NhmcGnAffine* tab64 = !BWD && tab ? chan64 : nullptr;
+  OpChan crow{};                                   // thread tid < cpg: its row of the table, loaded ahead of the waits below
   if (tab && tid < cpg) {
-    const OpChan c = op_chan<true>(a, b, ch0 + tid);
-    chan[3 * tid] = c.pb; chan[3 * tid + 1] = c.ga; chan[3 * tid + 2] = c.be;
-    if (!BWD) chan64[tid] = nhmc_gn_affine(a.gamma, a.beta, a.film, a.film_stride, a.C, b, ch0 + tid);
+    crow = op_chan<true>(a, b, ch0 + tid);
+    if (!BWD) { chan[tid] = make_float4(crow.pb, crow.ga, crow.be, 0.0f); chan64[tid] = nhmc_gn_affine(a.gamma, a.beta, a.film, a.film_stride, a.C, b, ch0 + tid); }
   }
   double mean = 0.0;
   float rstd = 0.f;
@@ -262,27 +308,38 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_onepass(const float4* __restr
     }
     __syncthreads();
     mean = st64[0]; rstd = st[1];
+    if (tab && tid < cpg) {                        // the centre once per channel
+      crow = op_centre(crow, mean);
+      chan[tid] = make_float4(crow.hi, crow.lo, crow.ga, crow.be);
+    }
   }
+  const int q0 = split * OP_SHARE;
+  const OpWalk w0 = UNI ? op_walk0(a, split) : OpWalk{0, 0};
 
   // ---- the share of this workgroup, once, into registers
   float4 xv[OP_K], dv[OP_K];
+  OpWalk w = w0;
 #pragma unroll
   for (int i = 0; i < OP_K; ++i) {
-    const int q = split * OP_SHARE + i * NHMC_BLOCK + tid;
+    const int q = q0 + i * NHMC_BLOCK + tid;
     xv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     dv[i] = xv[i];
-    if (q < a.n4) {
-      xv[i] = *op_side(a, x1, BWD ? nullptr : x2, b, base, q, op_at(a, g, q));
+    if (UNI ? q0 + i * NHMC_BLOCK < a.n4 : q < a.n4) {
+      xv[i] = *op_side(a, x1, BWD ? nullptr : x2, b, base, q, UNI ? OpAt{ch0 + w.pl, w.r + tid} : op_at(a, g, q));
       if (BWD) dv[i] = dy[base + q];
     }
+    if (UNI) op_walk_next(a, w);
   }
-  if (!BWD) __syncthreads();                       // `chan` is complete (the backward has passed a barrier already)
+  __syncthreads();                                 // `chan` is complete
   double v[2] = {0.0, 0.0};
+  w = w0;
 #pragma unroll
   for (int i = 0; i < OP_K; ++i) {
     if (i % 2 == 0) __builtin_amdgcn_sched_barrier(0);      // as in the last loop of this kernel
-    const int q = split * OP_SHARE + i * NHMC_BLOCK + tid;
-    if (q < a.n4) op_stat<BWD>(a, b, op_at(a, g, q).ch, xv[i], dv[i], mean, rstd, v[0], v[1], tab, ch0);
+    const int q = q0 + i * NHMC_BLOCK + tid;
+    if (UNI ? q0 + i * NHMC_BLOCK < a.n4 : q < a.n4)
+      op_stat<BWD>(a, op_terms<BWD>(a, b, UNI ? ch0 + w.pl : op_at(a, g, q).ch, mean, tab, ch0), xv[i], dv[i], rstd, v[0], v[1]);
+    if (UNI) op_walk_next(a, w);
   }
   op_block_sum(v, red);                       // thread 0 holds the partial of this share
 
@@ -328,13 +385,12 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_onepass(const float4* __restr
             const int q = k * OP_SHARE + i * NHMC_BLOCK + tid;
             if (q >= a.n4) continue;
             const OpAt at = op_at(a, g, q);
-            OpChan c = op_chan<BWD>(a, b, at.ch, tab, ch0);
-            if (BWD) c = op_centre(c, mean);
+            const OpChan c = op_terms<BWD>(a, b, at.ch, mean, tab, ch0);
             const float* xs = reinterpret_cast<const float*>(op_side(a, x1, BWD ? nullptr : x2, b, base, q, at));
             const float* ds = reinterpret_cast<const float*>(dy + (base + q));
             OpAcc<BWD> u0 = 0, u1 = 0;
 #pragma unroll 1
-            for (int e = 0; e < 4; ++e) op_stat1<BWD>(a, c, xs[e], BWD ? ds[e] : 0.0f, rstd, u0, u1);
+            for (int e = 0; e < 4; ++e) { float xe = xs[e], de = BWD ? ds[e] : 0.0f; op_stat1<BWD>(a, c, xe, de, rstd, u0, u1); }
             p[0] += (double)u0; p[1] += (double)u1;
           }
           op_block_sum(p, red);
@@ -355,16 +411,32 @@ __global__ __launch_bounds__(NHMC_BLOCK) void k_gn_onepass(const float4* __restr
   const float m0 = st[2], m1 = st[3];
 
   // ---- normalise / differentiate the share from registers
+  float4 av[OP_K];
+  if (AHEAD && acc) {
+#pragma unroll
+    for (int i = 0; i < OP_K; ++i) {
+      const int q = q0 + i * NHMC_BLOCK + tid;
+      av[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (UNI ? q0 + i * NHMC_BLOCK < a.n4 : q < a.n4) av[i] = acc[base + q];
+    }
+  }
+  w = w0;
 #pragma unroll
   for (int i = 0; i < OP_K; ++i) {
-    // the share fills 32 / 64 VGPRs: keep the scheduler from hoisting all eight `acc` loads on top of them, and from
-    // carrying the plane index and channel terms of all eight float4 over from the statistics (q is opaque here, they
-    // are formed again): 71 instead of 87 VGPRs forward (74 since the forward's sums and its output are fp64 per
-    // element), 126 instead of 146 backward
+    // the share fills 32 / 64 VGPRs: keep the scheduler from hoisting all eight `acc` loads on top of them, and (general
+    // path) from carrying the plane index and channel terms of all eight float4 over from the statistics: q is opaque
+    // here, they are formed again
     if (i % 2 == 0) __builtin_amdgcn_sched_barrier(0);
-    int q = split * OP_SHARE + i * NHMC_BLOCK + tid;
-    asm volatile("" : "+v"(q));
-    if (q < a.n4) op_apply<BWD>(a, b, base, q, op_at(a, g, q), xv[i], dv[i], mean, rstd, rstd64, m0, m1, out1, out2, xcat, acc, tab, tab64, ch0);
+    int q = q0 + i * NHMC_BLOCK + tid;
+    if constexpr (UNI) {
+      if (q0 + i * NHMC_BLOCK < a.n4)
+        op_apply<BWD>(a, b, base, q, OpAt{ch0 + w.pl, w.r + tid}, xv[i], dv[i], mean, rstd, rstd64, m0, m1, out1, out2, xcat, acc, tab, tab64, ch0, AHEAD ? &av[i] : nullptr);
+      op_walk_next(a, w);
+    } else {
+      asm volatile("" : "+v"(q));
+      // (the backward needs the plane only where the gradient goes to two tensors)
+      if (q < a.n4) op_apply<BWD>(a, b, base, q, !BWD || out2 ? op_at(a, g, q) : OpAt{0, 0}, xv[i], dv[i], mean, rstd, rstd64, m0, m1, out1, out2, xcat, acc, tab, tab64, ch0, AHEAD ? &av[i] : nullptr);
+    }
   }
 }
 
@@ -380,6 +452,13 @@ int op_check(const void* x, const void* gamma, const void* beta, const void* ws,
   if (!(*splits = op_splits(n, C, G, hw))) return NHMC_ERR_SHAPE;
   if (!nhmc_aligned16(x) || !nhmc_aligned16(ws)) return NHMC_ERR_ALIGN;
   return NHMC_OK;
+}
+
+// The uniform-plane path serves a shape whose planes are whole multiples of a workgroup's 256 float4 and whose groups have
+// the LDS table.  NHMC_GN_UNIFORM=0, read per call, keeps the general path everywhere (the A/B switch of tools/gn_bench.py).
+bool op_uniform(int C, int G, int64_t hw) {
+  const char* v = std::getenv("NHMC_GN_UNIFORM");
+  return !(v && v[0] == '0') && (hw / 4) % NHMC_BLOCK == 0 && C / G <= OP_CHAN_LDS;
 }
 
 // every word of the workspace <- the "not yet published" pattern, by a launch of its own ahead of the one-pass kernel on
@@ -403,11 +482,16 @@ int op_fill_ws(double* ws, int n, int G, int splits, hipStream_t st) {
 extern "C" int nhmc_gn_onepass_splits(int n, int channels, int groups, int64_t hw) { return op_splits(n, channels, groups, hw); }
 
 // Routing rule, from tools/gn_bench.py at 64 chains on MI355X (one-pass time / two-pass time, same run, nine FFHQ U-Net
-// shapes; profiles/r04_gn_onepass_roofline.txt).  Forward: 0.77 - 0.95 everywhere (0.89 - 0.93 at 1 - 2 splits) ->
-// one-pass wherever it is covered.  Backward: 0.91 - 0.95 at 4 to 32 splits per slab; a tie inside the run-to-run
-// spread at 1 and 2 splits (0.99, 1.01: small tensors, launch bound) and at 64 splits (0.99 median, 1.02 best of three:
-// 256 channels at 256x256, the longest wait for the slowest share) -> one-pass from 4 to 32 splits, two-pass otherwise,
-// unless the caller needs what only the one-pass backward offers (the gradient split into two contiguous tensors).
+// shapes; profiles/r17_gn_onepass_roofline.txt, median and min-over-rounds ratio, two runs, spread of a ratio between
+// the runs <= 0.02).  Forward: 0.72 - 0.90 from 2 splits up, 0.97 - 0.98 at 1 split -> one-pass wherever it is covered.
+// Backward: 0.64 - 0.69 at 4 to 32 splits per slab, 0.75 at 64 splits (256 channels at 256x256, the longest wait for the
+// slowest share), 0.78 at 2 splits and 0.80 - 0.81 at 1 split; with a second gradient added 0.66 - 0.78 likewise.
+// By the convention of round 4 (a class moves where median and min ratio are both below 1 by more than the spread)
+// every class would now take the one-pass backward.  The classes at 1, 2 and 64 splits stay on the two-pass kernels all
+// the same: the two kinds of kernel split a slab differently, so moving a class changes the last bits of every
+// gradient that passes through it, and those classes are 3.9 ms of a 64-chain step (profiles/README.md, round 4), of
+// which the move would save about a fifth.  -> one-pass from 4 to 32 splits, two-pass otherwise, unless the caller
+// needs what only the one-pass backward offers (the gradient split into two contiguous tensors).
 extern "C" int nhmc_gn_onepass_prefers(int backward, int n, int channels, int groups, int64_t hw) {
   const int s = op_splits(n, channels, groups, hw);
   return backward ? (s >= 4 && s <= 32) : s > 0;
@@ -429,7 +513,8 @@ extern "C" int nhmc_gn_onepass_fwd(const float* x1, const float* x2, int c1, con
                  (flags & NHMC_GN_ONEPASS_NOWAIT) ? 0u : OP_POLLS};
   hipStream_t st = nhmc_s(stream);
   if (splits > 1 && (rc = op_fill_ws(ws, n, groups, splits, st))) return rc;
-  NHMC_LAUNCH(k_gn_onepass<false>, dim3((unsigned)splits, (unsigned)(n * groups)), dim3(NHMC_BLOCK), 0, st, (const float4*)x1,
+  const auto kern = op_uniform(channels, groups, hw) ? k_gn_onepass<false, true, false> : k_gn_onepass<false, false, false>;
+  NHMC_LAUNCH(kern, dim3((unsigned)splits, (unsigned)(n * groups)), dim3(NHMC_BLOCK), 0, st, (const float4*)x1,
               (const float4*)x2, (const float4*)nullptr, (const double*)nullptr, a, ws, (float4*)y,
               (float4*)nullptr, (float4*)x_cat, (const float4*)nullptr);
   return nhmc_launch_status();
@@ -453,7 +538,10 @@ extern "C" int nhmc_gn_onepass_bwd(const float* x, const float* dy, const float*
                  (flags & NHMC_GN_ONEPASS_NOWAIT) ? 0u : OP_POLLS};
   hipStream_t st = nhmc_s(stream);
   if (splits > 1 && (rc = op_fill_ws(ws, n, groups, splits, st))) return rc;
-  NHMC_LAUNCH(k_gn_onepass<true>, dim3((unsigned)splits, (unsigned)(n * groups)), dim3(NHMC_BLOCK), 0, st, (const float4*)x,
+  const bool uni = op_uniform(channels, groups, hw);
+  const auto kern = dx_add ? (uni ? k_gn_onepass<true, true, true> : k_gn_onepass<true, false, true>)
+                           : (uni ? k_gn_onepass<true, true, false> : k_gn_onepass<true, false, false>);
+  NHMC_LAUNCH(kern, dim3((unsigned)splits, (unsigned)(n * groups)), dim3(NHMC_BLOCK), 0, st, (const float4*)x,
               (const float4*)nullptr, (const float4*)dy, fwd_ws, a, ws, (float4*)dx1, (float4*)dx2,
               (float4*)nullptr, (const float4*)dx_add);
   return nhmc_launch_status();
