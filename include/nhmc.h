@@ -376,6 +376,30 @@ int nhmc_data_phase_vjp(const float* xt_next, const float* y, const float* fac, 
                         int e_channels, const float* at, const float* at_next, float* g_xt, float* g_e, double* loss_ws,
                         float* tmp, int n_chains, int channels, int dim, int pad, nhmc_stream_t stream);
 
+/* Fourier sampling (--deg mri<R>, --deg fourier): undersampled k-space, partial Fourier, band-limited optics.  Not in the
+ * reference.  The linear, weighted use of the spectrum above at pad = 0: with F = Cm + i Sm the centred orthonormal DFT
+ * matrix of size dim (dim % 32 == 0) and Y_c = F X_c F^T per channel plane,
+ *     H(x)   = [w o Re Y ; w o Im Y]                      [n_chains][C][2][dim][dim],  M = 2 C dim^2,
+ *     H^T(v) = Re[F^H (w o (v_re + i v_im)) conj(F)]       = nhmc_phase_adjoint(w o v, pad = 0),
+ * w: float[dim][dim], every entry >= 0 and finite (the caller checks), centred layout (DC at [dim/2][dim/2]), one map for
+ * all channels and chains; a binary mask is the common case.  fac, tmp and the loss partials are those of the phase
+ * entries at pad = 0: float[6 dim dim], nhmc_phase_tmp_floats(n_chains, C, dim, 0), nhmc_phase_tiles(C, dim, 0).
+ *   nhmc_fourier_H       : out = H(x).
+ *   nhmc_data_fourier    : r = y - H(v) where w > 0 and EXACTLY 0 where w = 0 -- a selection, not a product, so that the
+ *                          unmeasured entries of y (noise, NaN, inf) reach neither the loss nor the gradient; a NaN in a
+ *                          measured entry propagates.  Loss partials of sum r^2 (fp32 squares summed in fp64), and
+ *                          g_xt = -2 H^T r, times the clip mask of xt when apply_clip (v = clip(xt) then).
+ *   nhmc_data_fourier_vjp: the same on xt_next (the clipped decode of the LAST DDIM step) with that step's VJP in the
+ *                          last product's epilogue (as nhmc_data_phase_vjp): writes g_xt and channels [0, C) of g_e.
+ * Return codes as everywhere: NHMC_ERR_ARG for a null pointer, NHMC_ERR_SHAPE (dim % 32, e_channels), NHMC_ERR_ALIGN. */
+int nhmc_fourier_H(const float* x, const float* fac, const float* w, float* out, float* tmp, int n_chains, int channels,
+                   int dim, nhmc_stream_t stream);
+int nhmc_data_fourier(const float* xt, const float* y, const float* fac, const float* w, int apply_clip, float* g_xt,
+                      double* loss_ws, float* tmp, int n_chains, int channels, int dim, nhmc_stream_t stream);
+int nhmc_data_fourier_vjp(const float* xt_next, const float* y, const float* fac, const float* w, const float* xt,
+                          const float* e, int e_channels, const float* at, const float* at_next, float* g_xt, float* g_e,
+                          double* loss_ws, float* tmp, int n_chains, int channels, int dim, nhmc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * General 2-D PSF blur (--deg deblur_motion): camera shake, defocus, any measured PSF.  Not in the reference's
  * prepare_measurement (its README names an external motion-blur generator that is never wired); the two blurs it has

@@ -74,6 +74,9 @@ SIGNATURES = {
     'nhmc_phase_adjoint': (I, [P, P, P, P, I, I, I, I, P]),
     'nhmc_data_phase': (I, [P, P, P, I, P, P, P, I, I, I, I, P]),
     'nhmc_data_phase_vjp': (I, [P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, P]),
+    'nhmc_fourier_H': (I, [P, P, P, P, P, I, I, I, P]),
+    'nhmc_data_fourier': (I, [P, P, P, P, I, P, P, P, I, I, I, P]),
+    'nhmc_data_fourier_vjp': (I, [P, P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, P]),
     'nhmc_blur2d_check_taps': (I, [P, I, I]),
     'nhmc_blur2d_tiles': (I, [I, I]),
     'nhmc_blur2d_apply': (I, [P, P, P, I, I, I, P, I, I, I, P]),

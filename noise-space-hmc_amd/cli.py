@@ -27,6 +27,14 @@ sparse-operator kernels (operators.SparseLinear).  `--deg sparse --operator FILE
 forward model: FILE.npz holds a CSR matrix [m, image_size^2] in the layout `scipy.sparse.save_npz` writes (`data`,
 `indices`, `indptr`, `shape`), applied to every channel plane alike; it is read with numpy alone.
 
+`--deg mri<R>` (not in the reference) is Cartesian accelerated MRI at acceleration R: the centred orthonormal 2-D DFT of
+every channel plane, kept on image_size // R whole columns of k-space (operators.cartesian_mask, drawn from the global
+torch RNG right after the seed is set, so every rank holds the same mask), through the Fourier-sampling kernels
+(operators.FourierSampling); the measurement is [Re ; Im] per plane, M = 2 C image_size^2, read only where the mask is
+set.  `--deg fourier --kspace_mask FILE.npy` takes any real weight map [image_size, image_size] (>= 0, DC at the centre)
+instead: partial Fourier, band limits, a measured sampling density.  With `--save_images` rank 0 also writes
+`kspace_mask.png`, the weights scaled to their maximum, once.
+
 `--replicas K` spends the chains on K replica chains per image instead (a batch then holds `--chains` // K images, chain
 i * K + r being replica r of the batch's image i): all replicas see the same measurement, replica 0 starts where the
 single chain starts, replicas r >= 1 start from their own N(0,1) draw keyed by (seed, s, r), and the Philox stream of
@@ -100,6 +108,9 @@ def get_parser(latent=False):
     p.add_argument('--operator', type=str, default=None, metavar='FILE.npz',
                    help='--deg sparse: the forward model as a CSR matrix [m, image_size^2] in the layout scipy.sparse.save_npz '
                         'writes (data, indices, indptr, shape), applied to every channel plane')
+    p.add_argument('--kspace_mask', type=str, default=None, metavar='FILE.npy',
+                   help='--deg fourier: the k-space weight map, a real [image_size, image_size] array (>= 0, DC at the '
+                        'centre; a binary mask is the common case), shared by all channels')
     p.add_argument('--graph', dest='use_graph', action='store_true',
                    help='replay each decode+gradient chunk as a hipGraph (helps single-chain runs: ~1.2x)')
     p.add_argument('--hmc_epochs', type=int, default=60, help='annealing epochs (reference: 60, main_sampling.py:665)')
@@ -269,11 +280,19 @@ def _setup(opt, latent):
     size, ch = config['data']['image_size'], config['data']['channels']
     # mask = first torch RNG draw, as in the reference
     operator_file = getattr(opt, 'operator', None)
+    kspace_mask_file = getattr(opt, 'kspace_mask', None)
     if opt.deg == 'sparse' or operator_file:
         if opt.deg != 'sparse' or not operator_file:
             raise SystemExit('--deg sparse and --operator FILE.npz go together')
         try:
             op = operators.build_operator(opt.deg, ch, size, device, operator_file=operator_file)
+        except operators.NhmcError as exc:
+            raise SystemExit(str(exc))
+    elif opt.deg == 'fourier' or kspace_mask_file or (opt.deg.startswith('mri') and opt.deg[3:].isdigit()):
+        if (opt.deg == 'fourier') != bool(kspace_mask_file):
+            raise SystemExit('--deg fourier and --kspace_mask FILE.npy go together')
+        try:
+            op = operators.build_operator(opt.deg, ch, size, device, kspace_mask_file=kspace_mask_file)
         except operators.NhmcError as exc:
             raise SystemExit(str(exc))
     else:
@@ -283,6 +302,9 @@ def _setup(opt, latent):
         span = float(k.max() - k.min())
         k01 = (k - k.min()) / span if span > 0 else torch.ones_like(k)
         sampler._save_png((2 * k01 - 1)[None].expand(3, -1, -1), os.path.join(opt.image_folder, 'blur_kernel.png'))
+    if opt.save_images and rank == 0 and isinstance(op, operators.FourierSampling):
+        w01 = op.weights / op.weights.max()                                 # max > 0: the constructor checked
+        sampler._save_png((2 * w01 - 1)[None].expand(3, -1, -1), os.path.join(opt.image_folder, 'kspace_mask.png'))
     opt.sigma_0 = 2 * opt.sigma_0                                           # [-1,1] scaling, main_sampling.py:348
     if world > 1 and not opt.philox:
         if rank == 0:

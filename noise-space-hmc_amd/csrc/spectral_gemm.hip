@@ -877,14 +877,36 @@ extern "C" int nhmc_data_srconv_vjp(const float* xt_next, const float* y, const 
 // k_cgemm: one complex-shaped product  P = A^T SA - B^T SB,  Q = A^T SB + B^T SA   (A, B: [K][R] rows of ld_in floats
 // per image; SA, SB: [K][C] rows of ld_s floats, shared).  Block tile T x T = (32 NW)^2, one 32 x 32 MFMA tile of P and
 // of Q per wave, K step 32, the four operand tiles staged through LDS as in k_sgemm (T = 64: 32 KB, four blocks per CU).
-enum { PEPI_PAIR = 0, PEPI_MOD = 1, PEPI_RESID = 2 };
+// Fourier sampling (below) adds two epilogues on the same spectrum, with a weight map w [R][C] >= 0 shared by all images:
+//   PEPI_WPAIR : out = [w o P ; w o Q]
+//   PEPI_WRESID: y = the observation pair [img][2][R][C];  r = y - w o (P, Q) where w > 0, exactly 0 elsewhere (a SELECT:
+//                whatever the unmeasured entries of y hold never reaches a register that is used), loss partial += r^2,
+//                out = [w o r_re ; w o r_im] -- what the adjoint consumes.
+enum { PEPI_PAIR = 0, PEPI_MOD = 1, PEPI_RESID = 2, PEPI_WPAIR = 3, PEPI_WRESID = 4 };
 namespace {
+
+// The weighted epilogues read two arrays where the others read one.  They get them as one kernel argument of their own
+// type, so that the instantiations that were there before keep their argument list (and their code) as it was.
+struct FourierObs { const float* y; const float* w; };
+template <int EPI> struct CgObs {
+  typedef const float* __restrict__ type;
+  static type make(const float* y, const float*) { return y; }
+};
+template <> struct CgObs<PEPI_WPAIR> {
+  typedef FourierObs type;
+  static type make(const float* y, const float* w) { return FourierObs{y, w}; }
+};
+template <> struct CgObs<PEPI_WRESID> : CgObs<PEPI_WPAIR> {};
+__device__ __forceinline__ const float* obs_y(const float* y) { return y; }
+__device__ __forceinline__ const float* obs_y(const FourierObs& o) { return o.y; }
+__device__ __forceinline__ const float* obs_w(const float*) { return nullptr; }
+__device__ __forceinline__ const float* obs_w(const FourierObs& o) { return o.w; }
 
 template <int NW, int EPI>
 __global__ __launch_bounds__(64 * NW * NW) void k_cgemm(
     const float* __restrict__ A, const float* __restrict__ B, int ld_in, int64_t in_stride,
     const float* __restrict__ SA, const float* __restrict__ SB, int ld_s, float* __restrict__ OUT,
-    const float* __restrict__ Y, double* __restrict__ ws, int K, int R, int C) {
+    typename CgObs<EPI>::type Y, double* __restrict__ ws, int K, int R, int C) {
   constexpr int T = 32 * NW, NT = 64 * NW * NW;
   constexpr int NV = (BK * T / 4) / NT;          // float4 per thread per operand tile
   __shared__ float L[4 * BK * T];                // four operand tiles in the main loop, the P and Q slabs in the epilogue
@@ -942,7 +964,9 @@ __global__ __launch_bounds__(64 * NW * NW) void k_cgemm(
   float* const LQ = L + 32 * T;
   const int64_t plane = (int64_t)R * C;
   float* __restrict__ out_img = OUT + (int64_t)img * plane * (EPI == PEPI_MOD ? 1 : 2);
-  const float* __restrict__ y_img = EPI == PEPI_RESID ? Y + (int64_t)img * plane : nullptr;
+  const float* __restrict__ y_img = EPI == PEPI_RESID ? obs_y(Y) + (int64_t)img * plane
+                                  : (EPI == PEPI_WRESID ? obs_y(Y) + (int64_t)img * plane * 2 : nullptr);
+  const float* __restrict__ w_map = obs_w(Y);           // [R][C], the same for every image (weighted epilogues only)
   double lsum = 0.0;                                    // fp32 squares summed in fp64
   constexpr int SLAB_V = (32 * T / 4) / NT;
   for (int h = 0; h < NW; ++h) {
@@ -961,7 +985,28 @@ __global__ __launch_bounds__(64 * NW * NW) void k_cgemm(
       const int64_t off = (int64_t)(tr + h * 32 + row) * C + tc + c4i * 4;
       nhmc_v4f p = *reinterpret_cast<const nhmc_v4f*>(&LP[row * T + c4i * 4]);
       nhmc_v4f q = *reinterpret_cast<const nhmc_v4f*>(&LQ[row * T + c4i * 4]);
-      if (EPI == PEPI_PAIR) {
+      if (EPI == PEPI_WPAIR || EPI == PEPI_WRESID) {
+        const nhmc_v4f wv = *reinterpret_cast<const nhmc_v4f*>(&w_map[off]);
+        if (EPI == PEPI_WPAIR) {
+          p = p * wv;
+          q = q * wv;
+        } else {
+          const nhmc_v4f yre = *reinterpret_cast<const nhmc_v4f*>(&y_img[off]);
+          const nhmc_v4f yim = *reinterpret_cast<const nhmc_v4f*>(&y_img[plane + off]);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const bool measured = wv[j] > 0.0f;
+            const float rp = measured ? yre[j] - wv[j] * p[j] : 0.0f;     // selected, not multiplied: a NaN or inf in an
+            const float rq = measured ? yim[j] - wv[j] * q[j] : 0.0f;     // unmeasured entry of y ends here
+            lsum += (double)(rp * rp);
+            lsum += (double)(rq * rq);
+            p[j] = measured ? wv[j] * rp : 0.0f;
+            q[j] = measured ? wv[j] * rq : 0.0f;
+          }
+        }
+        *reinterpret_cast<nhmc_v4f*>(&out_img[off]) = p;
+        *reinterpret_cast<nhmc_v4f*>(&out_img[plane + off]) = q;
+      } else if (EPI == PEPI_PAIR) {
         *reinterpret_cast<nhmc_v4f*>(&out_img[off]) = p;
         *reinterpret_cast<nhmc_v4f*>(&out_img[plane + off]) = q;
       } else {
@@ -986,7 +1031,7 @@ __global__ __launch_bounds__(64 * NW * NW) void k_cgemm(
     }
     __syncthreads();                                      // the slabs are rewritten by the next row of waves
   }
-  if (EPI == PEPI_RESID) {
+  if (EPI == PEPI_RESID || EPI == PEPI_WRESID) {
     __shared__ double red[NW * NW];
     double sw = nhmc_wave_sum(lsum);
     if (lane == 0) red[wave] = sw;
@@ -1003,13 +1048,15 @@ int ctile_of(int R, int C) { return (R % 64 == 0 && C % 64 == 0) ? 64 : 32; }
 
 template <int EPI>
 int cgemm(const float* A, const float* B, int ld_in, int64_t in_stride, const float* SA, const float* SB, int ld_s,
-          float* OUT, const float* Y, double* ws, int n_img, int K, int R, int C, hipStream_t st) {
+          float* OUT, const float* Y, double* ws, int n_img, int K, int R, int C, hipStream_t st,
+          const float* Wmap = nullptr) {
   const int T = ctile_of(R, C);
   dim3 grid((unsigned)((C / T) * (R / T) * n_img));
+  const typename CgObs<EPI>::type obs = CgObs<EPI>::make(Y, Wmap);
   if (T == 64)
-    NHMC_LAUNCH((k_cgemm<2, EPI>), grid, dim3(256), 0, st, A, B, ld_in, in_stride, SA, SB, ld_s, OUT, Y, ws, K, R, C);
+    NHMC_LAUNCH((k_cgemm<2, EPI>), grid, dim3(256), 0, st, A, B, ld_in, in_stride, SA, SB, ld_s, OUT, obs, ws, K, R, C);
   else
-    NHMC_LAUNCH((k_cgemm<1, EPI>), grid, dim3(64), 0, st, A, B, ld_in, in_stride, SA, SB, ld_s, OUT, Y, ws, K, R, C);
+    NHMC_LAUNCH((k_cgemm<1, EPI>), grid, dim3(64), 0, st, A, B, ld_in, in_stride, SA, SB, ld_s, OUT, obs, ws, K, R, C);
   return nhmc_launch_status();
 }
 
@@ -1025,13 +1072,14 @@ PhaseFactors phase_factors(const float* fac, int d, int n) {
   return PhaseFactors{fac, fac + (int64_t)2 * n * d, fac + (int64_t)4 * n * d};
 }
 
-// stages 1-2: x -> the epilogue EPI of the complex spectrum.  tmp: float[n_img * 2 n d]
+// stages 1-2: x -> the epilogue EPI of the complex spectrum.  tmp: float[n_img * 2 n d].  wmap: the weight map [n][n] of
+// the weighted epilogues.
 template <int EPI, bool PRECLIP>
 int phase_forward(const float* x, const PhaseFactors& f, float* out, const float* y, double* ws, float* tmp, int n_img,
-                  int channels, int d, int n, hipStream_t st) {
+                  int channels, int d, int n, hipStream_t st, const float* wmap = nullptr) {
   int rc;
   if ((rc = gemm_krc<EPI_NONE, PRECLIP>(x, f.catT, tmp, nullptr, nullptr, nullptr, n_img, channels, d, d, 2 * n, st))) return rc;
-  return cgemm<EPI>(tmp, tmp + n, 2 * n, (int64_t)d * 2 * n, f.catT, f.catT + n, 2 * n, out, y, ws, n_img, d, n, n, st);
+  return cgemm<EPI>(tmp, tmp + n, 2 * n, (int64_t)d * 2 * n, f.catT, f.catT + n, 2 * n, out, y, ws, n_img, d, n, n, st, wmap);
 }
 
 // stages 3-4: W [n_img][2][n][n] -> the epilogue EPI of Cm^T Wre Cm - Sm^T Wre Sm + Cm^T Wim Sm + Sm^T Wim Cm
@@ -1134,4 +1182,66 @@ extern "C" int nhmc_data_phase_vjp(const float* xt_next, const float* y, const f
   if ((rc = phase_forward<PEPI_RESID, false>(xt_next, f, W, y, loss_ws, tmp, n_img, channels, dim, n, st))) return rc;
   const VjpArgs vjp{e, g_e, at, at_next, e_channels};
   return phase_adjoint<EPI_VJP>(W, f, g_xt, xt, &vjp, tmp, n_img, channels, dim, n, st);
+}
+
+// ---- Fourier sampling: undersampled k-space, partial Fourier, band-limited optics ------------------------------------
+// The linear, weighted use of the spectrum above at pad = 0 (n = d): with F = Cm + i Sm the centred orthonormal DFT of size
+// d, Y_c = F X_c F^T and a weight map w [d][d] >= 0 in centred layout (DC at [d/2][d/2]; a binary mask is the common case),
+//     H(x)   = [w o Re Y ; w o Im Y]                        [n_chains][C][2][d][d],  M = 2 C d^2,
+//     H^T(v) = Re[F^H (w o (v_re + i v_im)) conj(F)]         = nhmc_phase_adjoint(w o v).
+// Same chain, same launches as phase retrieval: k_sgemm, k_cgemm with PEPI_WPAIR / PEPI_WRESID, then the adjoint's
+// k_cgemm + k_sgemm with EPI_GRAD / EPI_VJP unchanged.  fac, tmp and the loss partials are those of the phase entries at
+// pad = 0 (nhmc_phase_tiles(C, d, 0), nhmc_phase_tmp_floats(n_chains, C, d, 0)).
+namespace {
+bool fourier_aligned(const void* a, const void* b, const void* c, const void* d, const void* e, const void* f = nullptr,
+                     const void* g = nullptr, const void* h = nullptr, const void* i = nullptr) {
+  return nhmc_aligned16(a) && nhmc_aligned16(b) && nhmc_aligned16(c) && nhmc_aligned16(d) && nhmc_aligned16(e) &&
+         nhmc_aligned16(f) && nhmc_aligned16(g) && nhmc_aligned16(h) && nhmc_aligned16(i);
+}
+}  // namespace
+
+extern "C" int nhmc_fourier_H(const float* x, const float* fac, const float* w, float* out, float* tmp, int n_chains,
+                              int channels, int dim, nhmc_stream_t stream) {
+  if (!x || !fac || !w || !out || !tmp) return NHMC_ERR_ARG;
+  if (phase_bad(n_chains, channels, dim, 0)) return NHMC_ERR_SHAPE;
+  if (!fourier_aligned(x, fac, w, out, tmp)) return NHMC_ERR_ALIGN;
+  return phase_forward<PEPI_WPAIR, false>(x, phase_factors(fac, dim, dim), out, nullptr, nullptr, tmp, n_chains * channels,
+                                          channels, dim, dim, nhmc_s(stream), w);
+}
+
+// Data term: r = y - H(clip xt) where w > 0 and exactly 0 elsewhere, loss partials of sum r^2 (nhmc_phase_tiles(C, d, 0)
+// per chain), g = -2 H^T r times the clip mask of xt when apply_clip.  y [n_chains][C][2][d][d].
+extern "C" int nhmc_data_fourier(const float* xt, const float* y, const float* fac, const float* w, int apply_clip,
+                                 float* g_xt, double* loss_ws, float* tmp, int n_chains, int channels, int dim,
+                                 nhmc_stream_t stream) {
+  if (!xt || !y || !fac || !w || !g_xt || !loss_ws || !tmp) return NHMC_ERR_ARG;
+  if (phase_bad(n_chains, channels, dim, 0)) return NHMC_ERR_SHAPE;
+  if (!fourier_aligned(xt, y, fac, w, g_xt, tmp)) return NHMC_ERR_ALIGN;
+  const int n_img = n_chains * channels;
+  const PhaseFactors f = phase_factors(fac, dim, dim);
+  float* Wr = tmp + (int64_t)n_img * 2 * dim * dim;
+  hipStream_t st = nhmc_s(stream);
+  int rc;
+  if (apply_clip) rc = phase_forward<PEPI_WRESID, true>(xt, f, Wr, y, loss_ws, tmp, n_img, channels, dim, dim, st, w);
+  else            rc = phase_forward<PEPI_WRESID, false>(xt, f, Wr, y, loss_ws, tmp, n_img, channels, dim, dim, st, w);
+  if (rc) return rc;
+  return phase_adjoint<EPI_GRAD>(Wr, f, g_xt, apply_clip ? xt : nullptr, nullptr, tmp, n_img, channels, dim, dim, st);
+}
+
+// The same on the clipped decode xt_next, with the VJP of the last DDIM step (inputs xt, e) in the last product's epilogue.
+extern "C" int nhmc_data_fourier_vjp(const float* xt_next, const float* y, const float* fac, const float* w, const float* xt,
+                                     const float* e, int e_channels, const float* at, const float* at_next, float* g_xt,
+                                     float* g_e, double* loss_ws, float* tmp, int n_chains, int channels, int dim,
+                                     nhmc_stream_t stream) {
+  if (!xt_next || !y || !fac || !w || !xt || !e || !at || !at_next || !g_xt || !g_e || !loss_ws || !tmp) return NHMC_ERR_ARG;
+  if (phase_bad(n_chains, channels, dim, 0) || (e_channels != channels && e_channels != 2 * channels)) return NHMC_ERR_SHAPE;
+  if (!fourier_aligned(xt_next, y, fac, w, xt, e, g_xt, g_e, tmp)) return NHMC_ERR_ALIGN;
+  const int n_img = n_chains * channels;
+  const PhaseFactors f = phase_factors(fac, dim, dim);
+  float* Wr = tmp + (int64_t)n_img * 2 * dim * dim;
+  hipStream_t st = nhmc_s(stream);
+  int rc;
+  if ((rc = phase_forward<PEPI_WRESID, false>(xt_next, f, Wr, y, loss_ws, tmp, n_img, channels, dim, dim, st, w))) return rc;
+  const VjpArgs vjp{e, g_e, at, at_next, e_channels};
+  return phase_adjoint<EPI_VJP>(Wr, f, g_xt, xt, &vjp, tmp, n_img, channels, dim, dim, st);
 }

@@ -702,6 +702,55 @@ def data_phase_vjp(xt_next, y, fac, pad, xt, e, at, at_next, g_e_out=None, loss_
     return (loss, *outs)
 
 
+# ---- Fourier sampling (mri<R>, fourier): the weighted spectrum at pad = 0 ------------------------------
+def _fourier_shapes(x, fac, w):
+    """x: [B, C, d, d]; fac: the phase factors at pad = 0; w: the weight map [d, d] -> B, C, d."""
+    B, Cc, dim, _ = _phase_shapes(x, fac, 0)
+    if tuple(w.shape) != (dim, dim):
+        raise _lib.NhmcError(f'the k-space weights must be [{dim}, {dim}], got {tuple(w.shape)}')
+    return B, Cc, dim
+
+
+def _fourier_io(xt, y, fac, w):
+    """What data_fourier and data_fourier_vjp share -> (tiles, tmp, operands (y, fac, w), the trailing (B, C, dim))."""
+    B, Cc, dim = _fourier_shapes(xt, fac, w)
+    if tuple(y.shape) != (B, Cc, 2, dim, dim):
+        raise _lib.NhmcError(f'the k-space observation must be [{B}, {Cc}, 2, {dim}, {dim}], got {tuple(y.shape)}')
+    ops = (_p(y, torch.float32, 'y'), _p(fac, torch.float32, 'fac'), _p(w, torch.float32, 'w'))
+    return _lib.load().nhmc_phase_tiles(Cc, dim, 0), _phase_tmp(B, Cc, dim, 0, xt.device), ops, (B, Cc, dim)
+
+
+def fourier_H(x, fac, w):
+    """[w o Re Y ; w o Im Y] of the centred orthonormal 2-D DFT of every plane: [B, C, d, d] -> [B, C, 2, d, d]."""
+    lib = _lib.load()
+    B, Cc, dim = _fourier_shapes(x, fac, w)
+    out = torch.empty(B, Cc, 2, dim, dim, dtype=torch.float32, device=x.device)
+    tmp = _phase_tmp(B, Cc, dim, 0, x.device)
+    rc = lib.nhmc_fourier_H(_p(x, torch.float32, 'x'), _p(fac, torch.float32, 'fac'), _p(w, torch.float32, 'w'), _p(out), _p(tmp),
+                            B, Cc, dim, _stream())
+    _lib.check(rc, 'nhmc_fourier_H')
+    return out
+
+
+def data_fourier(xt, y, fac, w, apply_clip=True, loss_out=None):
+    """-> (loss [B] float64, g_xt) for H = w o fft2c(x); y [B, C, 2, d, d], read only where w > 0."""
+    tiles, tmp, ops, dims = _fourier_io(xt, y, fac, w)
+    g = torch.empty_like(xt)
+    loss = _two_pass('nhmc_data_fourier', tiles, dims[0], xt.device, loss_out,
+                     (_p(xt, torch.float32, 'xt'), *ops, int(apply_clip), _p(g)), (_p(tmp), *dims))
+    return loss, g
+
+
+def data_fourier_vjp(xt_next, y, fac, w, xt, e, at, at_next, g_e_out=None, loss_out=None):
+    """Fourier-sampling data term on the clipped decode `xt_next` + VJP of the last DDIM step (inputs xt, e) in the last
+    product's epilogue -> (loss [B] float64, g_xt, g_e)."""
+    _, mix, grads, outs, alphas = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
+    tiles, tmp, ops, dims = _fourier_io(xt, y, fac, w)
+    loss = _two_pass('nhmc_data_fourier_vjp', tiles, dims[0], xt.device, loss_out,
+                     (_xt_next(xt_next, xt), *ops, *mix, *grads), (_p(tmp), *dims))
+    return (loss, *outs)
+
+
 # ---- general 2-D PSF blur (deblur_motion) --------------------------------------------------------
 class BlurTaps:
     """The compacted tap list of a 2-D PSF (include/nhmc.h): the non-zero entries of k [K, K] in row-major order as

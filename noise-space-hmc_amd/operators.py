@@ -1,6 +1,7 @@
 """Forward operators with the reference's `H_functions` surface, on the HIP kernels (the linear ones, the two
-nonlinear ones that need nothing from outside: HDR and phase retrieval, and two that the reference does not have: a
-general 2-D PSF blur, `Blur2D`, and any linear operator given as a sparse matrix, `SparseLinear`).
+nonlinear ones that need nothing from outside: HDR and phase retrieval, and three that the reference does not have: a
+general 2-D PSF blur, `Blur2D`, any linear operator given as a sparse matrix, `SparseLinear`, and any weighting of the
+centred 2-D spectrum, `FourierSampling`).
 
 Mirrors obs_functions/Hfuncs.py for the three operators on the HMC hot path -- same constructor
 arguments, same `H / Ht / H_pinv / is_linear`, inputs `[B, ...]`, outputs `[B, flat]` -- but each
@@ -496,6 +497,15 @@ def centred_dft_factors(n, pad, dim):
     return Fc.real.contiguous(), Fc.imag.contiguous()
 
 
+def packed_dft_factors(Cm, Sm, device):
+    """Cm, Sm [n, d] float64 -> the fp32 block float[6 n d] the MFMA chain reads (include/nhmc.h): [Cm^T | Sm^T] ([d][2n]),
+    [Cm | Sm] ([n][2d]), [Sm ; Cm] ([2n][d])."""
+    cat_t = torch.cat([Cm.t(), Sm.t()], dim=1)
+    cat = torch.cat([Cm, Sm], dim=1)
+    stk = torch.cat([Sm, Cm], dim=0)
+    return torch.cat([m.contiguous().reshape(-1) for m in (cat_t, cat, stk)]).float().contiguous().to(device)
+
+
 class PhaseRetrievalOperator(DecodeFused):
     """obs_functions/Hfuncs.py:318-366: H(x) = |fft2c(pad(x, p))| per channel plane with p = int(oversample / 8 * 256)
     WHATEVER the image size (so n = img_dim + 128 for the reference's oversample = 2), M = C n n; H^+(y) = crop(|ifft2c(y)|).
@@ -512,10 +522,7 @@ class PhaseRetrievalOperator(DecodeFused):
         self.M = channels * n * n
         Cm, Sm = centred_dft_factors(n, self.pad, img_dim)
         self.Cm, self.Sm = Cm, Sm                                   # float64, host: the definition the tests restate
-        cat_t = torch.cat([Cm.t(), Sm.t()], dim=1)                  # [d][2n]
-        cat = torch.cat([Cm, Sm], dim=1)                            # [n][2d]
-        stk = torch.cat([Sm, Cm], dim=0)                            # [2n][d]
-        self.factors = torch.cat([m.contiguous().reshape(-1) for m in (cat_t, cat, stk)]).float().contiguous().to(device)
+        self.factors = packed_dft_factors(Cm, Sm, device)
 
     def is_linear(self):
         return False
@@ -545,6 +552,104 @@ class PhaseRetrievalOperator(DecodeFused):
 
     def _data_vjp(self, xt_next, obs, xt_in, e, at, at_next, g_e_out, loss_out):
         return K.data_phase_vjp(xt_next, obs, self.factors, self.pad, xt_in, e, at, at_next, g_e_out=g_e_out, loss_out=loss_out)
+
+
+class FourierSampling(DecodeFused):
+    """A forward model that lives in Fourier space (undersampled k-space, partial Fourier, band-limited optics): with
+    F = Cm + i Sm = centred_dft_factors(d, 0, d) and Y_c = F X_c F^T per channel plane,
+        H(x)  = [W o Re Y ; W o Im Y]   [B, C, 2, d, d] flattened to [B, M], M = 2 C d^2,
+        Ht(v) = Re[F^H (W o (v_re + i v_im)) conj(F)], the exact adjoint.
+    Not in the reference.  `weights` is a real [d, d] array, every entry >= 0 and finite and at least one > 0 (a binary mask
+    is the common case), in centred layout (DC at [d/2, d/2]), shared by all channels and chains.  The data term reads the
+    observation only where W > 0 (include/nhmc.h).  The spectrum is PhaseRetrievalOperator's MFMA chain at pad = 0."""
+
+    def __init__(self, weights, channels, img_dim, device):
+        self.channels, self.img_dim, self.device = channels, img_dim, device
+        if img_dim <= 0 or img_dim % 32:
+            raise NhmcError(f'Fourier sampling needs img_dim % 32 == 0, got {img_dim}')
+        w = torch.as_tensor(weights).detach().cpu()
+        if w.dim() != 2 or tuple(w.shape) != (img_dim, img_dim):
+            raise NhmcError(f'the k-space weights must be [{img_dim}, {img_dim}], got {tuple(w.shape)}')
+        if w.is_complex():
+            raise NhmcError('the k-space weights must be real')
+        w = w.to(torch.float32)
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+            raise NhmcError('the k-space weights must be finite and >= 0')
+        if not bool((w > 0).any()):
+            raise NhmcError('the k-space weights measure nothing: at least one entry must be > 0')
+        self.weights = w.contiguous().clone()                       # float32, host: what `kspace_mask.png` shows
+        self.W = self.weights.to(device)
+        self.M = 2 * channels * img_dim * img_dim
+        Cm, Sm = centred_dft_factors(img_dim, 0, img_dim)
+        self.Cm, self.Sm = Cm, Sm                                   # float64, host: the definition the tests restate
+        self.factors = packed_dft_factors(Cm, Sm, device)           # PhaseRetrievalOperator's, at n = d
+
+    def _observation(self, y, shape):
+        return y.reshape(shape[0], self.channels, 2, self.img_dim, self.img_dim).contiguous()
+
+    def H(self, vec):
+        x = _img(vec, self.channels, self.img_dim)
+        return K.fourier_H(x, self.factors, self.W).reshape(x.shape[0], -1)
+
+    def Ht(self, vec):
+        v = self._observation(vec, vec.shape)
+        return K.phase_adjoint((v * self.W).contiguous(), self.factors, 0).reshape(v.shape[0], -1)
+
+    def H_pinv(self, vec):
+        raise NotImplementedError('Fourier sampling has no pseudo-inverse here (a zero-filled inverse is not one for '
+                                  'non-binary weights); no sampler calls H_pinv')
+
+    def data_term(self, xt, y, apply_clip=True, loss_out=None):
+        return K.data_fourier(xt, self._observation(y, xt.shape), self.factors, self.W, apply_clip, loss_out=loss_out)
+
+    def _data_vjp(self, xt_next, obs, xt_in, e, at, at_next, g_e_out, loss_out):
+        return K.data_fourier_vjp(xt_next, obs, self.factors, self.W, xt_in, e, at, at_next, g_e_out=g_e_out, loss_out=loss_out)
+
+
+def cartesian_mask(img_dim, accel, generator=None):
+    """A Cartesian undersampling mask [d, d] float32 for acceleration `accel`, our own construction: whole columns are kept
+    (phase-encode lines along the width), keep = d // accel of them.  c = min(keep, max(1, int(0.32 d / accel + 0.5))) are
+    central, columns [d/2 - c//2, d/2 - c//2 + c); the other keep - c are the first entries of torch.randperm over the
+    remaining columns in ascending order, drawn from `generator` (the global torch RNG when None, so every rank holds the
+    same mask after torch.manual_seed)."""
+    d, R = int(img_dim), int(accel)
+    if d < 1 or R < 1 or d // R < 1:
+        raise NhmcError(f'cartesian_mask: needs accel >= 1 and img_dim // accel >= 1, got img_dim {img_dim}, accel {accel}')
+    keep = d // R
+    c = min(keep, max(1, int(0.32 * d / R + 0.5)))
+    lo = d // 2 - c // 2
+    cols = torch.zeros(d, dtype=torch.bool)
+    cols[lo:lo + c] = True
+    rest = torch.nonzero(~cols).squeeze(1)                              # ascending
+    perm = torch.randperm(rest.numel(), generator=generator)
+    cols[rest[perm[:keep - c]]] = True
+    return cols.to(torch.float32)[None, :].expand(d, d).contiguous()
+
+
+def load_kspace_mask(path, img_dim):
+    """The weight map of `--deg fourier`: a real [img_dim, img_dim] array saved with numpy.save, read with
+    np.load(allow_pickle=False) -> float32 tensor.  Every refusal names the file."""
+    import numpy as np
+    if not os.path.isfile(path):
+        raise NhmcError(f'--kspace_mask: no such file: {path}')
+    try:
+        a = np.load(path, allow_pickle=False)
+    except Exception as exc:
+        raise NhmcError(f'--kspace_mask: {path} is not a .npy array ({exc})') from exc
+    if not isinstance(a, np.ndarray):
+        raise NhmcError(f'--kspace_mask: {path} is an archive, not a single .npy array')
+    if a.ndim != 2:
+        raise NhmcError(f'--kspace_mask: {path} has rank {a.ndim}, expected a 2-D array [{img_dim}, {img_dim}]')
+    if a.shape != (img_dim, img_dim):
+        raise NhmcError(f'--kspace_mask: {path} is {a.shape[0]} x {a.shape[1]}, the image is {img_dim} x {img_dim}')
+    if a.dtype.kind not in 'biuf':
+        raise NhmcError(f'--kspace_mask: {path} holds {a.dtype}, expected real numbers (or booleans)')
+    a = a.astype(np.float64)
+    if not np.isfinite(a).all() or (a < 0).any():
+        raise NhmcError(f'--kspace_mask: {path}: the weights must be finite and >= 0')
+    if not (a > 0).any():
+        raise NhmcError(f'--kspace_mask: {path}: the weights measure nothing (all zero)')
+    return torch.from_numpy(np.ascontiguousarray(a.astype(np.float32)))
 
 
 class Blur2D(DecodeFused):
@@ -761,10 +866,12 @@ def gaussian_taps(sigma, half=4):
     return k / k.sum()
 
 
-def build_operator(deg, channels, img_dim, device, generator=None, spectral_projected=None, operator_file=None):
+def build_operator(deg, channels, img_dim, device, generator=None, spectral_projected=None, operator_file=None,
+                   kspace_mask_file=None):
     """`prepare_measurement` (main_sampling.py:261-351) for the degradations on the HMC hot path.
     spectral_projected: the four-product data term of the two blur operators (see Deblurring2D).
-    operator_file: the CSR .npz of `sparse` (load_sparse_npz)."""
+    operator_file: the CSR .npz of `sparse` (load_sparse_npz).
+    kspace_mask_file: the weight map .npy of `fourier` (load_kspace_mask)."""
     if deg.startswith('sr_bicubic') and deg[10:].isdigit():
         factor = int(deg[10:])
         return SRConv(bicubic_taps(factor), channels, img_dim, device, stride=factor)
@@ -806,4 +913,13 @@ def build_operator(deg, channels, img_dim, device, generator=None, spectral_proj
         if shape[1] != img_dim ** 2:
             raise NhmcError(f'--operator: {operator_file} has {shape[1]} columns, the image has {img_dim}^2 = {img_dim ** 2} pixels')
         return SparseLinear(triple, channels, img_dim, device, shape=shape)
+    if deg.startswith('mri') and deg[3:].isdigit():                     # not in the reference: Cartesian accelerated MRI
+        accel = int(deg[3:])
+        if accel < 1 or img_dim // accel < 1:
+            raise NhmcError(f'mri<R> needs R >= 1 and image_size // R >= 1, got R = {accel} at image size {img_dim}')
+        return FourierSampling(cartesian_mask(img_dim, accel, generator), channels, img_dim, device)
+    if deg == 'fourier':                                                # any k-space weight map, as a .npy array
+        if not kspace_mask_file:
+            raise NhmcError('--deg fourier needs --kspace_mask FILE.npy (a real [image_size, image_size] array, DC at the centre)')
+        return FourierSampling(load_kspace_mask(kspace_mask_file, img_dim), channels, img_dim, device)
     raise NotImplementedError(f'degradation {deg!r} is outside the HMC hot path of this build')
