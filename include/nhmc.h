@@ -705,6 +705,24 @@ int nhmc_conv3x3_wino_k32(const float* x, const float* u, const float* bias, con
                           int h, int w, int stride, int padding, nhmc_stream_t stream);
 int nhmc_conv3x3_wino_k32_covers(int n, int c, int k, int h, int w);
 int nhmc_conv3x3_wino_k32_prefers(int backward, int n, int c, int k, int h, int w);
+/* nhmc_conv3x3_wino_up: nhmc_conv3x3_wino next to a nearest 2x upsample (unet_ffhq.py:299-321, the up-sampling ResBlock),
+ *   with the upsampled or pooled tensor never in memory.  n, c, k, h, w are the convolution's own; `mode` is ONE of
+ *   NHMC_WINO_IN_UP:    x is [n][c][h / 2][w / 2] and stands for its nearest 2x upsample; add must be null.  The seven
+ *                       Winograd frequencies that are +0 for such an input are not multiplied.
+ *   NHMC_WINO_ADD_UP:   add (required, not y) is [n][k][h / 2][w / 2] and stands for its nearest 2x upsample.
+ *   NHMC_WINO_OUT_POOL: y is [n][k][h / 2][w / 2], the sum over each 2 x 2 block of the convolution's output, formed as
+ *                       ((((0 + y00) + y01) + y10) + y11) * 0.25f * 4.0f; bias and add must be null.
+ *   For finite inputs each gives the bits of nhmc_conv3x3_wino composed with nhmc_sr_Ht (scale 1) / nhmc_sr_H and a
+ *   multiplication by 4 on the materialised tensor.  With non-finite inputs the non-finite output positions are the same,
+ *   their values may differ (the skipped products held inf - inf).  Runs on the eight-wave kernel only:
+ *   nhmc_conv3x3_wino_up_covers = nhmc_conv3x3_wino_covers and NHMC_WINO_WAVES unset or 8; anything else is
+ *   NHMC_ERR_SHAPE.  Validation order as nhmc_conv3x3_wino, a mode / pointer mismatch is NHMC_ERR_ARG. */
+#define NHMC_WINO_IN_UP 1
+#define NHMC_WINO_ADD_UP 2
+#define NHMC_WINO_OUT_POOL 4
+int nhmc_conv3x3_wino_up(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c, int k,
+                         int h, int w, int mode, nhmc_stream_t stream);
+int nhmc_conv3x3_wino_up_covers(int n, int c, int k, int h, int w);
 
 /* PSNR of clamp((xt+1)/2,0,1) against clamp((x_orig+1)/2,0,1)   main_sampling.py:738-739
  * ws: double[n_chains][nhmc_data_tiles(n_elem)]. */

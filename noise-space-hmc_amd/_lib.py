@@ -119,6 +119,8 @@ SIGNATURES = {
     'nhmc_conv3x3_wino_k32': (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
     'nhmc_conv3x3_wino_k32_covers': (I, [I, I, I, I, I]),
     'nhmc_conv3x3_wino_k32_prefers': (I, [I, I, I, I, I, I]),
+    'nhmc_conv3x3_wino_up': (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
+    'nhmc_conv3x3_wino_up_covers': (I, [I, I, I, I, I]),
     'nhmc_psnr':(I, [P, P, P, P, I, I64, P]),
     'nhmc_psnr_samples': (I, [P, P, P, P, I, I, I64, P]),
     'nhmc_ssim_tiles': (I, [I, I]),

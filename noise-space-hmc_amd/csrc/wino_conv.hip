@@ -33,6 +33,21 @@
 // (kh, th) share a SIMD; before the output transform the pair exchanges accumulator halves through LDS, lane by lane, and
 // each wave transforms 8 of the lane's 16 channel rows.  Same LDS layout, same MFMA chains, same transform expressions: the
 // same bits.  NHMC_WINO_WAVES = 4 | 8, read per call, chooses (wc_waves); the comment above k_conv3x3_wino8 has the details.
+// Nearest 2x upsample (template parameters of k_conv3x3_wino8, entry nhmc_conv3x3_wino_up; the up-sampling ResBlocks, whose
+// upsampled tensors then never reach memory).  IN_UP: x is [n][C][H / 2][W / 2] and stands for its nearest 2x upsample.  The
+// tiles are even-aligned, so rows 1 and 2 of every 4 x 4 patch are one low-res row and columns 1 and 2 one low-res column, at
+// the zero-padded borders too.  Column b = 2 of the transform is d(r, 2) - d(r, 1) and entry a = 2 is e[2] - e[1]: every V
+// entry with a == 2 or b == 2 is exactly +0.0f, the frequencies f = 2, 6, 8, 9, 10, 11, 14, and their accumulators stay +0
+// (u * (+0) = +-0, +0 + (-0) = +0; tests/test_wino_up_cpu.py).  The loader fetches three rows of one dword instead of four
+// of two, column 2 of V is neither formed nor stored nor read, and no MFMA is issued for the seven frequencies: 6 per unit in
+// the lower frequency half, 3 in the upper, whose j < 4 is one uniform branch.  The accumulators of the skipped frequencies
+// keep their zero state and the exchange and Y = A^T M A run unchanged, adding the same +0 terms in the same order: for
+// finite inputs the bits are those of the kernel on the materialised tensor.  With +-inf or NaN in x the skipped products held
+// inf - inf = NaN, so the values at non-finite outputs may differ; the set of non-finite output positions is the same.
+// ADD_UP: add is [n][K][H / 2][W / 2]; the epilogue loads the two low-res values under the lane's four output columns and
+// adds {l.x, l.x, l.y, l.y} where it adds the float4 otherwise.  OUT_POOL: y is [n][K][H / 2][W / 2]; a lane's 2 x 2 patch
+// is one low-res pixel, stored as ((((0 + o00) + o01) + o10) + o11) * 0.25f * 4.0f, the chain of k_sr<2, 1> followed by the
+// multiplication by 4 of the upsample's backward (denormals round as there), with no exchange between lanes.
 #include "nhmc_common.h"
 
 #include <cstdlib>
@@ -434,13 +449,18 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
 // (tests/test_wino_exchange_cpu.py).  Each wave then runs the four-wave transform expression on its 8 channel rows.
 constexpr int WC8_XSLOTS = 16;                   // float4 per lane and wave in the exchange: 8 frequencies x 2 register quads
 
+// IN_UP, ADD_UP, OUT_POOL: the forms next to a nearest 2x upsample (file header, "Nearest 2x upsample"): x, add or y at half
+// the resolution.  All false is the kernel described above, instruction for instruction.
+template <bool IN_UP = false, bool ADD_UP = false, bool OUT_POOL = false>
 __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
+  static_assert(!(OUT_POOL && ADD_UP), "the pooled epilogue takes no add");
   constexpr int TC = 32, BLK_ROWS = 128 / TC, BLK_COLS = 2 * TC;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
   const int kh = wave & 1, th = (wave >> 1) & 1;
   const int fh = __builtin_amdgcn_readfirstlane(wave >> 2);
   const int C = a.C, K = a.K, H = a.H, W = a.W, HW = H * W;
+  const int XW = IN_UP ? W >> 1 : W, XHW = IN_UP ? HW >> 2 : HW;      // row and plane of x: IN_UP reads the low-res tensor
 #ifdef NHMC_WINO_STAMPS
   unsigned long long t64[7] = {};
   unsigned t32[17] = {};
@@ -467,8 +487,13 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
   for (int q = 0; q < 4; ++q) {
     const int row = h0 + 2 * ty - 1 + q;
     const bool rok = (unsigned)row < (unsigned)H;
-    voff[q] = rok ? 4u * (unsigned)(lc * HW + row * W + w0 + 2 * lt) : 0u;
-    eoff[q] = rok ? 4u * (unsigned)(lc * HW + row * W + (eok ? ecol : w0 + 2 * lt)) : 0u;
+    if (IN_UP) {                                         // row >> 1, column >> 1 of the low-res tensor; one dword per row
+      voff[q] = rok ? 4u * (unsigned)(lc * XHW + (row >> 1) * XW + (w0 >> 1) + lt) : 0u;
+      eoff[q] = rok ? 4u * (unsigned)(lc * XHW + (row >> 1) * XW + (eok ? ecol >> 1 : (w0 >> 1) + lt)) : 0u;
+    } else {
+      voff[q] = rok ? 4u * (unsigned)(lc * HW + row * W + w0 + 2 * lt) : 0u;
+      eoff[q] = rok ? 4u * (unsigned)(lc * HW + row * W + (eok ? ecol : w0 + 2 * lt)) : 0u;
+    }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const int col = w0 + 2 * lt - 1 + s;
@@ -476,7 +501,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
       okmask |= ok ? 1u << (q * 4 + s) : 0u;
     }
   }
-  const float* xn = a.x + (int64_t)n * C * HW;
+  const float* xn = a.x + (int64_t)n * C * XHW;
   const char* un = reinterpret_cast<const char*>(a.U + (int64_t)kb * WC_KBLK * 16);
   const unsigned uoff = 16u * t8 + (unsigned)ty * (unsigned)K * 64u;                // float4 t8 of piece 2 i + ty
   const int uw = (t8 & ~3) * 4 + (((t8 & 3) ^ wc_swz(t8 >> 2)) << 2) + 1024 * ty;
@@ -484,15 +509,17 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
 
   // A chunk's 12 loads per thread: 0 .. 7 the patch (row q = i >> 1: its 8-byte load, then its edge load), 8 .. 11 U pieces
   wc_v2f xm[4];
-  float xl[4], xq[4], xe[4];
+  float xl[4], xq[4], xe[4], xu[4];                      // xu: IN_UP's one dword per row, both middle columns
   nhmc_v4f ur[4];
   auto load_one = [&](int ch, int i) {
     if (i < 8) {
-      const char* xs = reinterpret_cast<const char*>(xn + (int64_t)ch * WC_CHUNK * HW);
+      const char* xs = reinterpret_cast<const char*>(xn + (int64_t)ch * WC_CHUNK * XHW);
       const int q = i >> 1;
+      if (IN_UP && q == 2) return;                       // rows 1 and 2 of the patch are one low-res row
       unsigned off = (i & 1) ? eoff[q] : voff[q];
       asm volatile("" : "+v"(off));
       if (i & 1) xe[q] = *reinterpret_cast<const float*>(xs + off);
+      else if (IN_UP) xu[q] = *reinterpret_cast<const float*>(xs + off);
       else xm[q] = *reinterpret_cast<const wc_v2f*>(xs + off);
     } else {
       const char* us = un + (int64_t)ch * WC_CHUNK * K * 64 + (int64_t)(2 * (i - 8)) * K * 64;
@@ -508,32 +535,42 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
   auto pin_patch = [&]() {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      asm volatile("" : "+v"(xm[q]));
+      if (IN_UP && q == 2) continue;
+      if (IN_UP) asm volatile("" : "+v"(xu[q]));
+      else asm volatile("" : "+v"(xm[q]));
       asm volatile("" : "+v"(xe[q]));
     }
   };
   auto exchange_patch = [&]() {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
+      if (IN_UP && q == 2) continue;
+      if (IN_UP) xm[q] = wc_v2f{xu[q], xu[q]};
       xl[q] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(xm[q].y), 0x138, 0xF, 0xF, false));
       xq[q] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(xm[q].x), 0x130, 0xF, 0xF, false));
       xl[q] = lt == 0 ? xe[q] : xl[q];
       xq[q] = lt == TC - 1 ? xe[q] : xq[q];
     }
   };
-  auto d = [&](int q, int s) {
+  auto d = [&](int q0, int s) {
+    const int q = IN_UP && q0 == 2 ? 1 : q0;             // IN_UP: row 2 IS row 1, values and padding mask
     const float v = s == 0 ? xl[q] : s == 1 ? xm[q].x : s == 2 ? xm[q].y : xq[q];
     return (okmask >> (q * 4 + s)) & 1u ? v : 0.0f;
   };
   float e[4];
   auto stage_rows = [&](int b) {
+    if (IN_UP && b == 2) return;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       e[q] = b == 0 ? d(q, 0) - d(q, 2) : b == 1 ? d(q, 1) + d(q, 2) : b == 2 ? d(q, 2) - d(q, 1) : d(q, 1) - d(q, 3);
   };
   nhmc_v4f vt;
-  auto stage_cols = [&]() { vt.x = e[0] - e[2]; vt.y = e[1] + e[2]; vt.z = e[2] - e[1]; vt.w = e[1] - e[3]; };
+  auto stage_cols = [&](int b = 0) {
+    if (IN_UP && b == 2) return;
+    vt.x = e[0] - e[2]; vt.y = e[1] + e[2]; vt.z = e[2] - e[1]; vt.w = e[1] - e[3];
+  };
   auto stage_v = [&](int st, int b) {
+    if (IN_UP && b == 2) return;                         // column 2 of V is +0 throughout: neither formed, stored nor read
     *reinterpret_cast<nhmc_v4f*>(lds + st * 2 * WC_OPER + WC_OPER + vw + ((b ^ vswz) << 2)) = vt;
   };
   auto stage_u = [&](int st, int i) { *reinterpret_cast<nhmc_v4f*>(lds + st * 2 * WC_OPER + uw + 2048 * i) = ur[i]; };
@@ -568,21 +605,32 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
   auto unit = [&](int v, int st, int cl) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[v & 1][j], bv[v & 1][j], acc[j], 0, 0, 0);
+      // IN_UP: the frequencies with a == 2 (j = 2, 6) or b == 2 (j = 0 .. 3 of the upper half) have V = +0: no MFMA; fh is
+      // a scalar, so the upper half's j < 4 is one uniform branch, and that half never reads granule 2
+      if constexpr (IN_UP) {
+        if (j != 2 && j != 6 && (j >= 4 || fh == 0))
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[v & 1][j], bv[v & 1][j], acc[j], 0, 0, 0);
+      } else {
+        acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[v & 1][j], bv[v & 1][j], acc[j], 0, 0, 0);
+      }
       if (j == 0 && v == 1) {
         WC_T32(7);
         pin_patch();
         exchange_patch();
         WC_T32(8);
       }
-      if (j < 2) fetch_half(st, (v + 1) & 3, j, av[(v + 1) & 1], bv[(v + 1) & 1]);
+      if constexpr (IN_UP) {
+        if (j == 1 || (j == 0 && fh == 0)) fetch_half(st, (v + 1) & 3, j, av[(v + 1) & 1], bv[(v + 1) & 1]);
+      } else {
+        if (j < 2) fetch_half(st, (v + 1) & 3, j, av[(v + 1) & 1], bv[(v + 1) & 1]);
+      }
       if (v == 2 && j >= 5) issue_loads(cl, 2 * (j - 5), 2 * (j - 5) + 2);
       if (v == 3 && j < 2) issue_loads(cl, 6 + j, 7 + j);
       if (v == 0 && (j & 1)) issue_loads(cl, 8 + j / 2, 9 + j / 2);
       if (v == 1 || v == 2) {
         const int b = 2 * (v - 1);
         if (j == 1) stage_rows(b);
-        if (j == 2) stage_cols();
+        if (j == 2) stage_cols(b);
         if (j == 3) stage_v(st ^ 1, b);
         if (j == 4) { stage_rows(b + 1); stage_cols(); }
         if (j == 5) stage_v(st ^ 1, b + 1);
@@ -598,7 +646,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
 #pragma unroll
   for (int b = 0; b < 4; ++b) {
     stage_rows(b);
-    stage_cols();
+    stage_cols(b);
     stage_v(0, b);
     stage_u(0, b);
   }
@@ -606,7 +654,11 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
   WC_T64(1);
   int cl = 1 < chunks ? 1 : 0;
   issue_loads(cl, 0, 8);
-  fetch_half(0, 0, 0, av[0], bv[0]);
+  if constexpr (IN_UP) {
+    if (fh == 0) fetch_half(0, 0, 0, av[0], bv[0]);
+  } else {
+    fetch_half(0, 0, 0, av[0], bv[0]);
+  }
   fetch_half(0, 0, 1, av[0], bv[0]);
   // ONE instance of the chunk body, as in the four-wave kernel: the last chunk stages itself once more into the idle buffer.
   // One barrier per chunk, between units 2 and 3, when unit 3's operands are in registers: the first operands of the
@@ -642,12 +694,17 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
   const int k0 = kb * WC_KBLK + kh * 32 + 4 * lh + 16 * fh;
   const bool odd = lr & 1;
   const int64_t at0 = (((int64_t)n * K + k0) * H + oh) * W + ow + (odd ? W - 2 : 0);
+  // ADD_UP: add is [n][K][H / 2][W / 2]; the two low-res values under the lane's four output columns.  OUT_POOL: y is
+  // [n][K][H / 2][W / 2]; the lane's 2 x 2 patch is its pixel (oh / 2, ow / 2)
+  const int64_t lt0 = !(ADD_UP || OUT_POOL) ? 0 : (((int64_t)n * K + k0) * (H >> 1) + (oh >> 1)) * (W >> 1) + (OUT_POOL ? ow >> 1 : (ow >> 1) - (odd ? 1 : 0));
   float bc[8];
   nhmc_v4f ad[8];
+  wc_v2f al[8];
 #pragma unroll
   for (int rr = 0; rr < 8; ++rr) {
     bc[rr] = 0.0f;
     ad[rr] = nhmc_v4f{0.0f, 0.0f, 0.0f, 0.0f};
+    al[rr] = wc_v2f{0.0f, 0.0f};
   }
   if (has_bias) {
 #pragma unroll
@@ -655,8 +712,10 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
   }
   if (has_add) {
 #pragma unroll
-    for (int rr = 0; rr < 8; ++rr)
-      ad[rr] = *reinterpret_cast<const nhmc_v4f*>(a.add + at0 + (int64_t)((rr & 3) + 8 * (rr >> 2)) * HW);
+    for (int rr = 0; rr < 8; ++rr) {
+      if (ADD_UP) al[rr] = *reinterpret_cast<const wc_v2f*>(a.add + lt0 + (int64_t)((rr & 3) + 8 * (rr >> 2)) * (HW >> 2));
+      else ad[rr] = *reinterpret_cast<const nhmc_v4f*>(a.add + at0 + (int64_t)((rr & 3) + 8 * (rr >> 2)) * HW);
+    }
   }
   nhmc_v4f* xch = reinterpret_cast<nhmc_v4f*>(lds);
   const int xw = wave * WC8_XSLOTS * 64 + lane, xr = (wave ^ 4) * WC8_XSLOTS * 64 + lane;
@@ -699,11 +758,16 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
         o[i].x = has_bias ? o[i].x + bc[rr] : o[i].x;
         o[i].y = has_bias ? o[i].y + bc[rr] : o[i].y;
       }
+      if (OUT_POOL) {                                  // k_sr<2, 1>'s block mean, then _Resample2x.backward's mul_(4.0)
+        const float pooled = ((((0.0f + o[0].x) + o[0].y) + o[1].x) + o[1].y) * 0.25f * 4.0f;
+        __builtin_nontemporal_store(pooled, a.y + lt0 + (int64_t)((rr & 3) + 8 * (rr >> 2)) * (HW >> 2));
+        continue;
+      }
       const wc_v2f keep = odd ? o[1] : o[0], give = odd ? o[0] : o[1];
       const wc_v2f recv = {neighbour(give.x), neighbour(give.y)};
       nhmc_v4f v;
       v.x = odd ? recv.x : keep.x; v.y = odd ? recv.y : keep.y; v.z = odd ? keep.x : recv.x; v.w = odd ? keep.y : recv.y;
-      if (has_add) v += ad[rr];
+      if (has_add) v += ADD_UP ? nhmc_v4f{al[rr].x, al[rr].x, al[rr].y, al[rr].y} : ad[rr];
       __builtin_nontemporal_store(v, reinterpret_cast<nhmc_v4f*>(a.y + at0 + (int64_t)((rr & 3) + 8 * (rr >> 2)) * HW));
     }
   };
@@ -799,20 +863,21 @@ int wc_waves() {
   return -1;
 }
 
+template <bool IN_UP = false, bool ADD_UP = false, bool OUT_POOL = false>
 int wc_launch8(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c, int k, int h, int w,
                nhmc_stream_t stream) {
   static bool attr_set[64] = {};
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wino8), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            WC_LDS_BYTES) != hipSuccess)
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wino8<IN_UP, ADD_UP, OUT_POOL>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, WC_LDS_BYTES) != hipSuccess)
       return NHMC_ERR_LAUNCH;
     if (dev >= 0 && dev < 64) attr_set[dev] = true;
   }
   const WinoArgs a{x, u, bias, add, y, c, k, h, w, h / WC_ROWS, w / WC_COLS};
   const int64_t blocks = (int64_t)n * a.row_blocks * a.col_blocks * (k / WC_KBLK);
-  NHMC_LAUNCH(k_conv3x3_wino8, dim3((unsigned)blocks), dim3(512), WC_LDS_BYTES, nhmc_s(stream), a);
+  NHMC_LAUNCH((k_conv3x3_wino8<IN_UP, ADD_UP, OUT_POOL>), dim3((unsigned)blocks), dim3(512), WC_LDS_BYTES, nhmc_s(stream), a);
   return nhmc_launch_status();
 }
 
@@ -978,6 +1043,26 @@ extern "C" int nhmc_conv3x3_wino(const float* x, const float* u, const float* bi
   if (stride != 1 || padding != 1 || !wc_covers(n, c, k, h, w)) return NHMC_ERR_SHAPE;
   if (!nhmc_aligned16(x) || !nhmc_aligned16(u) || !nhmc_aligned16(y) || !nhmc_aligned16(add)) return NHMC_ERR_ALIGN;
   return wc_launch<32>(x, u, bias, add, y, n, c, k, h, w, stream);
+}
+
+// The upsample forms of the eight-wave kernel (the paragraph "Nearest 2x upsample" of the file header).  h, w are the
+// convolution's own resolution; mode names which tensor is at half of it.
+extern "C" int nhmc_conv3x3_wino_up_covers(int n, int c, int k, int h, int w) {
+  return wc_covers(n, c, k, h, w) && wc_waves() == 8;
+}
+
+extern "C" int nhmc_conv3x3_wino_up(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c,
+                                    int k, int h, int w, int mode, nhmc_stream_t stream) {
+  if (!x || !u || !y || y == x || (add && add == x)) return NHMC_ERR_ARG;
+  if (mode != NHMC_WINO_IN_UP && mode != NHMC_WINO_ADD_UP && mode != NHMC_WINO_OUT_POOL) return NHMC_ERR_ARG;
+  if ((mode == NHMC_WINO_ADD_UP) != (add != nullptr) || (mode == NHMC_WINO_ADD_UP && add == y)) return NHMC_ERR_ARG;
+  if (mode == NHMC_WINO_OUT_POOL && bias) return NHMC_ERR_ARG;
+  if (wc_waves() < 0) return NHMC_ERR_ARG;
+  if (!wc_covers(n, c, k, h, w) || wc_waves() != 8) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(x) || !nhmc_aligned16(u) || !nhmc_aligned16(y) || !nhmc_aligned16(add)) return NHMC_ERR_ALIGN;
+  return mode == NHMC_WINO_IN_UP    ? wc_launch8<true, false, false>(x, u, bias, add, y, n, c, k, h, w, stream)
+         : mode == NHMC_WINO_ADD_UP ? wc_launch8<false, true, false>(x, u, bias, add, y, n, c, k, h, w, stream)
+                                    : wc_launch8<false, false, true>(x, u, bias, add, y, n, c, k, h, w, stream);
 }
 
 extern "C" int nhmc_conv3x3_wino_narrow(const float* x, const float* u, const float* bias, const float* add, float* y, int n,

@@ -1321,13 +1321,16 @@ def conv3x3_wino_k32_prefers(backward, n, c, k, h, w):
 
 def conv3x3_wino(x, weight, bias=None, add=None, backward=False):
     """conv2d(x, weight, stride 1, padding 1) (+ bias[k]) (+ add) on the Winograd MFMA kernel; backward=True: the
-    backward-data pass of that convolution, x being the output gradient [N, K, H, W] -> [N, C, H, W]."""
+    backward-data pass of that convolution, x being the output gradient [N, K, H, W] -> [N, C, H, W].
+    An `add` of shape [N, K, H / 2, W / 2] stands for its nearest 2x upsample (conv3x3_wino_up, WINO_ADD_UP)."""
     lib = _lib.load()
     if x.dim() != 4 or weight.dim() != 4 or x.shape[1] != weight.shape[1 if not backward else 0]:
         raise _lib.NhmcError(f'conv3x3_wino: x {tuple(x.shape)} does not match the filter {tuple(weight.shape)}')
     u = wino_weights(weight, backward)
     N, Cc, H, W = x.shape
     Kk = u.shape[2]
+    if add is not None and tuple(add.shape) == (N, Kk, H // 2, W // 2):
+        return conv3x3_wino_up(x, weight, WINO_ADD_UP, bias, add, backward=backward)
     y = torch.empty((N, Kk, H, W), dtype=torch.float32, device=x.device)
     if (bias is not None and bias.numel() != Kk) or (add is not None and add.shape != y.shape):
         raise _lib.NhmcError('conv3x3_wino: bias / add do not match the output')
@@ -1335,6 +1338,37 @@ def conv3x3_wino(x, weight, bias=None, add=None, backward=False):
     rc = getattr(lib, entry)(_p(x, torch.float32, 'x'), _p(u), _p(bias, torch.float32, 'bias'), _p(add, torch.float32, 'add'),
                              _p(y), N, Cc, Kk, H, W, 1, 1, _stream())
     _lib.check(rc, entry)
+    return y
+
+
+WINO_IN_UP, WINO_ADD_UP, WINO_OUT_POOL = 1, 2, 4      # NHMC_WINO_* of include/nhmc.h
+
+
+def conv3x3_wino_up_covers(n, c, k, h, w):
+    """nhmc_conv3x3_wino_up_covers at the convolution's own (upsampled) shape: the wide geometry on eight waves
+    (NHMC_WINO_WAVES is read per call) and NHMC_WINO_UP, the A/B switch of the fused upsample forms, not 0."""
+    if os.environ.get('NHMC_WINO_UP', '1') == '0' or _wino_narrow(w):
+        return False
+    return bool(_lib.load().nhmc_conv3x3_wino_up_covers(n, c, k, h, w))
+
+
+def conv3x3_wino_up(x, weight, mode, bias=None, add=None, backward=False):
+    """conv3x3_wino next to a nearest 2x upsample that never reaches memory (nhmc_conv3x3_wino_up).  WINO_IN_UP: x is the
+    low-res tensor [N, C, H / 2, W / 2]; WINO_ADD_UP: add is [N, K, H / 2, W / 2]; WINO_OUT_POOL: the result is the 2 x 2
+    block sum [N, K, H / 2, W / 2] of the convolution's output (the gradient of an upsampled input)."""
+    lib = _lib.load()
+    if x.dim() != 4 or weight.dim() != 4 or x.shape[1] != weight.shape[1 if not backward else 0]:
+        raise _lib.NhmcError(f'conv3x3_wino_up: x {tuple(x.shape)} does not match the filter {tuple(weight.shape)}')
+    u = wino_weights(weight, backward)
+    N, Cc = x.shape[0], x.shape[1]
+    H, W = (2 * x.shape[2], 2 * x.shape[3]) if mode == WINO_IN_UP else (x.shape[2], x.shape[3])
+    Kk = u.shape[2]
+    y = torch.empty((N, Kk, H // 2, W // 2) if mode == WINO_OUT_POOL else (N, Kk, H, W), dtype=torch.float32, device=x.device)
+    if (bias is not None and bias.numel() != Kk) or (add is not None and tuple(add.shape) != (N, Kk, H // 2, W // 2)):
+        raise _lib.NhmcError('conv3x3_wino_up: bias / add do not match the output')
+    rc = lib.nhmc_conv3x3_wino_up(_p(x, torch.float32, 'x'), _p(u), _p(bias, torch.float32, 'bias'), _p(add, torch.float32, 'add'),
+                                  _p(y), N, Cc, Kk, H, W, int(mode), _stream())
+    _lib.check(rc, 'nhmc_conv3x3_wino_up')
     return y
 
 

@@ -213,16 +213,19 @@ class _Conv3x3Wino(torch.autograd.Function):
         return dx, None, None, (g if ctx.needs_input_grad[3] else None), None
 
 
-def wino_route(conv, x, wino=None):
+def wino_route(conv, x, wino=None, up=False):
     """(forward, backward) routing of `conv` applied to x onto the Winograd MFMA kernel, or None when it stays F.conv2d:
     a frozen 3x3 stride-1 padding-1 convolution of fp32 GPU activations whose shape the kernel covers and, per direction,
-    the library's measured table prefers (wino=True: wherever it is covered -- tests); NHMC_WINO=0 keeps the vendor library."""
+    the library's measured table prefers (wino=True: wherever it is covered -- tests); NHMC_WINO=0 keeps the vendor library.
+    up=True: the routing at twice x's resolution, for a convolution behind a nearest 2x upsample of x."""
     if wino is False or x.dim() != 4 or not fused_glue(x, conv.weight, conv.bias) or os.environ.get('NHMC_WINO', '1') == '0':
         return None
     if tuple(conv.kernel_size) != (3, 3) or tuple(conv.stride) != (1, 1) or conv.padding != (1, 1) \
             or tuple(conv.dilation) != (1, 1) or conv.groups != 1 or conv.padding_mode != 'zeros':
         return None
     n, c, h, w = x.shape
+    if up:
+        h, w = 2 * h, 2 * w
     k = conv.out_channels
     fwd, bwd = K.conv3x3_wino_k32_covers(n, c, k, h, w), K.conv3x3_wino_k32_covers(n, k, c, h, w)
     if not wino:                                        # a shape is in one table only: k32's rows have k % 64 == 32
@@ -230,6 +233,58 @@ def wino_route(conv, x, wino=None):
         bwd = bwd and (K.conv3x3_wino_prefers(1, n, k, c, h, w) or K.conv3x3_wino_k32_prefers(1, n, k, c, h, w))
     bwd = bwd and x.requires_grad and torch.is_grad_enabled()
     return (fwd, bwd) if fwd or bwd else None
+
+
+class _Conv3x3WinoUp(torch.autograd.Function):
+    """conv(nearest 2x upsample of x), no bias, with the upsampled tensor never in memory: the Winograd kernel reads the
+    low-res x (WINO_IN_UP) and skips the seven frequencies that are zero for such an input.  `pool`: the backward-data pass
+    writes the 2 x 2 block sums of its output, the gradient of x, from its epilogue (WINO_OUT_POOL); otherwise the
+    convolution's backward as in _Conv3x3Wino, then _Resample2x's."""
+
+    @staticmethod
+    def forward(ctx, x, weight, route_bwd, pool):
+        xc = x if x.is_contiguous() else x.contiguous()
+        ctx.save_for_backward(weight)
+        ctx.route_bwd, ctx.pool, ctx.x_shape = route_bwd, pool, tuple(x.shape)
+        return K.conv3x3_wino_up(xc, weight, K.WINO_IN_UP)
+
+    @staticmethod
+    def backward(ctx, g):
+        (weight,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        gc = g if g.is_contiguous() else g.contiguous()
+        if ctx.pool:
+            return K.conv3x3_wino_up(gc, weight, K.WINO_OUT_POOL, backward=True), None, None, None
+        B, C, h, w = ctx.x_shape
+        full = K.conv3x3_wino(gc, weight, backward=True) if ctx.route_bwd \
+            else torch.nn.grad.conv2d_input((B, C, 2 * h, 2 * w), weight, gc, 1, 1)
+        return K.sr_H(full, 2).view(B, C, h, w).mul_(4.0), None, None, None
+
+
+class _Conv3x3WinoAddUp(torch.autograd.Function):
+    """_Conv3x3Wino with the forward pass on the kernel and `add` at half the resolution, standing for its nearest 2x
+    upsample (WINO_ADD_UP): the residual of an up-sampling ResBlock.  The gradient reaches `add` as _Resample2x's backward
+    would form it, 4 x the 2 x 2 block means."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, add, route_bwd):
+        xc = x if x.is_contiguous() else x.contiguous()
+        ctx.save_for_backward(weight)
+        ctx.route_bwd, ctx.x_shape, ctx.add_shape = route_bwd, tuple(x.shape), tuple(add.shape)
+        return K.conv3x3_wino(xc, weight, bias, add if add.is_contiguous() else add.contiguous())    # low-res add: ADD_UP
+
+    @staticmethod
+    def backward(ctx, g):
+        (weight,) = ctx.saved_tensors
+        gc = g if g.is_contiguous() else g.contiguous()
+        dx = dadd = None
+        if ctx.needs_input_grad[0]:
+            dx = K.conv3x3_wino(gc, weight, backward=True) if ctx.route_bwd \
+                else torch.nn.grad.conv2d_input(ctx.x_shape, weight, gc, 1, 1)
+        if ctx.needs_input_grad[3]:
+            dadd = K.sr_H(gc, 2).view(ctx.add_shape).mul_(4.0)
+        return dx, None, None, dadd, None
 
 
 def conv_nobias(conv, x, wino=None):
@@ -288,9 +343,13 @@ class Resample(nn.Module):
         super().__init__()
         self.up = up
 
+    def on_kernels(self, x):
+        """True when x is resampled by the block-mean kernels (_Resample2x)."""
+        return fused_glue(x) and x.dim() == 4 and x.shape[2] == x.shape[3] and x.shape[0] <= 65535 \
+            and (x.shape[2] % 8 == 0 or (self.up and x.shape[2] % 2 == 0))
+
     def forward(self, x):
-        if fused_glue(x) and x.dim() == 4 and x.shape[2] == x.shape[3] and x.shape[0] <= 65535 \
-                and (x.shape[2] % 8 == 0 or (self.up and x.shape[2] % 2 == 0)):
+        if self.on_kernels(x):
             return _Resample2x.apply(x, self.up)
         return F.interpolate(x, scale_factor=2, mode='nearest') if self.up else F.avg_pool2d(x, 2)
 
@@ -303,12 +362,29 @@ class ResBlock(nn.Module):
         super().__init__()
         out_ch = out_ch or ch
         self.in_layers = nn.Sequential(nn.GroupNorm(32, ch), nn.SiLU(), nn.Conv2d(ch, out_ch, 3, padding=1))
-        self.resample = up or down
+        self.resample, self.up = up or down, up
         self.h_upd = self.x_upd = Resample(up) if self.resample else nn.Identity()
         self.emb_layers = nn.Sequential(nn.SiLU(), nn.Linear(emb_ch, 2 * out_ch))
         self.out_layers = nn.Sequential(nn.GroupNorm(32, out_ch), nn.SiLU(), nn.Identity(),
                                         nn.Conv2d(out_ch, out_ch, 3, padding=1))
         self.skip_connection = nn.Identity() if out_ch == ch else nn.Conv2d(ch, out_ch, 1)
+
+    def up_routes(self, h, x):
+        """An up-sampling block whose two upsamples fold into its convolutions (csrc/wino_conv.hip, "Nearest 2x upsample"):
+        ((forward, backward, pooled backward) of conv1, (forward, backward) of conv2), or None for the materialised path.
+        Both forward passes must be routed to the wide Winograd kernel at the upsampled shape, on eight waves
+        (NHMC_WINO_WAVES) and with NHMC_WINO_UP not 0 (both read per call); the skip path must be the identity; h and x
+        must be what the block-mean kernels would upsample."""
+        conv1, conv2 = self.in_layers[2], self.out_layers[3]
+        if not isinstance(self.skip_connection, nn.Identity) or not self.h_upd.on_kernels(h) or not self.x_upd.on_kernels(x) \
+                or x.shape != h.shape or not fused_glue(h, conv1.bias, conv2.bias):
+            return None
+        n, c, k, hh, ww = h.shape[0], conv1.in_channels, conv1.out_channels, 2 * h.shape[2], 2 * h.shape[3]
+        r1, r2 = wino_route(conv1, h, self.wino, up=True), wino_route(conv2, h, self.wino, up=True)
+        if r1 is None or r2 is None or not r1[0] or not r2[0] or conv2.in_channels != k \
+                or not K.conv3x3_wino_up_covers(n, c, k, hh, ww) or not K.conv3x3_wino_up_covers(n, k, k, hh, ww):
+            return None
+        return (True, r1[1], r1[1] and K.conv3x3_wino_up_covers(n, k, c, hh, ww)), (True, r2[1])
 
     def forward(self, x, emb):
         """x: the block input, or a pair (h, skip) standing for cat([h, skip], dim=1) (the output blocks)."""
@@ -316,9 +392,17 @@ class ResBlock(nn.Module):
             h, x = group_norm_act_pair(self.in_layers[0], *x)
         else:
             h, x = group_norm_act_fork(self.in_layers[0], x)             # GroupNorm + SiLU; x goes on to the skip path
-        if self.resample:
+        up = self.up_routes(h, x) if self.up else None
+        if self.resample and up is None:
             h, x = self.h_upd(h), self.x_upd(x)
         conv1, conv2, film = self.in_layers[2], self.out_layers[3], self.emb_layers(emb)
+        if up is not None and not fused_glue(h, conv1.bias, conv2.bias, film):
+            h, x, up = self.h_upd(h), self.x_upd(x), None
+        if up is not None:
+            # the upsampled h and x never reach memory: conv1 reads the low-res h, conv2's epilogue adds the low-res x
+            (_, bwd1, pool), (_, bwd2) = up
+            h = group_norm_act(self.out_layers[0], _Conv3x3WinoUp.apply(h, conv1.weight, bwd1, pool), film=film, pre=conv1.bias)
+            return _Conv3x3WinoAddUp.apply(h, conv2.weight, conv2.bias, x, bwd2)
         if fused_glue(h, conv1.bias, conv2.bias, film):
             # the two convolutions run without their broadcast bias passes: conv1's bias enters the next GroupNorm's
             # load, conv2's the residual add

@@ -6,12 +6,17 @@ median of 3 rounds of 10 event-timed launches per variant on rotating buffers th
 Cache.  Prints microseconds, the ratio kernel / F.conv2d and
 TFLOP/s in direct-convolution terms (2 * 9 * N * C * K * H * W).  Rows at or below 0.90 are what
 nhmc_conv3x3_wino_prefers and nhmc_conv3x3_wino_narrow_prefers may list.
-Usage: python tools/conv_bench.py [chains] [rounds] [--epilogue] [--only=C,K,res] [--latent]
+Usage: python tools/conv_bench.py [chains] [rounds] [--epilogue] [--only=C,K,res] [--latent] [--up]
 --epilogue adds, per forward row, the kernel with its (acc + bias) + add epilogue against kernel + k_bias_add2.
 --latent measures the latent sampler's two networks instead (ldm.conv3x3_shapes; chains defaults to 16, the chain count of
 BASELINE configs[4]): the score network's covered shapes forward only (it is evaluated without gradient), the first-stage
 decoder's forward and backward-data.  Rows at or below 0.90 with K % 64 == 32 are what nhmc_conv3x3_wino_k32_prefers may
-list; the others go to the two tables above."""
+list; the others go to the two tables above.
+--up times, at the up-sampling ResBlocks' shapes that the wide kernel covers (up_shapes(); --only=C,K,res overrides), the
+passes that carry a nearest 2x upsample to the convolution against the kernel's upsample forms (nhmc_conv3x3_wino_up), both
+alternating in one process: conv1 forward, sr_Ht + kernel against IN_UP on the low-res tensor; conv2 forward with its
+residual, sr_Ht + kernel with bias and add against ADD_UP; conv1 backward-data, kernel + sr_H + mul_(4) against OUT_POOL.
+Prints microseconds of each, the ratio fused / materialised, and the convolution alone for scale."""
 import sys
 import torch
 import torch.nn.functional as F
@@ -37,6 +42,65 @@ def latent_shapes(chains=16):
     return tuple(rows)
 
 
+def up_shapes(chains=64):
+    """(C, K, output resolution) of conv1 of every up-sampling ResBlock of FFHQ_CONFIG that the upsample forms cover."""
+    with torch.device('meta'):
+        model = unet.create_model(**unet.FFHQ_CONFIG)
+    seen, hooks = [], []
+    for mod in model.modules():
+        if isinstance(mod, unet.ResBlock) and mod.up:
+            hooks.append(mod.register_forward_hook(
+                lambda m, args, out: seen.append((m.in_layers[2].in_channels, m.in_layers[2].out_channels, out.shape[-1]))))
+    size = unet.FFHQ_CONFIG['image_size']
+    with torch.no_grad():
+        model(torch.empty(1, 3, size, size, device='meta'), torch.zeros(1, device='meta'))
+    for h in hooks:
+        h.remove()
+    return tuple(s for s in sorted(set(seen), key=lambda s: -s[2])
+                 if K.conv3x3_wino_up_covers(chains, s[0], s[1], s[2], s[2]) and K.conv3x3_wino_up_covers(chains, s[1], s[0], s[2], s[2]))
+
+
+def up_mode(B, ROUNDS, only):
+    """--up: see the module docstring."""
+    dev = torch.device('cuda')
+    print(f'chains {B}, rounds {ROUNDS}: us materialised | us fused | ratio (best of rounds) | us convolution alone')
+    for Cc, Kk, res in only or up_shapes(B):
+        w = torch.randn(Kk, Cc, 3, 3, device=dev) / (9 * Cc) ** 0.5
+        bias = torch.randn(Kk, device=dev)
+        low, full = res // 2, res
+        nbuf = max(2, -(-(320 << 20) // (B * min(Cc, Kk) * low * low * 4)))
+        lows = [torch.randn(B, Cc, low, low, device=dev) for _ in range(nbuf)]
+        nfull = max(2, -(-(320 << 20) // (B * min(Cc, Kk) * full * full * 4)))
+        fulls = [torch.randn(B, Cc, full, full, device=dev) for _ in range(nfull)]
+        grads = [torch.randn(B, Kk, full, full, device=dev) for _ in range(nfull)]
+        adds = [torch.randn(B, Kk, low, low, device=dev) for _ in range(nfull)]
+        up = lambda t, ch: K.sr_Ht(t.reshape(B, -1), 2, ch, full, 1.0).view(B, ch, full, full)
+        legs = (
+            ('conv1 fwd  IN_UP   ', lows, lambda t: K.conv3x3_wino(up(t, Cc), w), lambda t: K.conv3x3_wino_up(t, w, K.WINO_IN_UP),
+             lambda t: K.conv3x3_wino(fulls[0], w)),
+            ('conv2 fwd  ADD_UP  ', list(zip(fulls, adds)), lambda t: K.conv3x3_wino(t[0], w, bias, up(t[1], Kk)),
+             lambda t: K.conv3x3_wino_up(t[0], w, K.WINO_ADD_UP, bias, t[1]), lambda t: K.conv3x3_wino(t[0], w, bias, grads[0])),
+            ('conv1 bwd  OUT_POOL', grads, lambda t: K.sr_H(K.conv3x3_wino(t, w, backward=True), 2).mul_(4.0),
+             lambda t: K.conv3x3_wino_up(t, w, K.WINO_OUT_POOL, backward=True), lambda t: K.conv3x3_wino(t, w, backward=True)),
+        )
+        for name, bufs, mat, fused, alone in legs:
+            if name.startswith('conv2') and Cc != Kk:
+                continue
+            for _ in range(100 // len(bufs) + 1):
+                for t in bufs:
+                    mat(t)
+                    fused(t)
+            tm, tf, ta = [], [], []
+            for _ in range(ROUNDS):
+                tm.append(timeit(mat, bufs))
+                tf.append(timeit(fused, bufs))
+                ta.append(timeit(alone, bufs))
+            med = lambda v: sorted(v)[len(v) // 2]
+            print(f'[{B},{Cc}->{Kk},{res}x{res}] {name}: {med(tm) * 1e3:8.0f} | {med(tf) * 1e3:8.0f} | {med(tf) / med(tm):.3f} '
+                  f'({min(tf) / min(tm):.3f}) | {med(ta) * 1e3:8.0f}', flush=True)
+        del lows, fulls, grads, adds, w
+
+
 def timeit(f, bufs, n=10):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -54,6 +118,8 @@ def main():
     B = int(args[0]) if len(args) > 0 else 16 if LATENT else 64
     ROUNDS = int(args[1]) if len(args) > 1 else 3
     EPILOGUE = '--epilogue' in sys.argv
+    if '--up' in sys.argv:
+        return up_mode(B, ROUNDS, [tuple(int(v) for v in a[7:].split(',')) for a in sys.argv[1:] if a.startswith('--only=')])
     SHAPES = latent_shapes(B) if LATENT else tuple(s + ((False, True),) for s in default_shapes(B))
     print(f'chains {B}, rounds {ROUNDS}: us wino | us F.conv2d | ratio | TFLOP/s wino | TFLOP/s F.conv2d')
     ONLY = [tuple(int(v) for v in a[7:].split(',')) for a in sys.argv[1:] if a.startswith('--only=')]
