@@ -400,6 +400,58 @@ int nhmc_data_fourier_vjp(const float* xt_next, const float* y, const float* fac
                           const float* e, int e_channels, const float* at, const float* at_next, float* g_xt, float* g_e,
                           double* loss_ws, float* tmp, int n_chains, int channels, int dim, nhmc_stream_t stream);
 
+/* Modulated Fourier operators (--deg mcmri<R>: multi-coil MRI, SENSE; --deg cdp<K>: coded diffraction patterns).  Not in
+ * the reference.  The centred DFT of the image times K known complex maps, y_k = post(F (S_k o x) F^T):
+ *   d = dim, d % 32 == 0;  F = Cm + i Sm = centred_dft_factors(d, 0, d), fac the phase factors at pad = 0 (float[6 d d]);
+ *   maps: float[K][2][d][d], S_k = Sre_k + i Sim_k (a real and an imaginary plane per map), 1 <= K <= 32, every entry
+ *         finite, not all zero (the caller checks); the maps are shared by all channels and chains;
+ *   w   : float[d][d], real, >= 0 and finite, at least one entry > 0, centred layout (DC at [d/2][d/2]); all ones = no
+ *         weighting.
+ * Per chain b, channel c and map k, with v = x, or v = clip(x, -1, 1) under apply_clip:
+ *     A = Sre_k o v,  B = Sim_k o v                        one fp32 product each
+ *     Re Y = Re Y_A - Im Y_B,   Im Y = Im Y_A + Re Y_B     Y_A, Y_B: what nhmc_phase_H(mode 1, pad 0) gives for A and B
+ *   linear  (modulus = 0):  H(x) = [w o Re Y ; w o Im Y]      [n_chains][C][K][2][d][d],  M = 2 C K d^2
+ *                           r = y - w o Y where w > 0, EXACTLY 0 elsewhere (a selection, as nhmc_data_fourier);  q = w o r
+ *   modulus (modulus = 1):  a = sqrtf(Re^2 + Im^2),  H(x) = w o a      [n_chains][C][K][d][d],  M = C K d^2
+ *                           r = y - w a where w > 0, else 0;  q = a == 0 ? 0 : (w r) (Y / a)   (nhmc_data_phase's rule: a
+ *                           NaN |Y| stays NaN)
+ *     loss_b = sum r^2   (fp32 squares, fp64 partials: nhmc_modfourier_tiles per chain, summed in a fixed order)
+ *     U_k = Re[F^H q_k conj(F)] = adj(q_re, q_im),   V_k = Im[F^H q_k conj(F)] = adj(q_im, -q_re)
+ *                                                          adj = nhmc_phase_adjoint at pad 0
+ *     g   = -2 sum_k (Sre_k o U_k + Sim_k o V_k)   [o clip mask of x, selected as everywhere]
+ *     H^T(v) (linear only) = sum_k (Sre_k o U_k + Sim_k o V_k) with q = w o v
+ * The sum over k ascends from 0.0f; one fixed expression serves H^T, the data term and the fused form, so the fused form
+ * is the split path bit for bit, and a chain's bits do not depend on the batch it sits in.
+ * Three streaming kernels (csrc/mod_fourier.hip: modulate, combine, demodulate) around the phase chain, which runs on
+ * n_chains * C * 2K planes at pad 0: 48 d^3 FLOP per (plane, map).  n_chains * C * 2K <= 65535 (the chain's plane limit).
+ * tmp: float[nhmc_modfourier_tmp_floats(...)]: 7 d^2 floats per modulated plane (the planes A and B, their spectra, the
+ * chain's own scratch), at most 8 d^2.  The entries walk the chains in slabs of at most 1024 modulated planes (chains are
+ * independent), which caps the scratch: 64 chains x 3 channels x 8 maps at 256^2 are 3072 planes, 6.4 GB at 8 d^2 floats
+ * each if taken at once, 1.9 GB in slabs.
+ *   nhmc_modfourier_H       : out = H(x).
+ *   nhmc_modfourier_Ht      : out = H^T(v) [n_chains][C][d][d], v [n_chains][C][K][2][d][d]; linear only, so `modulus` is
+ *                             no parameter.
+ *   nhmc_data_modfourier    : loss partials and g_xt as above.  The entries of y under w = 0 are loaded and dropped by a
+ *                             select: noise, NaN or inf there changes no bit; a NaN in a measured entry propagates.
+ *   nhmc_data_modfourier_vjp: the same on xt_next (the clipped decode of the LAST DDIM step) with that step's VJP in the
+ *                             demodulating kernel's epilogue: writes g_xt and channels [0, C) of g_e.
+ * Return codes: NHMC_ERR_ARG for a null pointer or modulus outside {0, 1}; NHMC_ERR_SHAPE for dim % 32, n_maps outside
+ * 1...32, n_chains * channels * 2 * n_maps > 65535, e_channels outside {C, 2C}; NHMC_ERR_ALIGN for a pointer that is not
+ * 16-byte aligned.  Shape is checked before alignment. */
+int nhmc_modfourier_tiles(int channels, int n_maps, int dim);
+size_t nhmc_modfourier_tmp_floats(int n_chains, int channels, int n_maps, int dim);
+int nhmc_modfourier_H(const float* x, const float* maps, const float* fac, const float* w, int modulus, float* out,
+                      float* tmp, int n_chains, int channels, int n_maps, int dim, nhmc_stream_t stream);
+int nhmc_modfourier_Ht(const float* v, const float* maps, const float* fac, const float* w, float* out, float* tmp,
+                       int n_chains, int channels, int n_maps, int dim, nhmc_stream_t stream);
+int nhmc_data_modfourier(const float* xt, const float* y, const float* maps, const float* fac, const float* w, int modulus,
+                         int apply_clip, float* g_xt, double* loss_ws, float* tmp, int n_chains, int channels, int n_maps,
+                         int dim, nhmc_stream_t stream);
+int nhmc_data_modfourier_vjp(const float* xt_next, const float* y, const float* maps, const float* fac, const float* w,
+                             int modulus, const float* xt, const float* e, int e_channels, const float* at,
+                             const float* at_next, float* g_xt, float* g_e, double* loss_ws, float* tmp, int n_chains,
+                             int channels, int n_maps, int dim, nhmc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * General 2-D PSF blur (--deg deblur_motion): camera shake, defocus, any measured PSF.  Not in the reference's
  * prepare_measurement (its README names an external motion-blur generator that is never wired); the two blurs it has

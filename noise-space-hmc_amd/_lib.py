@@ -77,6 +77,12 @@ SIGNATURES = {
     'nhmc_fourier_H': (I, [P, P, P, P, P, I, I, I, P]),
     'nhmc_data_fourier': (I, [P, P, P, P, I, P, P, P, I, I, I, P]),
     'nhmc_data_fourier_vjp': (I, [P, P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, P]),
+    'nhmc_modfourier_tiles': (I, [I, I, I]),
+    'nhmc_modfourier_tmp_floats': (SZ, [I, I, I, I]),
+    'nhmc_modfourier_H': (I, [P, P, P, P, I, P, P, I, I, I, I, P]),
+    'nhmc_modfourier_Ht': (I, [P, P, P, P, P, P, I, I, I, I, P]),
+    'nhmc_data_modfourier': (I, [P, P, P, P, P, I, I, P, P, P, I, I, I, I, P]),
+    'nhmc_data_modfourier_vjp': (I, [P, P, P, P, P, I, P, P, I, P, P, P, P, P, P, I, I, I, I, P]),
     'nhmc_blur2d_check_taps': (I, [P, I, I]),
     'nhmc_blur2d_tiles': (I, [I, I]),
     'nhmc_blur2d_apply': (I, [P, P, P, I, I, I, P, I, I, I, P]),

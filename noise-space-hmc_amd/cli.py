@@ -35,6 +35,16 @@ set.  `--deg fourier --kspace_mask FILE.npy` takes any real weight map [image_si
 instead: partial Fourier, band limits, a measured sampling density.  With `--save_images` rank 0 also writes
 `kspace_mask.png`, the weights scaled to their maximum, once.
 
+`--deg mcmri<R>` (not in the reference) is multi-coil accelerated MRI (SENSE): `--coils K` receive coils (default 8, 1 ...
+32), each seeing the image times its complex sensitivity map (operators.coil_maps, deterministic), all undersampled by the
+Cartesian mask of `mri<R>`, through the modulated-Fourier kernels (operators.ModulatedFourier); the measurement is
+[Re ; Im] per plane and coil, M = 2 C K image_size^2.  `--coil_maps FILE.npy` takes the maps from a complex or real
+[K, image_size, image_size] array instead; it goes only with `mcmri<R>`.  With `--save_images` rank 0 also writes
+`kspace_mask.png` and `coil_maps.png`, the K magnitudes side by side scaled to their maximum, once.  `--deg cdp<K>` (not in
+the reference) is coded diffraction: the K moduli |F (M_k o x) F^T| behind K random unit-modulus masks
+(operators.diffraction_masks, drawn from the global torch RNG right after the seed is set), M = C K image_size^2 -- the
+well-posed form of `phase_retrieval`; nonlinear, through the same kernels.
+
 `--replicas K` spends the chains on K replica chains per image instead (a batch then holds `--chains` // K images, chain
 i * K + r being replica r of the batch's image i): all replicas see the same measurement, replica 0 starts where the
 single chain starts, replicas r >= 1 start from their own N(0,1) draw keyed by (seed, s, r), and the Philox stream of
@@ -111,6 +121,10 @@ def get_parser(latent=False):
     p.add_argument('--kspace_mask', type=str, default=None, metavar='FILE.npy',
                    help='--deg fourier: the k-space weight map, a real [image_size, image_size] array (>= 0, DC at the '
                         'centre; a binary mask is the common case), shared by all channels')
+    p.add_argument('--coils', type=int, default=8, help='--deg mcmri<R>: the number of synthetic receive coils (1 ... 32)')
+    p.add_argument('--coil_maps', type=str, default=None, metavar='FILE.npy',
+                   help='--deg mcmri<R>: the coil sensitivities, a complex or real [K, image_size, image_size] array, instead '
+                        'of the synthetic ones')
     p.add_argument('--graph', dest='use_graph', action='store_true',
                    help='replay each decode+gradient chunk as a hipGraph (helps single-chain runs: ~1.2x)')
     p.add_argument('--hmc_epochs', type=int, default=60, help='annealing epochs (reference: 60, main_sampling.py:665)')
@@ -281,6 +295,10 @@ def _setup(opt, latent):
     # mask = first torch RNG draw, as in the reference
     operator_file = getattr(opt, 'operator', None)
     kspace_mask_file = getattr(opt, 'kspace_mask', None)
+    coil_maps_file = getattr(opt, 'coil_maps', None)
+    multi_coil = opt.deg.startswith('mcmri') and opt.deg[5:].isdigit()
+    if coil_maps_file and not multi_coil:
+        raise SystemExit('--coil_maps FILE.npy goes only with --deg mcmri<R>')
     if opt.deg == 'sparse' or operator_file:
         if opt.deg != 'sparse' or not operator_file:
             raise SystemExit('--deg sparse and --operator FILE.npz go together')
@@ -295,6 +313,11 @@ def _setup(opt, latent):
             op = operators.build_operator(opt.deg, ch, size, device, kspace_mask_file=kspace_mask_file)
         except operators.NhmcError as exc:
             raise SystemExit(str(exc))
+    elif multi_coil or (opt.deg.startswith('cdp') and opt.deg[3:].isdigit()):
+        try:
+            op = operators.build_operator(opt.deg, ch, size, device, n_coils=getattr(opt, 'coils', 8), coil_maps_file=coil_maps_file)
+        except operators.NhmcError as exc:
+            raise SystemExit(str(exc))
     else:
         op = operators.build_operator(opt.deg, ch, size, device, spectral_projected=opt.spectral_projected or None)
     if opt.save_images and rank == 0 and isinstance(op, operators.Blur2D):
@@ -302,9 +325,12 @@ def _setup(opt, latent):
         span = float(k.max() - k.min())
         k01 = (k - k.min()) / span if span > 0 else torch.ones_like(k)
         sampler._save_png((2 * k01 - 1)[None].expand(3, -1, -1), os.path.join(opt.image_folder, 'blur_kernel.png'))
-    if opt.save_images and rank == 0 and isinstance(op, operators.FourierSampling):
+    if opt.save_images and rank == 0 and (isinstance(op, operators.FourierSampling) or multi_coil):
         w01 = op.weights / op.weights.max()                                 # max > 0: the constructor checked
         sampler._save_png((2 * w01 - 1)[None].expand(3, -1, -1), os.path.join(opt.image_folder, 'kspace_mask.png'))
+    if opt.save_images and rank == 0 and multi_coil:                        # the K magnitudes side by side
+        mag = torch.cat(list(op.maps.abs()), dim=1)
+        sampler._save_png((2 * mag / mag.max() - 1)[None].expand(3, -1, -1), os.path.join(opt.image_folder, 'coil_maps.png'))
     opt.sigma_0 = 2 * opt.sigma_0                                           # [-1,1] scaling, main_sampling.py:348
     if world > 1 and not opt.philox:
         if rank == 0:

@@ -751,6 +751,89 @@ def data_fourier_vjp(xt_next, y, fac, w, xt, e, at, at_next, g_e_out=None, loss_
     return (loss, *outs)
 
 
+# ---- modulated Fourier operators (mcmri<R>, cdp<K>): the spectrum of the image times K complex maps --------
+def _modfourier_shapes(x, maps, fac, w):
+    """x: [B, C, d, d]; maps: [K, 2, d, d] (a real and an imaginary plane per map); fac: the phase factors at pad = 0;
+    w: the weight map [d, d] -> B, C, K, d."""
+    B, Cc, dim, _ = _phase_shapes(x, fac, 0)
+    if maps.dim() != 4 or tuple(maps.shape[1:]) != (2, dim, dim) or not 1 <= maps.shape[0] <= 32:
+        raise _lib.NhmcError(f'the modulation maps must be [K, 2, {dim}, {dim}] with 1 <= K <= 32, got {tuple(maps.shape)}')
+    if tuple(w.shape) != (dim, dim):
+        raise _lib.NhmcError(f'the k-space weights must be [{dim}, {dim}], got {tuple(w.shape)}')
+    if B * Cc * 2 * maps.shape[0] > 65535:
+        raise _lib.NhmcError(f'{B} chains x {Cc} channels x {maps.shape[0]} maps are {B * Cc * 2 * maps.shape[0]} modulated '
+                             f'planes, the spectral chain takes 65535 per call')
+    return B, Cc, maps.shape[0], dim
+
+
+def _modfourier_tmp(B, Cc, Km, dim, device):
+    return torch.empty(_lib.load().nhmc_modfourier_tmp_floats(B, Cc, Km, dim), dtype=torch.float32, device=device)
+
+
+def _modfourier_obs_shape(B, Cc, Km, dim, modulus):
+    return (B, Cc, Km, dim, dim) if modulus else (B, Cc, Km, 2, dim, dim)
+
+
+def _modfourier_io(xt, y, maps, fac, w, modulus):
+    """What data_modfourier and data_modfourier_vjp share -> (tiles, tmp, operands (y, maps, fac, w, modulus), the trailing
+    (B, C, K, dim))."""
+    B, Cc, Km, dim = _modfourier_shapes(xt, maps, fac, w)
+    want = _modfourier_obs_shape(B, Cc, Km, dim, modulus)
+    if tuple(y.shape) != want:
+        raise _lib.NhmcError(f'the observation must be {list(want)}, got {tuple(y.shape)}')
+    ops = (_p(y, torch.float32, 'y'), _p(maps, torch.float32, 'maps'), _p(fac, torch.float32, 'fac'), _p(w, torch.float32, 'w'),
+           int(bool(modulus)))
+    return (_lib.load().nhmc_modfourier_tiles(Cc, Km, dim), _modfourier_tmp(B, Cc, Km, dim, xt.device), ops, (B, Cc, Km, dim))
+
+
+def modfourier_H(x, maps, fac, w, modulus=False):
+    """The centred orthonormal 2-D DFT of every plane times every map, weighted: [B, C, d, d] -> [w o Re Y ; w o Im Y]
+    [B, C, K, 2, d, d], or under `modulus` w o |Y| [B, C, K, d, d]."""
+    lib = _lib.load()
+    B, Cc, Km, dim = _modfourier_shapes(x, maps, fac, w)
+    out = torch.empty(_modfourier_obs_shape(B, Cc, Km, dim, modulus), dtype=torch.float32, device=x.device)
+    tmp = _modfourier_tmp(B, Cc, Km, dim, x.device)
+    rc = lib.nhmc_modfourier_H(_p(x, torch.float32, 'x'), _p(maps, torch.float32, 'maps'), _p(fac, torch.float32, 'fac'),
+                               _p(w, torch.float32, 'w'), int(bool(modulus)), _p(out), _p(tmp), B, Cc, Km, dim, _stream())
+    _lib.check(rc, 'nhmc_modfourier_H')
+    return out
+
+
+def modfourier_Ht(v, maps, fac, w):
+    """The exact adjoint of the linear modfourier_H: v [B, C, K, 2, d, d] -> [B, C, d, d]."""
+    lib = _lib.load()
+    if v.dim() != 6 or v.shape[3] != 2:
+        raise _lib.NhmcError(f'modfourier_Ht takes [B, C, K, 2, d, d], got {tuple(v.shape)}')
+    B, Cc, Km, dim = _modfourier_shapes(v[:, :, 0, 0], maps, fac, w)
+    if v.shape[2] != Km:
+        raise _lib.NhmcError(f'modfourier_Ht: v holds {v.shape[2]} maps, the operator {Km}')
+    out = torch.empty(B, Cc, dim, dim, dtype=torch.float32, device=v.device)
+    tmp = _modfourier_tmp(B, Cc, Km, dim, v.device)
+    rc = lib.nhmc_modfourier_Ht(_p(v, torch.float32, 'v'), _p(maps, torch.float32, 'maps'), _p(fac, torch.float32, 'fac'),
+                                _p(w, torch.float32, 'w'), _p(out), _p(tmp), B, Cc, Km, dim, _stream())
+    _lib.check(rc, 'nhmc_modfourier_Ht')
+    return out
+
+
+def data_modfourier(xt, y, maps, fac, w, modulus=False, apply_clip=True, loss_out=None):
+    """-> (loss [B] float64, g_xt) for the modulated Fourier operator; y as modfourier_H returns it, read only where w > 0."""
+    tiles, tmp, ops, dims = _modfourier_io(xt, y, maps, fac, w, modulus)
+    g = torch.empty_like(xt)
+    loss = _two_pass('nhmc_data_modfourier', tiles, dims[0], xt.device, loss_out,
+                     (_p(xt, torch.float32, 'xt'), *ops, int(apply_clip), _p(g)), (_p(tmp), *dims))
+    return loss, g
+
+
+def data_modfourier_vjp(xt_next, y, maps, fac, w, modulus, xt, e, at, at_next, g_e_out=None, loss_out=None):
+    """The modulated Fourier data term on the clipped decode `xt_next` + VJP of the last DDIM step (inputs xt, e) in the
+    demodulating kernel's epilogue -> (loss [B] float64, g_xt, g_e)."""
+    _, mix, grads, outs, alphas = _last_vjp_io(xt, e, at, at_next, g_e_out, False)
+    tiles, tmp, ops, dims = _modfourier_io(xt, y, maps, fac, w, modulus)
+    loss = _two_pass('nhmc_data_modfourier_vjp', tiles, dims[0], xt.device, loss_out,
+                     (_xt_next(xt_next, xt), *ops, *mix, *grads), (_p(tmp), *dims))
+    return (loss, *outs)
+
+
 # ---- general 2-D PSF blur (deblur_motion) --------------------------------------------------------
 class BlurTaps:
     """The compacted tap list of a 2-D PSF (include/nhmc.h): the non-zero entries of k [K, K] in row-major order as

@@ -1,7 +1,8 @@
 """Forward operators with the reference's `H_functions` surface, on the HIP kernels (the linear ones, the two
-nonlinear ones that need nothing from outside: HDR and phase retrieval, and three that the reference does not have: a
-general 2-D PSF blur, `Blur2D`, any linear operator given as a sparse matrix, `SparseLinear`, and any weighting of the
-centred 2-D spectrum, `FourierSampling`).
+nonlinear ones that need nothing from outside: HDR and phase retrieval, and four that the reference does not have: a
+general 2-D PSF blur, `Blur2D`, any linear operator given as a sparse matrix, `SparseLinear`, any weighting of the
+centred 2-D spectrum, `FourierSampling`, and the spectrum of the image times K complex maps, weighted or as a modulus,
+`ModulatedFourier`).
 
 Mirrors obs_functions/Hfuncs.py for the three operators on the HMC hot path -- same constructor
 arguments, same `H / Ht / H_pinv / is_linear`, inputs `[B, ...]`, outputs `[B, flat]` -- but each
@@ -554,6 +555,22 @@ class PhaseRetrievalOperator(DecodeFused):
         return K.data_phase_vjp(xt_next, obs, self.factors, self.pad, xt_in, e, at, at_next, g_e_out=g_e_out, loss_out=loss_out)
 
 
+def checked_kspace_weights(weights, img_dim):
+    """A k-space weight map as the Fourier operators take it: a real [img_dim, img_dim] array, finite, >= 0, at least one
+    entry > 0 -> a float32 host tensor of its own."""
+    w = torch.as_tensor(weights).detach().cpu()
+    if w.dim() != 2 or tuple(w.shape) != (img_dim, img_dim):
+        raise NhmcError(f'the k-space weights must be [{img_dim}, {img_dim}], got {tuple(w.shape)}')
+    if w.is_complex():
+        raise NhmcError('the k-space weights must be real')
+    w = w.to(torch.float32)
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise NhmcError('the k-space weights must be finite and >= 0')
+    if not bool((w > 0).any()):
+        raise NhmcError('the k-space weights measure nothing: at least one entry must be > 0')
+    return w.contiguous().clone()
+
+
 class FourierSampling(DecodeFused):
     """A forward model that lives in Fourier space (undersampled k-space, partial Fourier, band-limited optics): with
     F = Cm + i Sm = centred_dft_factors(d, 0, d) and Y_c = F X_c F^T per channel plane,
@@ -567,17 +584,7 @@ class FourierSampling(DecodeFused):
         self.channels, self.img_dim, self.device = channels, img_dim, device
         if img_dim <= 0 or img_dim % 32:
             raise NhmcError(f'Fourier sampling needs img_dim % 32 == 0, got {img_dim}')
-        w = torch.as_tensor(weights).detach().cpu()
-        if w.dim() != 2 or tuple(w.shape) != (img_dim, img_dim):
-            raise NhmcError(f'the k-space weights must be [{img_dim}, {img_dim}], got {tuple(w.shape)}')
-        if w.is_complex():
-            raise NhmcError('the k-space weights must be real')
-        w = w.to(torch.float32)
-        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
-            raise NhmcError('the k-space weights must be finite and >= 0')
-        if not bool((w > 0).any()):
-            raise NhmcError('the k-space weights measure nothing: at least one entry must be > 0')
-        self.weights = w.contiguous().clone()                       # float32, host: what `kspace_mask.png` shows
+        self.weights = checked_kspace_weights(weights, img_dim)     # float32, host: what `kspace_mask.png` shows
         self.W = self.weights.to(device)
         self.M = 2 * channels * img_dim * img_dim
         Cm, Sm = centred_dft_factors(img_dim, 0, img_dim)
@@ -650,6 +657,135 @@ def load_kspace_mask(path, img_dim):
     if not (a > 0).any():
         raise NhmcError(f'--kspace_mask: {path}: the weights measure nothing (all zero)')
     return torch.from_numpy(np.ascontiguousarray(a.astype(np.float32)))
+
+
+class ModulatedFourier(DecodeFused):
+    """The centred DFT of the image times K known complex maps (not in the reference): with F = Cm + i Sm =
+    centred_dft_factors(d, 0, d), maps S_k [d, d] complex and Y_{c,k} = F (S_k o X_c) F^T per channel plane and map,
+        linear  (modulus=False): H(x) = [W o Re Y ; W o Im Y]   [B, C, K, 2, d, d] flattened to [B, M], M = 2 C K d^2,
+                                 Ht(v) = sum_k Re[conj(S_k) o F^H (W o (v_re + i v_im)_k) conj(F)], the exact adjoint;
+        modulus (modulus=True):  H(x) = W o |Y|                 [B, C, K, d, d], M = C K d^2 (nonlinear: no Ht).
+    Multi-coil MRI (SENSE) is the linear form with coil sensitivities as maps and the sampling mask as W; coded diffraction
+    is the modulus form with unit-modulus random masks and W = 1.  `maps` is a complex or real [K, d, d] tensor or array,
+    1 <= K <= 32, every entry finite, not all zero, shared by all channels and chains; `weights` as FourierSampling's (None:
+    all ones).  The data term reads the observation only where W > 0 (include/nhmc.h).  The spectra are
+    PhaseRetrievalOperator's MFMA chain at pad = 0 on the real and the imaginary plane of every S_k o x."""
+
+    def __init__(self, maps, channels, img_dim, device, weights=None, modulus=False):
+        self.channels, self.img_dim, self.device, self.modulus = channels, img_dim, device, bool(modulus)
+        if img_dim <= 0 or img_dim % 32:
+            raise NhmcError(f'the modulated Fourier operator needs img_dim % 32 == 0, got {img_dim}')
+        try:
+            s = torch.as_tensor(maps).detach().cpu()
+        except (TypeError, ValueError, RuntimeError) as exc:
+            raise NhmcError(f'the modulation maps must be a complex or real tensor or array ({exc})') from exc
+        if s.dim() != 3 or tuple(s.shape[1:]) != (img_dim, img_dim):
+            raise NhmcError(f'the modulation maps must be [K, {img_dim}, {img_dim}], got {tuple(s.shape)}')
+        if not 1 <= s.shape[0] <= 32:
+            raise NhmcError(f'the modulated Fourier operator takes 1 to 32 maps, got {s.shape[0]}')
+        if s.dtype == torch.bool:
+            raise NhmcError('the modulation maps must be complex or real numbers, got booleans')
+        s = s.to(torch.complex64)
+        if not bool(torch.isfinite(torch.view_as_real(s)).all()):
+            raise NhmcError('the modulation maps must be finite')
+        if not bool((s != 0).any()):
+            raise NhmcError('the modulation maps are all zero: nothing is measured')
+        self.maps = s.contiguous().clone()                          # complex64, host: what `coil_maps.png` shows
+        self.n_maps = s.shape[0]
+        self.S = torch.view_as_real(self.maps).permute(0, 3, 1, 2).contiguous().to(device)   # [K, 2, d, d]: re and im planes
+        self.weights = checked_kspace_weights(torch.ones(img_dim, img_dim) if weights is None else weights, img_dim)
+        self.W = self.weights.to(device)
+        self.M = (1 if self.modulus else 2) * channels * self.n_maps * img_dim * img_dim
+        Cm, Sm = centred_dft_factors(img_dim, 0, img_dim)
+        self.Cm, self.Sm = Cm, Sm                                   # float64, host: the definition the tests restate
+        self.factors = packed_dft_factors(Cm, Sm, device)           # PhaseRetrievalOperator's, at n = d
+        if self.modulus:
+            self.forward = self.H
+
+    def is_linear(self):
+        return not self.modulus
+
+    def _observation(self, y, shape):
+        tail = (self.img_dim, self.img_dim) if self.modulus else (2, self.img_dim, self.img_dim)
+        return y.reshape(shape[0], self.channels, self.n_maps, *tail).contiguous()
+
+    def H(self, vec):
+        x = _img(vec, self.channels, self.img_dim)
+        return K.modfourier_H(x, self.S, self.factors, self.W, self.modulus).reshape(x.shape[0], -1)
+
+    def Ht(self, vec):
+        if self.modulus:
+            raise NotImplementedError('the modulus form of the modulated Fourier operator is nonlinear: it has no adjoint')
+        return K.modfourier_Ht(self._observation(vec, vec.shape), self.S, self.factors, self.W).reshape(vec.shape[0], -1)
+
+    def H_pinv(self, vec):
+        raise NotImplementedError('the modulated Fourier operator has no pseudo-inverse here; no sampler calls H_pinv')
+
+    def data_term(self, xt, y, apply_clip=True, loss_out=None):
+        return K.data_modfourier(xt, self._observation(y, xt.shape), self.S, self.factors, self.W, self.modulus, apply_clip,
+                                 loss_out=loss_out)
+
+    def _data_vjp(self, xt_next, obs, xt_in, e, at, at_next, g_e_out, loss_out):
+        return K.data_modfourier_vjp(xt_next, obs, self.S, self.factors, self.W, self.modulus, xt_in, e, at, at_next,
+                                     g_e_out=g_e_out, loss_out=loss_out)
+
+
+def coil_maps(img_dim, n_coils):
+    """Synthetic receive-coil sensitivities [K, d, d] complex64, our own construction, deterministic: K coils on a circle
+    around the image.  With c = (d - 1) / 2 and theta_k = 2 pi k / K, coil k has the magnitude
+    exp(-((row - c - 0.6 d sin theta_k)^2 + (col - c - 0.6 d cos theta_k)^2) / (2 (0.5 d)^2)) and the phase
+    pi ((col - c) cos theta_k + (row - c) sin theta_k) / d + theta_k; the K maps are then divided by sqrt(sum_k |S_k|^2)
+    per pixel, so that sum_k |S_k|^2 = 1 (the operator is an isometry under full sampling).  Built in float64."""
+    d, Kc = int(img_dim), int(n_coils)
+    if d < 1 or not 1 <= Kc <= 32:
+        raise NhmcError(f'coil_maps: needs img_dim >= 1 and 1 <= n_coils <= 32, got img_dim {img_dim}, n_coils {n_coils}')
+    c = (d - 1) / 2
+    row = (torch.arange(d, dtype=torch.float64) - c)[None, :, None]
+    col = (torch.arange(d, dtype=torch.float64) - c)[None, None, :]
+    theta = (2 * math.pi * torch.arange(Kc, dtype=torch.float64) / Kc)[:, None, None]
+    mag = torch.exp(-((row - 0.6 * d * torch.sin(theta)) ** 2 + (col - 0.6 * d * torch.cos(theta)) ** 2) / (2 * (0.5 * d) ** 2))
+    phase = math.pi * (col * torch.cos(theta) + row * torch.sin(theta)) / d + theta
+    s = torch.polar(mag, phase)
+    return (s / (s.abs() ** 2).sum(dim=0, keepdim=True).sqrt()).to(torch.complex64)
+
+
+def diffraction_masks(img_dim, n_masks, generator=None):
+    """The K modulation masks of coded diffraction [K, d, d] complex64, our own construction: exp(2 pi i u) with
+    u = torch.rand(K, d, d, dtype=float64) from `generator` (the global torch RNG when None, so every rank holds the same
+    masks after torch.manual_seed); unit modulus."""
+    d, Km = int(img_dim), int(n_masks)
+    if d < 1 or not 1 <= Km <= 32:
+        raise NhmcError(f'diffraction_masks: needs img_dim >= 1 and 1 <= n_masks <= 32, got img_dim {img_dim}, n_masks {n_masks}')
+    u = torch.rand(Km, d, d, dtype=torch.float64, generator=generator)
+    return torch.polar(torch.ones_like(u), 2 * math.pi * u).to(torch.complex64)
+
+
+def load_coil_maps(path, img_dim):
+    """The maps of `--deg mcmri<R> --coil_maps FILE.npy`: a complex or real [K, img_dim, img_dim] array saved with
+    numpy.save, read with np.load(allow_pickle=False) -> complex64 tensor.  Every refusal names the file."""
+    import numpy as np
+    if not os.path.isfile(path):
+        raise NhmcError(f'--coil_maps: no such file: {path}')
+    try:
+        a = np.load(path, allow_pickle=False)
+    except Exception as exc:
+        raise NhmcError(f'--coil_maps: {path} is not a .npy array ({exc})') from exc
+    if not isinstance(a, np.ndarray):
+        raise NhmcError(f'--coil_maps: {path} is an archive, not a single .npy array')
+    if a.ndim != 3:
+        raise NhmcError(f'--coil_maps: {path} has rank {a.ndim}, expected a 3-D array [K, {img_dim}, {img_dim}]')
+    if a.shape[1:] != (img_dim, img_dim):
+        raise NhmcError(f'--coil_maps: {path} holds maps of {a.shape[1]} x {a.shape[2]}, the image is {img_dim} x {img_dim}')
+    if not 1 <= a.shape[0] <= 32:
+        raise NhmcError(f'--coil_maps: {path} holds {a.shape[0]} maps, 1 to 32 are taken')
+    if a.dtype.kind not in 'iufc':
+        raise NhmcError(f'--coil_maps: {path} holds {a.dtype}, expected complex or real numbers')
+    a = a.astype(np.complex128)
+    if not (np.isfinite(a.real).all() and np.isfinite(a.imag).all()):
+        raise NhmcError(f'--coil_maps: {path}: the maps must be finite')
+    if not (a != 0).any():
+        raise NhmcError(f'--coil_maps: {path}: the maps are all zero')
+    return torch.from_numpy(np.ascontiguousarray(a.astype(np.complex64)))
 
 
 class Blur2D(DecodeFused):
@@ -867,11 +1003,12 @@ def gaussian_taps(sigma, half=4):
 
 
 def build_operator(deg, channels, img_dim, device, generator=None, spectral_projected=None, operator_file=None,
-                   kspace_mask_file=None):
+                   kspace_mask_file=None, n_coils=8, coil_maps_file=None):
     """`prepare_measurement` (main_sampling.py:261-351) for the degradations on the HMC hot path.
     spectral_projected: the four-product data term of the two blur operators (see Deblurring2D).
     operator_file: the CSR .npz of `sparse` (load_sparse_npz).
-    kspace_mask_file: the weight map .npy of `fourier` (load_kspace_mask)."""
+    kspace_mask_file: the weight map .npy of `fourier` (load_kspace_mask).
+    n_coils, coil_maps_file: the synthetic coil count of `mcmri<R>` (coil_maps), or its maps as a .npy (load_coil_maps)."""
     if deg.startswith('sr_bicubic') and deg[10:].isdigit():
         factor = int(deg[10:])
         return SRConv(bicubic_taps(factor), channels, img_dim, device, stride=factor)
@@ -922,4 +1059,13 @@ def build_operator(deg, channels, img_dim, device, generator=None, spectral_proj
         if not kspace_mask_file:
             raise NhmcError('--deg fourier needs --kspace_mask FILE.npy (a real [image_size, image_size] array, DC at the centre)')
         return FourierSampling(load_kspace_mask(kspace_mask_file, img_dim), channels, img_dim, device)
+    if deg.startswith('mcmri') and deg[5:].isdigit():                   # not in the reference: multi-coil accelerated MRI
+        accel = int(deg[5:])
+        if accel < 1 or img_dim // accel < 1:
+            raise NhmcError(f'mcmri<R> needs R >= 1 and image_size // R >= 1, got R = {accel} at image size {img_dim}')
+        mask = cartesian_mask(img_dim, accel, generator)
+        maps = load_coil_maps(coil_maps_file, img_dim) if coil_maps_file else coil_maps(img_dim, n_coils)
+        return ModulatedFourier(maps, channels, img_dim, device, weights=mask)
+    if deg.startswith('cdp') and deg[3:].isdigit():                     # not in the reference: coded diffraction patterns
+        return ModulatedFourier(diffraction_masks(img_dim, int(deg[3:]), generator), channels, img_dim, device, modulus=True)
     raise NotImplementedError(f'degradation {deg!r} is outside the HMC hot path of this build')

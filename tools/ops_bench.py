@@ -19,15 +19,15 @@ T = B * 3 * 256 * 256 * 4
 # term written with torch.fft + autograd (its last-step VJP by autograd through the clipped DDIM mix); medians.  FLOP model
 # per plane at n = d: 2 d d 2d + 8 (2 d d d) + 2 d d 2d = 24 d^3 (stage 1, the two four-product stages, stage 4).
 # `python tools/ops_bench.py 64 fourier` runs this leg alone.
+def timed(f, warm=10, n=100):
+    for _ in range(warm): f()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n): f()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
 def fourier_leg():
-    def timed(f, warm=10, n=100):
-        for _ in range(warm): f()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n): f()
-        e1.record(); torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n
     d = 256
     om = operators.build_operator('mri4', 3, d, dev, generator=torch.Generator().manual_seed(5678))
     e6 = K.randn_philox((B, 6, d, d), 1, 0, 2)
@@ -57,8 +57,57 @@ def fourier_leg():
     print(f'mri4 (64 of 256 columns) B={B}: data term + last VJP {ms*1e3:.1f} us {fl/ms/1e9:.1f} TFLOP/s ({fl/1e9:.1f} GFLOP; windows '
           f'{", ".join(f"{v*1e3:.1f}" for v in ours)}), torch.fft + autograd {mst*1e3:.1f} us ({mst/ms:.2f} x ours; windows '
           f'{", ".join(f"{v*1e3:.1f}" for v in theirs)});  data term {msD*1e3:.1f} us, H {msH*1e3:.1f} us')
+# Modulated Fourier operators (operators.ModulatedFourier): mcmri4 with 8 coils (linear) and cdp4 (modulus), timed as the
+# Fourier leg is: data term + last VJP, 10 warm-up calls then 100 timed ones between two events, three windows alternating
+# with the same term written with torch.fft + autograd; medians; then the data term alone and H.  FLOP model: the chain runs
+# on the real and the imaginary plane of every modulated image, 2 x 24 d^3 = 48 d^3 per (plane, map); a complex-input chain
+# would need 32 d^3 (a complex product is four real ones of 2 d^3 FLOP, two per transform, forward and adjoint).
+# `python tools/ops_bench.py 64 modfourier` runs this leg alone.
+def modfourier_leg():
+    d = 256
+    e6 = K.randn_philox((B, 6, d, d), 1, 0, 2)
+    ge = torch.zeros_like(e6)
+    at = torch.full((B,), 0.5214230418, device=dev)
+    an = torch.ones(B, device=dev)
+    cur = K.ddim_mix_fwd(x, e6, at, an, final_clip=True)['xt_next']
+    a_, b_ = at.view(B, 1, 1, 1), an.view(B, 1, 1, 1)
+    for deg, label in (('mcmri4', 'mcmri4, 8 coils (64 of 256 columns)'), ('cdp4', 'cdp4 (4 masks, modulus)')):
+        om = operators.build_operator(deg, 3, d, dev, generator=torch.Generator().manual_seed(5678), n_coils=8)
+        Km = om.maps.shape[0]
+        ym = K.randn_philox((B, om.M), 1, 0, 5)
+        if om.modulus: ym = ym.abs()
+        W, meas, S = om.W, om.W > 0, om.maps.to(dev)
+        yo = om._observation(ym, x.shape)
+        yc = yo if om.modulus else torch.complex(*yo.unbind(3))
+        def torch_term():
+            xl, el = x.detach().requires_grad_(True), e6.detach().requires_grad_(True)
+            x0 = ((xl - el[:, :3] * (1 - a_).sqrt()) / a_.sqrt()).clamp(-1, 1)   # the last DDIM step (eta = 0), then the final clip
+            dec = (b_.sqrt() * x0 + (1 - b_).sqrt() * el[:, :3]).clamp(-1, 1)
+            z = S * dec[:, :, None]
+            Y = torch.fft.fftshift(torch.fft.fft2(torch.fft.ifftshift(z, dim=(-2, -1)), norm='ortho'), dim=(-2, -1))
+            if om.modulus:
+                loss = (torch.where(meas, yc - W * Y.abs(), torch.zeros((), device=dev)) ** 2).sum()
+            else:
+                r = torch.where(meas, yc - W * Y, torch.zeros((), dtype=yc.dtype, device=dev))
+                loss = (r.real ** 2 + r.imag ** 2).sum()
+            return torch.autograd.grad(loss, (xl, el))
+        ours, theirs = [], []
+        for _ in range(3):
+            ours.append(timed(lambda: om.fused_last_vjp(x, e6, at, an, ym, g_e_out=ge, xt_next=cur)))
+            theirs.append(timed(torch_term))
+        ms, mst = sorted(ours)[1], sorted(theirs)[1]
+        msD, msH = timed(lambda: om.data_term(x, ym, True)), timed(lambda: om.H(x))
+        fl = B * 3 * Km * 48 * d ** 3
+        print(f'{label} B={B}: data term + last VJP {ms*1e3:.1f} us {fl/ms/1e9:.1f} TFLOP/s ({fl/1e9:.1f} GFLOP at 48 d^3 per plane and map; '
+              f'windows {", ".join(f"{v*1e3:.1f}" for v in ours)}), torch.fft + autograd {mst*1e3:.1f} us ({mst/ms:.2f} x ours; windows '
+              f'{", ".join(f"{v*1e3:.1f}" for v in theirs)});  data term {msD*1e3:.1f} us, H {msH*1e3:.1f} us', flush=True)
+        del om, ym, yo, yc
+        torch.cuda.empty_cache()
 if len(sys.argv) > 2 and sys.argv[2] == 'fourier':
     fourier_leg()
+    sys.exit(0)
+if len(sys.argv) > 2 and sys.argv[2] == 'modfourier':
+    modfourier_leg()
     sys.exit(0)
 op = operators.build_operator('deblur_aniso', 3, 256, dev)
 y = K.randn_philox((B, 3, 256, 256), 1, 0, 1).reshape(B, -1)
@@ -207,3 +256,4 @@ except Exception as exc:                                         # say so, and m
     m64, t64 = timeit100(lambda: o64.data_term(x64, y64, True)), timeit100(dense_data)
     print(f'    ct32 at 64 x 64 B={B}: data term {m64*1e3:.1f} us, torch dense product + autograd {t64*1e3:.1f} us ({t64/m64:.2f} x ours)')
 fourier_leg()
+modfourier_leg()
