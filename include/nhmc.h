@@ -775,6 +775,51 @@ int nhmc_conv3x3_wino_k32_prefers(int backward, int n, int c, int k, int h, int 
 int nhmc_conv3x3_wino_up(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c, int k,
                          int h, int w, int mode, nhmc_stream_t stream);
 int nhmc_conv3x3_wino_up_covers(int n, int c, int k, int h, int w);
+/* nhmc_conv3x3_wino_skip: nhmc_conv3x3_wino whose `add` arrives without its per-channel bias (the ResBlock whose skip path
+ *   is a 1x1 convolution: that convolution runs without its bias and the broadcast pass over its output never does).
+ *   add [n][k][h][w] and add_bias [k] are both required; y = (acc + bias[k]) + (add + add_bias[k]), bias nullable: the bits
+ *   of nhmc_conv3x3_wino on an `add` to which add_bias was added in fp32 beforehand, NaN and inf included.  add may be y.
+ *   Runs on the eight-wave kernel only: nhmc_conv3x3_wino_skip_covers = nhmc_conv3x3_wino_covers and NHMC_WINO_WAVES unset
+ *   or 8; anything else is NHMC_ERR_SHAPE.  Validation order as nhmc_conv3x3_wino; a null add or add_bias is NHMC_ERR_ARG. */
+int nhmc_conv3x3_wino_skip(const float* x, const float* u, const float* bias, const float* add, const float* add_bias, float* y,
+                           int n, int c, int k, int h, int w, nhmc_stream_t stream);
+int nhmc_conv3x3_wino_skip_covers(int n, int c, int k, int h, int w);
+
+/* ------------------------------------------------------------------------------------
+ * a16 thin conv  direct 3x3 stride-1 padding-1 convolution from a thin input (c <= 8 channels) to a wide output (k a multiple
+ *      of 32) on packed fp32 FMA (csrc/thin_conv.hip): the score network's first layer and the backward-data pass of its
+ *      last one; fp32 NCHW, one launch, no workspace.
+ *   y[n][k][h][w] = sum_c sum_rs x[n][c][h + r - 1][w + s - 1] g[k][c][r][s]   (+ bias[k])
+ * nhmc_thin_in_weights: wp[wide / 2][9 thin][2], the filter re-laid-out by output-channel pairs; thin * wide * 9 floats,
+ *   a function of the weights alone (build once, reuse).
+ *   backward = 0: weight is [wide][thin][3][3] and g = weight -- the forward convolution of a thin input;
+ *   backward = 1: weight is [thin][wide][3][3] and g[k][c][r][s] = weight[c][k][2 - r][2 - s] -- the backward-data pass of
+ *   a convolution with a thin OUTPUT, dx = conv(dy, g), dy thin.
+ * nhmc_conv3x3_thin_in: x [n][c][h][w], wp from nhmc_thin_in_weights with (thin, wide) = (c, k), bias (nullable) [k],
+ *   y [n][k][h][w].  One FMA chain per output (c, then r, then s ascending; zero padding by predicate), the bias added
+ *   last; no atomics: equal inputs give equal bits.
+ *   Covered (nhmc_conv3x3_thin_in_covers = 1): n >= 1, 1 <= c <= 8, k % 32 == 0, w % 4 == 0, h * w <= 2^24; stride and
+ *   padding must both be 1.  Anything else: NHMC_ERR_SHAPE; null x / wp / y, y == x or y == wp: NHMC_ERR_ARG; x, wp or y
+ *   off 16 bytes: NHMC_ERR_ALIGN; all before any device work.
+ * nhmc_conv3x3_thin_in_prefers(backward, n, c, k, h, w): 1 when this entry measured at most 0.90 of the vendor library's
+ *   sequence for the shape and direction (c, k: the channels of the convolution that runs); the table is next to its
+ *   definition.  Only n = 64 was measured; other batch sizes follow the same rows.
+ * nhmc_thin_out_weights, nhmc_conv3x3_thin_out, _covers, _prefers: the mirror image, a wide input (c % 32 == 0) to a thin
+ *   output (k <= 8): the network's last layer and the backward-data pass of its first one.  gp[wide][9][2 ceil(thin / 2)]
+ *   (wide * 9 * 2 ceil(thin / 2) floats); backward = 0: weight is [thin][wide][3][3]; backward = 1: weight is
+ *   [wide][thin][3][3] and g[k][c][r][s] = weight[c][k][2 - r][2 - s].  x [n][c][h][w], bias (nullable) [k], y [n][k][h][w];
+ *   the same summation order, coverage conditions (with c and k exchanged), error codes and validation order.
+ * ---------------------------------------------------------------------------------- */
+int nhmc_thin_in_weights(const float* weight, float* wp, int backward, int thin, int wide, nhmc_stream_t stream);
+int nhmc_conv3x3_thin_in(const float* x, const float* wp, const float* bias, float* y, int n, int c, int k, int h, int w,
+                         int stride, int padding, nhmc_stream_t stream);
+int nhmc_conv3x3_thin_in_covers(int n, int c, int k, int h, int w);
+int nhmc_conv3x3_thin_in_prefers(int backward, int n, int c, int k, int h, int w);
+int nhmc_thin_out_weights(const float* weight, float* gp, int backward, int thin, int wide, nhmc_stream_t stream);
+int nhmc_conv3x3_thin_out(const float* x, const float* gp, const float* bias, float* y, int n, int c, int k, int h, int w,
+                          int stride, int padding, nhmc_stream_t stream);
+int nhmc_conv3x3_thin_out_covers(int n, int c, int k, int h, int w);
+int nhmc_conv3x3_thin_out_prefers(int backward, int n, int c, int k, int h, int w);
 
 /* PSNR of clamp((xt+1)/2,0,1) against clamp((x_orig+1)/2,0,1)   main_sampling.py:738-739
  * ws: double[n_chains][nhmc_data_tiles(n_elem)]. */

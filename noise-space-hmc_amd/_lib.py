@@ -127,6 +127,16 @@ SIGNATURES = {
     'nhmc_conv3x3_wino_k32_prefers': (I, [I, I, I, I, I, I]),
     'nhmc_conv3x3_wino_up': (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
     'nhmc_conv3x3_wino_up_covers': (I, [I, I, I, I, I]),
+    'nhmc_conv3x3_wino_skip': (I, [P, P, P, P, P, P, I, I, I, I, I, P]),
+    'nhmc_conv3x3_wino_skip_covers': (I, [I, I, I, I, I]),
+    'nhmc_thin_in_weights': (I, [P, P, I, I, I, P]),
+    'nhmc_conv3x3_thin_in': (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
+    'nhmc_conv3x3_thin_in_covers': (I, [I, I, I, I, I]),
+    'nhmc_conv3x3_thin_in_prefers': (I, [I, I, I, I, I, I]),
+    'nhmc_thin_out_weights': (I, [P, P, I, I, I, P]),
+    'nhmc_conv3x3_thin_out': (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
+    'nhmc_conv3x3_thin_out_covers': (I, [I, I, I, I, I]),
+    'nhmc_conv3x3_thin_out_prefers': (I, [I, I, I, I, I, I]),
     'nhmc_psnr':(I, [P, P, P, P, I, I64, P]),
     'nhmc_psnr_samples': (I, [P, P, P, P, I, I, I64, P]),
     'nhmc_ssim_tiles': (I, [I, I]),

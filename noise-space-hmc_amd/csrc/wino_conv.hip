@@ -48,6 +48,10 @@
 // adds {l.x, l.x, l.y, l.y} where it adds the float4 otherwise.  OUT_POOL: y is [n][K][H / 2][W / 2]; a lane's 2 x 2 patch
 // is one low-res pixel, stored as ((((0 + o00) + o01) + o10) + o11) * 0.25f * 4.0f, the chain of k_sr<2, 1> followed by the
 // multiplication by 4 of the upsample's backward (denormals round as there), with no exchange between lanes.
+// Skip bias (template parameter ADD_BIAS of k_conv3x3_wino8, entry nhmc_conv3x3_wino_skip; the ResBlocks whose skip path is a
+// 1x1 convolution): add is that convolution's output WITHOUT its bias and add_bias [K] the bias; the epilogue stores
+// (acc + bias[k]) + (add + add_bias[k]).  The inner add is the fp32 add of the broadcast pass that would otherwise have run
+// over add before this kernel, so every output bit is that sequence's, and the pass (one read and one write of add) is gone.
 #include "nhmc_common.h"
 
 #include <cstdlib>
@@ -93,6 +97,7 @@ __device__ int nhmc_wino_stamp_chunk;
 struct WinoArgs {
   const float* x; const float* U; const float* bias; const float* add; float* y;
   int C, K, H, W, row_blocks, col_blocks;
+  const float* add_bias;                           // ADD_BIAS only; last, so that every other field keeps its offset
 };
 
 template <int TC, bool TAIL>
@@ -449,11 +454,13 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const WinoArgs a) {
 // (tests/test_wino_exchange_cpu.py).  Each wave then runs the four-wave transform expression on its 8 channel rows.
 constexpr int WC8_XSLOTS = 16;                   // float4 per lane and wave in the exchange: 8 frequencies x 2 register quads
 
+// ADD_BIAS: add arrives without its per-channel bias a.add_bias (file header, "Skip bias").
 // IN_UP, ADD_UP, OUT_POOL: the forms next to a nearest 2x upsample (file header, "Nearest 2x upsample"): x, add or y at half
 // the resolution.  All false is the kernel described above, instruction for instruction.
-template <bool IN_UP = false, bool ADD_UP = false, bool OUT_POOL = false>
+template <bool IN_UP = false, bool ADD_UP = false, bool OUT_POOL = false, bool ADD_BIAS = false>
 __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
   static_assert(!(OUT_POOL && ADD_UP), "the pooled epilogue takes no add");
+  static_assert(!ADD_BIAS || !(IN_UP || ADD_UP || OUT_POOL), "the skip bias goes with a full-resolution add");
   constexpr int TC = 32, BLK_ROWS = 128 / TC, BLK_COLS = 2 * TC;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
@@ -710,6 +717,14 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
 #pragma unroll
     for (int rr = 0; rr < 8; ++rr) bc[rr] = a.bias[k0 + (rr & 3) + 8 * (rr >> 2)];
   }
+  // ADD_BIAS: the wave's 16 channels k0 - 4 lh .. + 15 at a wave-uniform address, so they sit in scalar registers (the
+  // epilogue has no eight vector registers to spare); a lane's row rr is entry 4 lh + (rr & 3) + 8 (rr >> 2)
+  // (read through the constant address space, which nothing writes while the kernel runs: scalar loads)
+  typedef const __attribute__((address_space(4))) float* wc_cptr;
+  const wc_cptr sbp = (wc_cptr)(uintptr_t)a.add_bias + (kb * WC_KBLK + __builtin_amdgcn_readfirstlane(kh) * 32 + 16 * fh);
+  float sb[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) sb[j] = ADD_BIAS ? sbp[j] : 0.0f;
   if (has_add) {
 #pragma unroll
     for (int rr = 0; rr < 8; ++rr) {
@@ -767,7 +782,8 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino8(const WinoArgs a) {
       const wc_v2f recv = {neighbour(give.x), neighbour(give.y)};
       nhmc_v4f v;
       v.x = odd ? recv.x : keep.x; v.y = odd ? recv.y : keep.y; v.z = odd ? keep.x : recv.x; v.w = odd ? keep.y : recv.y;
-      if (has_add) v += ADD_UP ? nhmc_v4f{al[rr].x, al[rr].x, al[rr].y, al[rr].y} : ad[rr];
+      if (ADD_BIAS) v += ad[rr] + (lh ? sb[4 + (rr & 3) + 8 * (rr >> 2)] : sb[(rr & 3) + 8 * (rr >> 2)]);            // (acc + bias) + (add + add_bias): the bias pass's own add, then today's
+      else if (has_add) v += ADD_UP ? nhmc_v4f{al[rr].x, al[rr].x, al[rr].y, al[rr].y} : ad[rr];
       __builtin_nontemporal_store(v, reinterpret_cast<nhmc_v4f*>(a.y + at0 + (int64_t)((rr & 3) + 8 * (rr >> 2)) * HW));
     }
   };
@@ -863,21 +879,21 @@ int wc_waves() {
   return -1;
 }
 
-template <bool IN_UP = false, bool ADD_UP = false, bool OUT_POOL = false>
+template <bool IN_UP = false, bool ADD_UP = false, bool OUT_POOL = false, bool ADD_BIAS = false>
 int wc_launch8(const float* x, const float* u, const float* bias, const float* add, float* y, int n, int c, int k, int h, int w,
-               nhmc_stream_t stream) {
+               nhmc_stream_t stream, const float* add_bias = nullptr) {
   static bool attr_set[64] = {};
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wino8<IN_UP, ADD_UP, OUT_POOL>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wino8<IN_UP, ADD_UP, OUT_POOL, ADD_BIAS>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, WC_LDS_BYTES) != hipSuccess)
       return NHMC_ERR_LAUNCH;
     if (dev >= 0 && dev < 64) attr_set[dev] = true;
   }
-  const WinoArgs a{x, u, bias, add, y, c, k, h, w, h / WC_ROWS, w / WC_COLS};
+  const WinoArgs a{x, u, bias, add, y, c, k, h, w, h / WC_ROWS, w / WC_COLS, add_bias};
   const int64_t blocks = (int64_t)n * a.row_blocks * a.col_blocks * (k / WC_KBLK);
-  NHMC_LAUNCH((k_conv3x3_wino8<IN_UP, ADD_UP, OUT_POOL>), dim3((unsigned)blocks), dim3(512), WC_LDS_BYTES, nhmc_s(stream), a);
+  NHMC_LAUNCH((k_conv3x3_wino8<IN_UP, ADD_UP, OUT_POOL, ADD_BIAS>), dim3((unsigned)blocks), dim3(512), WC_LDS_BYTES, nhmc_s(stream), a);
   return nhmc_launch_status();
 }
 
@@ -1063,6 +1079,20 @@ extern "C" int nhmc_conv3x3_wino_up(const float* x, const float* u, const float*
   return mode == NHMC_WINO_IN_UP    ? wc_launch8<true, false, false>(x, u, bias, add, y, n, c, k, h, w, stream)
          : mode == NHMC_WINO_ADD_UP ? wc_launch8<false, true, false>(x, u, bias, add, y, n, c, k, h, w, stream)
                                     : wc_launch8<false, false, true>(x, u, bias, add, y, n, c, k, h, w, stream);
+}
+
+// The skip-bias form of the eight-wave kernel (the paragraph "Skip bias" of the file header): add and add_bias are required.
+extern "C" int nhmc_conv3x3_wino_skip_covers(int n, int c, int k, int h, int w) {
+  return wc_covers(n, c, k, h, w) && wc_waves() == 8;
+}
+
+extern "C" int nhmc_conv3x3_wino_skip(const float* x, const float* u, const float* bias, const float* add, const float* add_bias,
+                                      float* y, int n, int c, int k, int h, int w, nhmc_stream_t stream) {
+  if (!x || !u || !y || !add || !add_bias || y == x || add == x) return NHMC_ERR_ARG;
+  if (wc_waves() < 0) return NHMC_ERR_ARG;
+  if (!wc_covers(n, c, k, h, w) || wc_waves() != 8) return NHMC_ERR_SHAPE;
+  if (!nhmc_aligned16(x) || !nhmc_aligned16(u) || !nhmc_aligned16(y) || !nhmc_aligned16(add)) return NHMC_ERR_ALIGN;
+  return wc_launch8<false, false, false, true>(x, u, bias, add, y, n, c, k, h, w, stream, add_bias);
 }
 
 extern "C" int nhmc_conv3x3_wino_narrow(const float* x, const float* u, const float* bias, const float* add, float* y, int n,

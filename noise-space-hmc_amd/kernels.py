@@ -1402,6 +1402,14 @@ def conv3x3_wino_k32_prefers(backward, n, c, k, h, w):
     return bool(_lib.load().nhmc_conv3x3_wino_k32_prefers(int(bool(backward)), n, c, k, h, w))
 
 
+def conv3x3_wino_skip_covers(n, c, k, h, w):
+    """nhmc_conv3x3_wino_skip_covers: the wide geometry on eight waves (NHMC_WINO_WAVES is read per call) and NHMC_SKIP_BIAS,
+    the A/B switch of the skip bias in the epilogue (read per call), not 0."""
+    if os.environ.get('NHMC_SKIP_BIAS', '1') == '0' or _wino_narrow(w):
+        return False
+    return bool(_lib.load().nhmc_conv3x3_wino_skip_covers(n, c, k, h, w))
+
+
 def conv3x3_wino(x, weight, bias=None, add=None, backward=False):
     """conv2d(x, weight, stride 1, padding 1) (+ bias[k]) (+ add) on the Winograd MFMA kernel; backward=True: the
     backward-data pass of that convolution, x being the output gradient [N, K, H, W] -> [N, C, H, W].
@@ -1421,6 +1429,124 @@ def conv3x3_wino(x, weight, bias=None, add=None, backward=False):
     rc = getattr(lib, entry)(_p(x, torch.float32, 'x'), _p(u), _p(bias, torch.float32, 'bias'), _p(add, torch.float32, 'add'),
                              _p(y), N, Cc, Kk, H, W, 1, 1, _stream())
     _lib.check(rc, entry)
+    return y
+
+
+_thin_w = {}          # (id(weight), backward, thin output?) -> (weakref to it, its version counter, data_ptr, wp on its device)
+_thin_builds = 0
+
+
+def thin_weight_builds():
+    """How many times a re-laid-out thin filter was built (tests: once per weight tensor and direction)."""
+    return _thin_builds
+
+
+def thin_in_weights(weight, backward=False, out=False):
+    """wp [wide / 2][9 thin][2] of a filter for conv3x3_thin_in (nhmc_thin_in_weights): weight is [wide, thin, 3, 3] forward,
+    [thin, wide, 3, 3] for backward=True (the backward-data pass of a convolution with a thin output).  Cached like
+    wino_weights: per live weight tensor, version counter and storage address.
+    out=True: gp [wide][9][2 ceil(thin / 2)] for conv3x3_thin_out (nhmc_thin_out_weights): weight is [thin, wide, 3, 3]
+    forward, [wide, thin, 3, 3] for backward=True."""
+    global _thin_builds
+    key = (id(weight), bool(backward), bool(out))
+    hit = _thin_w.get(key)
+    if hit is not None and hit[0]() is weight and hit[1] == weight._version and hit[2] == weight.data_ptr():
+        return hit[3]
+    import weakref
+    lib = _lib.load()
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise _lib.NhmcError(f'thin_in_weights: a [K, C, 3, 3] filter is needed, got {tuple(weight.shape)}')
+    thin, wide = (weight.shape[0], weight.shape[1]) if bool(backward) != bool(out) else (weight.shape[1], weight.shape[0])
+    if not 1 <= thin <= 8 or wide % 32:
+        raise _lib.NhmcError(f'thin_in_weights: a thin side of at most 8 and a wide side that is a multiple of 32 are needed, '
+                             f'got {thin} and {wide}')
+    wd = weight.detach()
+    wp = torch.empty((wide, 9, 2 * ((thin + 1) // 2)) if out else (wide // 2, 9 * thin, 2), dtype=torch.float32, device=weight.device)
+    entry = 'nhmc_thin_out_weights' if out else 'nhmc_thin_in_weights'
+    _lib.check(getattr(lib, entry)(_p(wd, torch.float32, 'weight'), _p(wp), int(bool(backward)), thin, wide, _stream()), entry)
+    _thin_builds += 1
+    for k in [k for k, v in _thin_w.items() if v[0]() is None]:
+        del _thin_w[k]
+    _thin_w[key] = (weakref.ref(weight), weight._version, weight.data_ptr(), wp)
+    return wp
+
+
+def conv3x3_thin_in_covers(n, c, k, h, w):
+    return bool(_lib.load().nhmc_conv3x3_thin_in_covers(n, c, k, h, w))
+
+
+def conv3x3_thin_in_prefers(backward, n, c, k, h, w):
+    """The library's routing rule (nhmc_conv3x3_thin_in_prefers); NHMC_THIN_CONV=0 (the A/B switch, read per call) answers no."""
+    if os.environ.get('NHMC_THIN_CONV', '1') == '0':
+        return False
+    return bool(_lib.load().nhmc_conv3x3_thin_in_prefers(int(bool(backward)), n, c, k, h, w))
+
+
+def conv3x3_thin_in(x, weight, bias=None, backward=False):
+    """conv2d(x, weight, stride 1, padding 1) (+ bias[k]) of a thin input x [N, C <= 8, H, W] to a wide output on the packed-FMA
+    kernel (csrc/thin_conv.hip); backward=True: the backward-data pass of a convolution with a thin output, x being its
+    output gradient [N, K <= 8, H, W] -> [N, C, H, W]."""
+    lib = _lib.load()
+    if x.dim() != 4 or weight.dim() != 4 or x.shape[1] != weight.shape[0 if backward else 1]:
+        raise _lib.NhmcError(f'conv3x3_thin_in: x {tuple(x.shape)} does not match the filter {tuple(weight.shape)}')
+    wp = thin_in_weights(weight, backward)
+    N, Cc, H, W = x.shape
+    Kk = 2 * wp.shape[0]
+    if bias is not None and bias.numel() != Kk:
+        raise _lib.NhmcError('conv3x3_thin_in: bias does not match the output')
+    y = torch.empty((N, Kk, H, W), dtype=torch.float32, device=x.device)
+    rc = lib.nhmc_conv3x3_thin_in(_p(x, torch.float32, 'x'), _p(wp), _p(bias, torch.float32, 'bias'), _p(y), N, Cc, Kk, H, W,
+                                  1, 1, _stream())
+    _lib.check(rc, 'nhmc_conv3x3_thin_in')
+    return y
+
+
+def conv3x3_thin_out_covers(n, c, k, h, w):
+    return bool(_lib.load().nhmc_conv3x3_thin_out_covers(n, c, k, h, w))
+
+
+def conv3x3_thin_out_prefers(backward, n, c, k, h, w):
+    """nhmc_conv3x3_thin_out_prefers; NHMC_THIN_CONV=0 answers no."""
+    if os.environ.get('NHMC_THIN_CONV', '1') == '0':
+        return False
+    return bool(_lib.load().nhmc_conv3x3_thin_out_prefers(int(bool(backward)), n, c, k, h, w))
+
+
+def conv3x3_thin_out(x, weight, bias=None, backward=False):
+    """conv2d(x, weight, stride 1, padding 1) (+ bias[k]) of a wide input x [N, C, H, W] to a thin output (K <= 8) on the
+    packed-FMA kernel; backward=True: the backward-data pass of a convolution with a thin input, x being its output gradient
+    [N, K, H, W] (K wide) -> [N, C <= 8, H, W]."""
+    lib = _lib.load()
+    if x.dim() != 4 or weight.dim() != 4 or x.shape[1] != weight.shape[0 if backward else 1]:
+        raise _lib.NhmcError(f'conv3x3_thin_out: x {tuple(x.shape)} does not match the filter {tuple(weight.shape)}')
+    gp = thin_in_weights(weight, backward, out=True)
+    N, Cc, H, W = x.shape
+    Kk = weight.shape[1 if backward else 0]
+    if bias is not None and bias.numel() != Kk:
+        raise _lib.NhmcError('conv3x3_thin_out: bias does not match the output')
+    y = torch.empty((N, Kk, H, W), dtype=torch.float32, device=x.device)
+    rc = lib.nhmc_conv3x3_thin_out(_p(x, torch.float32, 'x'), _p(gp), _p(bias, torch.float32, 'bias'), _p(y), N, Cc, Kk, H, W,
+                                   1, 1, _stream())
+    _lib.check(rc, 'nhmc_conv3x3_thin_out')
+    return y
+
+
+def conv3x3_wino_skip(x, weight, bias, add, add_bias):
+    """conv3x3_wino(x, weight, bias, add + add_bias[k]) without the pass that adds add_bias to `add` [N, K, H, W]: the
+    kernel's epilogue forms (acc + bias[k]) + (add + add_bias[k]), the same bits (nhmc_conv3x3_wino_skip; forward filter,
+    where conv3x3_wino_skip_covers)."""
+    lib = _lib.load()
+    if x.dim() != 4 or weight.dim() != 4 or x.shape[1] != weight.shape[1]:
+        raise _lib.NhmcError(f'conv3x3_wino_skip: x {tuple(x.shape)} does not match the filter {tuple(weight.shape)}')
+    u = wino_weights(weight, False)
+    N, Cc, H, W = x.shape
+    Kk = u.shape[2]
+    y = torch.empty((N, Kk, H, W), dtype=torch.float32, device=x.device)
+    if (bias is not None and bias.numel() != Kk) or add is None or add.shape != y.shape or add_bias is None or add_bias.numel() != Kk:
+        raise _lib.NhmcError('conv3x3_wino_skip: bias / add / add_bias do not match the output')
+    rc = lib.nhmc_conv3x3_wino_skip(_p(x, torch.float32, 'x'), _p(u), _p(bias, torch.float32, 'bias'), _p(add, torch.float32, 'add'),
+                                    _p(add_bias, torch.float32, 'add_bias'), _p(y), N, Cc, Kk, H, W, _stream())
+    _lib.check(rc, 'nhmc_conv3x3_wino_skip')
     return y
 
 

@@ -187,17 +187,18 @@ class _Conv3x3Wino(torch.autograd.Function):
     """A frozen 3x3 stride-1 padding-1 convolution (+ bias_k) (+ add) whose forward and / or backward-data pass runs on the
     Winograd MFMA kernel (csrc/wino_conv.hip); `route` = (forward, backward) says which.  A pass that is not routed runs
     the vendor library's kernel, as F.conv2d and its autograd node would.  Saves the filter only: there is no weight
-    gradient, and the gradient reaches `add` unchanged."""
+    gradient, and the gradient reaches `add` unchanged.  `add_bias` (a routed forward only, conv_bias_add2_skip): `add` is a
+    skip convolution's output without its bias, which the kernel's epilogue adds to it."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, add, route):
+    def forward(ctx, x, weight, bias, add, route, add_bias=None):
         xc = x if x.is_contiguous() else x.contiguous()
         if add is not None and not add.is_contiguous():
             add = add.contiguous()
         ctx.save_for_backward(weight)
         ctx.route_bwd, ctx.x_shape = route[1], tuple(x.shape)
         if route[0]:
-            return K.conv3x3_wino(xc, weight, bias, add)
+            return K.conv3x3_wino(xc, weight, bias, add) if add_bias is None else K.conv3x3_wino_skip(xc, weight, bias, add, add_bias)
         if add is None:                                     # bias-only callers (conv_bias): the vendor kernel adds it
             return F.conv2d(xc, weight, bias, 1, 1)
         return K.bias_add2(F.conv2d(xc, weight, None, 1, 1), bias, add)
@@ -210,7 +211,7 @@ class _Conv3x3Wino(torch.autograd.Function):
             gc = g if g.is_contiguous() else g.contiguous()
             dx = K.conv3x3_wino(gc, weight, backward=True) if ctx.route_bwd \
                 else torch.nn.grad.conv2d_input(ctx.x_shape, weight, gc, 1, 1)
-        return dx, None, None, (g if ctx.needs_input_grad[3] else None), None
+        return dx, None, None, (g if ctx.needs_input_grad[3] else None), None, None
 
 
 def wino_route(conv, x, wino=None, up=False):
@@ -287,6 +288,66 @@ class _Conv3x3WinoAddUp(torch.autograd.Function):
         return dx, None, None, dadd, None
 
 
+class _Conv3x3Thin(torch.autograd.Function):
+    """A frozen 3x3 stride-1 padding-1 convolution (+ bias_k) with a thin side (at most 8 channels) whose forward and / or
+    backward-data pass runs on the direct packed-FMA kernels (csrc/thin_conv.hip); `route` = (forward, backward) says which.
+    The pass whose input is thin (forward of 3 -> 128, backward-data of 128 -> 6) runs the thin-input kernel, the other one
+    the thin-output kernel.  A pass that is not routed is the vendor library's call, as F.conv2d and its autograd node make
+    it.  Saves the filter only: there is no weight gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, route):
+        xc = x if x.is_contiguous() else x.contiguous()
+        ctx.save_for_backward(weight)
+        ctx.route_bwd, ctx.x_shape = route[1], tuple(x.shape)
+        if not route[0]:
+            return F.conv2d(xc, weight, bias, 1, 1)
+        return (K.conv3x3_thin_in if weight.shape[1] <= 8 else K.conv3x3_thin_out)(xc, weight, bias)
+
+    @staticmethod
+    def backward(ctx, g):
+        (weight,) = ctx.saved_tensors
+        dx = None
+        if ctx.needs_input_grad[0]:
+            gc = g if g.is_contiguous() else g.contiguous()
+            dx = (K.conv3x3_thin_in if weight.shape[0] <= 8 else K.conv3x3_thin_out)(gc, weight, backward=True) if ctx.route_bwd \
+                else torch.nn.grad.conv2d_input(ctx.x_shape, weight, gc, 1, 1)
+        return dx, None, None, None
+
+
+def thin_route(conv, x, thin=None):
+    """(forward, backward) routing of `conv` applied to x onto the thin kernels, or None when the module call stays: a
+    frozen 3x3 stride-1 padding-1 convolution of fp32 GPU activations with at most 8 channels on one side and a multiple of
+    32 on the other, each direction where the kernel that serves it covers the shape and the library's measured table
+    prefers it (thin=True: wherever it is covered -- tests).  NHMC_THIN_CONV=0, read per call, keeps the vendor library."""
+    if thin is False or x.dim() != 4 or not fused_glue(x, conv.weight, conv.bias) or os.environ.get('NHMC_THIN_CONV', '1') == '0':
+        return None
+    if tuple(conv.kernel_size) != (3, 3) or tuple(conv.stride) != (1, 1) or conv.padding != (1, 1) \
+            or tuple(conv.dilation) != (1, 1) or conv.groups != 1 or conv.padding_mode != 'zeros':
+        return None
+    n, c, h, w = x.shape
+    k = conv.out_channels
+    if c <= 8:                                          # thin -> wide: thin-input forward, thin-output backward-data
+        fwd, bwd = K.conv3x3_thin_in_covers(n, c, k, h, w), K.conv3x3_thin_out_covers(n, k, c, h, w)
+        if not thin:
+            fwd, bwd = fwd and K.conv3x3_thin_in_prefers(0, n, c, k, h, w), bwd and K.conv3x3_thin_out_prefers(1, n, k, c, h, w)
+    else:
+        fwd, bwd = K.conv3x3_thin_out_covers(n, c, k, h, w), K.conv3x3_thin_in_covers(n, k, c, h, w)
+        if not thin:
+            fwd, bwd = fwd and K.conv3x3_thin_out_prefers(0, n, c, k, h, w), bwd and K.conv3x3_thin_in_prefers(1, n, k, c, h, w)
+    bwd = bwd and x.requires_grad and torch.is_grad_enabled()
+    return (fwd, bwd) if fwd or bwd else None
+
+
+def conv_thin(conv, x, thin=None):
+    """conv(x) for the network's first and last convolution: on the thin kernels where thin_route says so, the plain
+    module call otherwise."""
+    route = thin_route(conv, x, thin)
+    if route is not None:
+        return _Conv3x3Thin.apply(x, conv.weight, conv.bias, route)
+    return conv(x)
+
+
 def conv_nobias(conv, x, wino=None):
     """The convolution without its bias (the fused glue adds it where the output is consumed)."""
     route = wino_route(conv, x, wino)
@@ -311,6 +372,22 @@ def conv_bias_add2(conv, x, other, wino=None):
     if route is not None and route[0]:
         return _Conv3x3Wino.apply(x, conv.weight, conv.bias, other, route)
     return _BiasAdd2.apply(conv_nobias(conv, x, wino), conv.bias, other)
+
+
+def conv_bias_add2_skip(conv, x, skip, sx, wino=None):
+    """conv_bias_add2(conv, x, skip(sx)) for a ResBlock's skip path `skip`.  Where that is a frozen 1x1 convolution with a
+    bias and `conv`'s forward pass runs on the eight-wave Winograd kernel, the skip convolution runs without its bias and
+    the kernel's epilogue adds it, (acc + bias) + (skip + skip_bias): the vendor path's broadcast pass over the skip
+    tensor (`output.add_(bias)` behind its GEMM) computed the same inner fp32 add, so the bits are unchanged and the pass
+    is gone.  NHMC_SKIP_BIAS=0 (read per call) keeps the pass; so do the narrow geometries, four waves and k_bias_add2."""
+    route = wino_route(conv, x, wino)
+    if route is not None and route[0] and isinstance(skip, nn.Conv2d) and skip.bias is not None \
+            and tuple(skip.kernel_size) == (1, 1) and tuple(skip.stride) == (1, 1) and skip.padding == (0, 0) \
+            and tuple(skip.dilation) == (1, 1) and skip.groups == 1 and skip.out_channels == conv.out_channels \
+            and fused_glue(sx, skip.weight, skip.bias) and sx.shape[2:] == x.shape[2:] \
+            and K.conv3x3_wino_skip_covers(x.shape[0], x.shape[1], conv.out_channels, x.shape[2], x.shape[3]):
+        return _Conv3x3Wino.apply(x, conv.weight, conv.bias, F.conv2d(sx, skip.weight, None), route, skip.bias)
+    return conv_bias_add2(conv, x, skip(sx), wino)
 
 
 class _Resample2x(torch.autograd.Function):
@@ -407,7 +484,7 @@ class ResBlock(nn.Module):
             # the two convolutions run without their broadcast bias passes: conv1's bias enters the next GroupNorm's
             # load, conv2's the residual add
             h = group_norm_act(self.out_layers[0], conv_nobias(conv1, h, self.wino), film=film, pre=conv1.bias)
-            return conv_bias_add2(conv2, h, self.skip_connection(x), self.wino)
+            return conv_bias_add2_skip(conv2, h, self.skip_connection, x, self.wino)
         h = group_norm_act(self.out_layers[0], conv1(h), film=film)      # scale-shift norm (FiLM) + SiLU
         return self.skip_connection(x) + conv2(h)
 
@@ -437,7 +514,10 @@ class AttentionBlock(nn.Module):
 class Stage(nn.Sequential):
     def forward(self, x, emb):
         for layer in self:
-            x = layer(x, emb) if getattr(layer, 'takes_emb', False) else layer(x)
+            if isinstance(layer, nn.Conv2d):                    # input_blocks[0]: the network's first, thin convolution
+                x = conv_thin(layer, x)
+            else:
+                x = layer(x, emb) if getattr(layer, 'takes_emb', False) else layer(x)
         return x
 
 
@@ -490,7 +570,7 @@ class UNetModel(nn.Module):
         for blk in self.output_blocks:
             # the pair goes to the block's first GroupNorm kernel, which forms the concatenation as a by-product
             h = blk((h, hs.pop()) if fused_glue(h) else torch.cat([h, hs.pop()], dim=1), emb)
-        return self.out[2](group_norm_act(self.out[0], h))
+        return conv_thin(self.out[2], group_norm_act(self.out[0], h))
 
 
 def create_model(image_size=256, num_channels=128, num_res_blocks=1, channel_mult='', learn_sigma=True,

@@ -22,7 +22,7 @@ src, tag = sys.argv[1], sys.argv[2]
 here = os.path.dirname(os.path.abspath(__file__))
 OURS = ('k_leapfrog', 'k_mix_', 'k_map_back', 'k_vq_', 'k_gn_', 'k_pair', 'k_data_inpaint', 'k_inpaint', 'k_sr', 'k_sgemm', 'k_sum_partials',
         'k_hamiltonian', 'k_metropolis', 'k_schedule', 'k_accept_commit', 'k_psnr', 'k_randn', 'k_uniform',
-        'k_color', 'k_fwht', 'k_cs_', 'k_copy_probe', 'k_latent', 'k_mass', 'k_rank', 'k_conv3x3_wino', 'k_wino_weights')
+        'k_color', 'k_fwht', 'k_cs_', 'k_copy_probe', 'k_latent', 'k_mass', 'k_rank', 'k_conv3x3_wino', 'k_wino_weights', 'k_conv3x3_thin', 'k_thin_in_weights')
 
 
 def short(name):

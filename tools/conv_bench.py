@@ -6,7 +6,7 @@ median of 3 rounds of 10 event-timed launches per variant on rotating buffers th
 Cache.  Prints microseconds, the ratio kernel / F.conv2d and
 TFLOP/s in direct-convolution terms (2 * 9 * N * C * K * H * W).  Rows at or below 0.90 are what
 nhmc_conv3x3_wino_prefers and nhmc_conv3x3_wino_narrow_prefers may list.
-Usage: python tools/conv_bench.py [chains] [rounds] [--epilogue] [--only=C,K,res] [--latent] [--up]
+Usage: python tools/conv_bench.py [chains] [rounds] [--epilogue] [--only=C,K,res] [--latent] [--up] [--skip-bias]
 --epilogue adds, per forward row, the kernel with its (acc + bias) + add epilogue against kernel + k_bias_add2.
 --latent measures the latent sampler's two networks instead (ldm.conv3x3_shapes; chains defaults to 16, the chain count of
 BASELINE configs[4]): the score network's covered shapes forward only (it is evaluated without gradient), the first-stage
@@ -16,7 +16,11 @@ list; the others go to the two tables above.
 passes that carry a nearest 2x upsample to the convolution against the kernel's upsample forms (nhmc_conv3x3_wino_up), both
 alternating in one process: conv1 forward, sr_Ht + kernel against IN_UP on the low-res tensor; conv2 forward with its
 residual, sr_Ht + kernel with bias and add against ADD_UP; conv1 backward-data, kernel + sr_H + mul_(4) against OUT_POOL.
-Prints microseconds of each, the ratio fused / materialised, and the convolution alone for scale."""
+Prints microseconds of each, the ratio fused / materialised, and the convolution alone for scale.
+--skip-bias times conv2's forward pass of the ResBlocks whose skip path is a 1x1 convolution and whose conv2 runs on the wide
+kernel (skip_shapes(); --only=C,K,res overrides), both alternating in one process: the broadcast bias pass over the skip
+tensor (`s.add_(b1)`, what the vendor path runs behind its GEMM) + the kernel with bias and add, against the kernel with the
+skip bias in its epilogue (nhmc_conv3x3_wino_skip).  Prints microseconds of each, the ratio, and the bias pass alone."""
 import sys
 import torch
 import torch.nn.functional as F
@@ -101,6 +105,52 @@ def up_mode(B, ROUNDS, only):
         del lows, fulls, grads, adds, w
 
 
+def skip_shapes(chains=64):
+    """(C, K, resolution) of conv2 of every ResBlock of FFHQ_CONFIG with a 1x1 skip convolution that the skip-bias form covers."""
+    with torch.device('meta'):
+        model = unet.create_model(**unet.FFHQ_CONFIG)
+    seen, hooks = [], []
+    for mod in model.modules():
+        if isinstance(mod, unet.ResBlock) and isinstance(mod.skip_connection, torch.nn.Conv2d):
+            hooks.append(mod.register_forward_hook(
+                lambda m, args, out: seen.append((m.out_layers[3].in_channels, m.out_layers[3].out_channels, out.shape[-1]))))
+    size = unet.FFHQ_CONFIG['image_size']
+    with torch.no_grad():
+        model(torch.empty(1, 3, size, size, device='meta'), torch.zeros(1, device='meta'))
+    for h in hooks:
+        h.remove()
+    return tuple((c, k, res, seen.count((c, k, res))) for c, k, res in sorted(set(seen), key=lambda s: -s[2])
+                 if K.conv3x3_wino_skip_covers(chains, c, k, res, res))
+
+
+def skip_mode(B, ROUNDS, only):
+    """--skip-bias: see the module docstring."""
+    dev = torch.device('cuda')
+    print(f'chains {B}, rounds {ROUNDS}: us bias pass + kernel | us fused | ratio (best of rounds) | us bias pass alone | blocks per evaluation')
+    for Cc, Kk, res, count in [o + (0,) for o in only] or skip_shapes(B):
+        w = torch.randn(Kk, Cc, 3, 3, device=dev) / (9 * Cc) ** 0.5
+        b2, b1 = torch.randn(Kk, device=dev), torch.randn(Kk, device=dev)
+        nbuf = max(2, -(-(320 << 20) // (B * min(Cc, Kk) * res * res * 4)))
+        bufs = [(torch.randn(B, Cc, res, res, device=dev), torch.randn(B, Kk, res, res, device=dev)) for _ in range(nbuf)]
+        b1v = b1.view(1, -1, 1, 1)
+        split = lambda t: K.conv3x3_wino(t[0], w, b2, t[1].add_(b1v))
+        fused = lambda t: K.conv3x3_wino_skip(t[0], w, b2, t[1], b1)
+        alone = lambda t: t[1].add_(b1v)
+        for _ in range(100 // nbuf + 1):
+            for t in bufs:
+                split(t)
+                fused(t)
+        ts, tf, ta = [], [], []
+        for _ in range(ROUNDS):
+            ts.append(timeit(split, bufs))
+            tf.append(timeit(fused, bufs))
+            ta.append(timeit(alone, bufs))
+        med = lambda v: sorted(v)[len(v) // 2]
+        print(f'[{B},{Cc}->{Kk},{res}x{res}] conv2 fwd: {med(ts) * 1e3:8.0f} | {med(tf) * 1e3:8.0f} | {med(tf) / med(ts):.3f} '
+              f'({min(tf) / min(ts):.3f}) | {med(ta) * 1e3:8.0f} | {count}', flush=True)
+        del bufs, w
+
+
 def timeit(f, bufs, n=10):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -118,6 +168,8 @@ def main():
     B = int(args[0]) if len(args) > 0 else 16 if LATENT else 64
     ROUNDS = int(args[1]) if len(args) > 1 else 3
     EPILOGUE = '--epilogue' in sys.argv
+    if '--skip-bias' in sys.argv:
+        return skip_mode(B, ROUNDS, [tuple(int(v) for v in a[7:].split(',')) for a in sys.argv[1:] if a.startswith('--only=')])
     if '--up' in sys.argv:
         return up_mode(B, ROUNDS, [tuple(int(v) for v in a[7:].split(',')) for a in sys.argv[1:] if a.startswith('--only=')])
     SHAPES = latent_shapes(B) if LATENT else tuple(s + ((False, True),) for s in default_shapes(B))
